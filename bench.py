@@ -5,16 +5,23 @@ Metric : CSR SpMV GB/s on the 27-pt 3-D Laplacian 256^3, fp64 values / int32
          indices (configs[1]); one "step" = one y = A x over the whole matrix
          with all operands resident in HBM.  GB/s = ALGORITHMIC bytes / time:
          nnz*(8+4) + (n+1)*4 + 8*n (x once) + 8*n (y)   (SURVEY.md 8(d)).
-Extras : CG iterations/s for configs[2] (CG + block-Jacobi(8), same matrix),
-         `roofline` for the SpMV kernel (HIP events on the launch stream),
+         A plain run measures this and nothing else; `roofline` for the SpMV
+         kernel comes from HIP events around the same timed steps.
+--full : the extras - CG iterations/s for configs[2] (CG + block-Jacobi(8),
+         same matrix) and Gmres(30); the SpMV's HBM traffic from rocprofv3
+         --pmc passes and the read ceiling measured on the same buffers;
          `cpu_baseline` (the reference's OmpExecutor from oracle/_ref when
          present, else the plain-C oracle) on a bounded sample, and `ginkgo_api`:
          the same SpMV and CG through the UNMODIFIED Ginkgo core on the drop-in
-         backend (gko::HipExecutor, tests/dropin/dropin_bench.cpp).
+         backend (gko::HipExecutor, tests/dropin/dropin_bench.cpp); at N > 1
+         PipeCg, rank 0's profile and the carried CPU baseline.
 N > 1  : the 256^3 problem is row-partitioned into z-slabs (strong scaling),
          one process per GPU, halo exchange + all-reduce over RCCL.
+--dump-outputs DIR: after the timed steps, y of the last step as DIR/y.npy
+         (float64; a fixed sample of rows for large grids, see dump_outputs).
 
-usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--grid G]
+usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--grid G] [--full]
+                       [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -27,6 +34,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X spec, /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_ROWS = 1 << 21    # rows of y written by --dump-outputs: 16 MB in float64
 
 
 def _sig3(v, digits=3):
@@ -37,6 +45,29 @@ def _sig3(v, digits=3):
 def spmv_algorithmic_bytes(n_rows, n_cols, nnz, val_bytes=8, idx_bytes=4):
     return nnz * (val_bytes + idx_bytes) + (n_rows + 1) * idx_bytes + \
         n_cols * val_bytes + n_rows * val_bytes
+
+
+def dump_outputs(out_dir, y, n_global, row0, all_reduce=None):
+    """--dump-outputs: y of the last timed step as out_dir/y.npy (float64) at every row when there are at
+    most DUMP_ROWS of them, else at DUMP_ROWS rows drawn with numpy's default_rng(0) and sorted.  The rows
+    depend on n_global only, so every build and every rank count writes the same ones.  `y` holds the global
+    rows row0 .. row0 + len - 1; at N > 1 `all_reduce` sums the ranks' parts (each one zero elsewhere) and
+    only the caller with `out_dir` set writes."""
+    import numpy as np
+    import torch
+    if n_global <= DUMP_ROWS:
+        rows = np.arange(n_global)
+    else:
+        rows = np.sort(np.random.default_rng(0).choice(n_global, DUMP_ROWS, replace=False))
+    v = y.values[:, 0]
+    mine = np.nonzero((rows >= row0) & (rows < row0 + v.shape[0]))[0]
+    sample = torch.zeros(len(rows), dtype=torch.float64, device=v.device)
+    sample[torch.from_numpy(mine).to(v.device)] = v[torch.from_numpy(rows[mine] - row0).to(v.device)].double()
+    if all_reduce is not None:
+        all_reduce(sample)
+    if out_dir:
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "y.npy"), sample.cpu().numpy())
 
 
 def _cpu_model():
@@ -564,10 +595,17 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--grid", type=int, default=256)
+    ap.add_argument("--full", action="store_true",
+                    help="the 27-pt runs: also measure the extras (CG / Gmres / PipeCg iterations/s, PMC traffic, "
+                         "measured read ceiling, CPU baseline, Ginkgo-API figures, rank 0's profile); a plain run "
+                         "times the SpMV only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write y of the last timed step to DIR/y.npy (float64; a fixed sample of "
+                         f"{DUMP_ROWS} rows beyond that many)")
     ap.add_argument("--cg-iters", type=int, default=100,
-                    help="fixed CG iterations timed for the iters/s figure")
+                    help="with --full: fixed CG iterations timed for the iters/s figure")
     ap.add_argument("--gmres-iters", type=int, default=60,
-                    help="fixed Gmres(30) + block-Jacobi(8) iterations timed at N = 1 (0 = skip)")
+                    help="with --full: fixed Gmres(30) + block-Jacobi(8) iterations timed at N = 1 (0 = skip)")
     ap.add_argument("--cpu-grid", type=int, default=0,
                     help="0 = the CPU baseline runs the GPU run's grid; otherwise this one")
     ap.add_argument("--no-cpu", action="store_true")
@@ -597,6 +635,10 @@ def main():
                     help="GKOC_ARENA mode of the library's allocator: 2 = memory-class regions "
                          "(default), 1 = plain chunks, 0 = one hipMalloc per array (DESIGN.md 3.2)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.matrix or args.workload):
+        ap.error("--dump-outputs is for the 27-pt runs, not --matrix / --workload")
     if args.cpu_baseline_child:
         return cpu_baseline_child(int(args.cpu_baseline_child[0]), float(args.cpu_baseline_child[1]))
     if args.arena is not None:
@@ -607,6 +649,10 @@ def main():
         return self_launch(args.gpus)
     if args.matrix or args.workload in ("flan", "irregular"):
         return matrix_bench(args)
+    if not args.full:
+        # a plain run does what its headline needs and nothing more: every other leg is --full's
+        args.cg_iters = args.gmres_iters = 0
+        args.no_pmc = args.no_cpu = args.no_ginkgo_api = True
 
     # stdout carries exactly one line, the JSON result: everything else written to
     # file descriptor 1 by this process (RCCL prints a version banner there from C
@@ -767,8 +813,16 @@ def main():
         step = lambda: op.apply(x, y)
 
     total_bytes = spmv_algorithmic_bytes(n_global, n_global, nnz_global)
-    dist_profile = op.profile(x, y) if use_dist else None
+    dist_profile = op.profile(x, y) if use_dist and args.full else None
 
+    if not use_dist:
+        # an idle MI355X needs ~20 ms of load to reach its clocks (profiles/r05_ginkgo_api_timeline.txt): the
+        # product runs for 0.2 s before the warm-up steps, whether or not a CG warm-up solve came before
+        t_ramp = time.perf_counter()
+        while time.perf_counter() - t_ramp < 0.2:
+            for _ in range(10):
+                step()
+            torch.cuda.synchronize()
     for _ in range(args.warmup):
         step()
     barrier()
@@ -787,6 +841,10 @@ def main():
     wall = float(t.item())
     ms_per_step = wall * 1e3 / args.steps
     gbs = total_bytes / (wall / args.steps) / 1e9
+    if args.dump_outputs:
+        row0 = 0 if not use_dist else part.range_of(rank)[0]
+        dump_outputs(args.dump_outputs if rank == 0 else None, y, n_global, row0,
+                     dist.all_reduce if use_dist else None)
 
     # ---- CG + block-Jacobi(8) iterations/s (configs[2]), fixed iteration count
     cg = {}
@@ -902,7 +960,7 @@ def main():
                          "algorithmic_bytes_per_launch": int(per_gpu_bytes)},
         }
         out.update(cg)
-        if not use_dist:
+        if not use_dist and args.full:
             try:
                 pk = measured_peaks(g, ex, torch, a, y)
                 out["roofline"]["peak_measured"] = pk["read_gbs"]
@@ -969,7 +1027,7 @@ def main():
                 json.dump(out["cpu_baseline"], open(cache, "w"))
             except OSError:
                 pass
-        elif use_dist:
+        elif use_dist and args.full:
             # no CPU twin at N > 1 (the baseline is one host running the whole problem): the N = 1
             # figure is carried - this host's, if an N = 1 run left it here, else the committed one
             base, src = None, None

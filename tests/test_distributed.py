@@ -99,7 +99,7 @@ def _bench(world, args, env_extra, timeout=1500):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
            f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(world)] + args
+           "--gpus", str(world), "--full"] + args
     env = dict(os.environ, OMP_NUM_THREADS="1", HSA_ENABLE_IPC_MODE_LEGACY="0", **env_extra)
     if world > 2 and env.get("GKO_BENCH_BACKEND") == "gloo":
         env.setdefault("GKOC_ARENA_MAX_WALK", "24")      # ranks sharing one GPU: short surveys (see _launch)
@@ -219,7 +219,7 @@ def test_bench_starts_its_own_ranks_and_the_line_has_every_key():
     roofline, the communicator check and what every rank's allocator found."""
     import json
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--grid", "32", "--steps", "3",
-           "--warmup", "1", "--cg-iters", "10"]
+           "--warmup", "1", "--cg-iters", "10", "--full"]
     env = dict(os.environ, OMP_NUM_THREADS="1", HSA_ENABLE_IPC_MODE_LEGACY="0", GKO_BENCH_BACKEND="gloo")
     env.setdefault("GKOC_ARENA_MAX_WALK", "24")          # eight ranks on one GPU: short surveys (see _launch)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
@@ -260,6 +260,27 @@ def test_bench_configs4_irregular_stand_in_one_and_eight_ranks():
     assert max(r["nnz"] for r in pr) <= 1.3 * sum(r["nnz"] for r in pr) / 8
     assert d8["formats"]["csr"]["peers"] == 7                     # the hubs reach every rank
     assert d8["cg"]["csr"]["cg_iterations"] == 10 and d8["cg"]["sellp"]["cg_iterations"] == 10
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_spmv_only_and_dumps_y(tmp_path, oracle):
+    """a plain run (no --full) prints the headline and no extra leg; --dump-outputs writes y of the last timed
+    step: the oracle's product of the 27-pt matrix with the seeded x, bit for bit on one rank, to rounding in the
+    boundary rows of two ranks"""
+    G = 32
+    d = _bench_plain(["--grid", str(G), "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "one")])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert (d["unit"], d["higher_is_better"], d["dtype"]) == ("GB/s", True, "f64")
+    assert not {"cg_iterations", "gmres_iterations", "cpu_baseline", "ginkgo_api"} & set(d), sorted(d)
+    assert "peak_measured" not in d["roofline"] and d["roofline"]["kernel_ms"] > 0
+    rp, ci, v = oracle.stencil_csr(3, G)
+    want = oracle.csr_spmv(rp, ci, v, np.random.default_rng(42).uniform(-1, 1, G ** 3))
+    y1 = np.load(tmp_path / "one" / "y.npy")
+    assert y1.dtype == np.float64 and np.array_equal(y1, want)
+    d2 = _bench_plain(["--gpus", "2", "--grid", str(G), "--steps", "3", "--warmup", "1",
+                       "--dump-outputs", str(tmp_path / "two")], {"GKO_BENCH_BACKEND": "gloo"})
+    assert d2["n_gpus"] == 2 and "cg_iterations" not in d2 and "pipe_cg_iterations" not in d2
+    np.testing.assert_allclose(np.load(tmp_path / "two" / "y.npy"), want, rtol=0, atol=1e-12)
 
 
 def _bench_plain(args, env_extra=None):

@@ -11,7 +11,7 @@ echo "== dropin"
 timeout 900 python -m pytest tests/test_dropin_gpu.py -m gpu -q 2>&1 | tail -3
 (cd oracle/_ref/dropin && LD_LIBRARY_PATH=.:../lib:$GRAFT_REPO_ROOT/ginkgo_amd/lib timeout 600 ./dropin_test 2>&1 | grep -i "convert_to\|lookup\|by-product\|user precond\|FAIL" | head -8) | tee $OUT/dropin_lines.txt
 echo "== driver's command"
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_line_unprofiled.json 2> $OUT/bench.err
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_line_unprofiled.json 2> $OUT/bench.err
 tail -1 $OUT/bench_line_unprofiled.json | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['config']['pct_hbm_peak'], d.get('cg_iters_per_s'), d['roofline']['frac'], d['roofline']['traffic'], d['ginkgo_api']['frac'], d['ginkgo_api']['cg_iters_per_s'], d['cpu_baseline']['value'], d['placement']['memory_classes_found'], d['placement']['search_ms'])"
 echo "== the same under rocprofv3"
 cd /tmp

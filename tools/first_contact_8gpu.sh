@@ -25,14 +25,14 @@ launch() { python -m torch.distributed.run --nnodes=1 --nproc-per-node "$1" --ma
 # 1. each transport alone, two ranks, the smallest problem: does it come up, are the answers right, what does an
 #    iteration's communication cost (comm_check in the line), who saw whom (topology)
 for T in ipc rccl torch; do
-  GKO_COMM=$T run "01_two_ranks_$T" 600 launch 2 bench.py --gpus 2 --grid 64 --steps 5 --warmup 2 --cg-iters 20
+  GKO_COMM=$T run "01_two_ranks_$T" 600 launch 2 bench.py --gpus 2 --grid 64 --steps 5 --warmup 2 --cg-iters 20 --full
 done
 # 2. the default choice (both transports timed, the faster one taken) with the product's soak, at the real size
 for N in 2 4 8; do
   [ "$N" -le "$NDEV" ] && [ "$N" -le "$MAXG" ] || continue
-  run "02_bench_${N}gpus" 1200 launch "$N" bench.py --gpus "$N" --grid "$GRID" --steps 20 --warmup 5
+  run "02_bench_${N}gpus" 1200 launch "$N" bench.py --gpus "$N" --grid "$GRID" --steps 20 --warmup 5 --full
   # the conservative shape next to it: RCCL, join-based product (nothing waits inside a kernel)
-  GKO_COMM=rccl GKO_GATED_SPMV=0 run "03_bench_${N}gpus_rccl_join" 1200 launch "$N" bench.py --gpus "$N" --grid "$GRID" --steps 20 --warmup 5
+  GKO_COMM=rccl GKO_GATED_SPMV=0 run "03_bench_${N}gpus_rccl_join" 1200 launch "$N" bench.py --gpus "$N" --grid "$GRID" --steps 20 --warmup 5 --full
 done
 # 3. the C++ driver on the C ABI alone (examples/native_dist_cg.cpp) where it has been built
 [ -x examples/native_dist_cg ] && for N in 2 8; do

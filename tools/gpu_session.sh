@@ -6,6 +6,7 @@ STEPS=${@:-"info pytest smoke bench lab prof"}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 for S in $STEPS; do
 case $S in
 info)
@@ -26,7 +27,7 @@ lab)
   timeout 600 tools/spmv_lab 256 20 2>&1 | tee $OUT/lab.txt ;;
 prof)
   echo "== rocprofv3 kernel-trace"
-  (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/prof -o bench -- python $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 3 --cg-iters 20 --no-cpu > $GRAFT_REPO_ROOT/$OUT/prof_run.txt 2>&1)
+  (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/prof -o bench -- python $ROOT/bench.py --steps 20 --warmup 3 --full --cg-iters 20 --no-cpu > $ROOT/$OUT/prof_run.txt 2>&1)
   find $OUT/prof -type f | head -20
   find $OUT/prof -name "*kernel_stats*" | head -1 | xargs -r head -25 ;;
 esac

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 line() { tail -1 $1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); p=d['placement']; print(d['value'], d['config']['pct_hbm_peak'], d.get('cg_iters_per_s'), 'classes', p['memory_classes_found'], p['class_of'], 'walked', p['granules_walked'], 'classified', p['granules_classified'], 'search_ms', p['search_ms'], 'retries', p['probe_retries'])"; }
 echo "== 20 fresh processes: python bench.py --gpus 1 --steps 20 --warmup 5 (no CPU / Ginkgo-API / PMC legs)"
 for i in $(seq 1 20); do
-timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-ginkgo-api --no-pmc --cg-iters 30 > $OUT/fresh_$i.json 2> $OUT/fresh_$i.err
+timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu --no-ginkgo-api --no-pmc --cg-iters 30 > $OUT/fresh_$i.json 2> $OUT/fresh_$i.err
 line $OUT/fresh_$i.json
 done | tee $OUT/fresh20.txt
 echo "== survey of a fresh device (tools/class_lab survey 24)"
@@ -19,7 +19,7 @@ HOLDER=$!
 for i in $(seq 1 180); do grep -q READY $OUT/starve.txt && break; sleep 1; done
 tail -5 $OUT/starve.txt
 for i in 1 2 3; do
-GKOC_ARENA_VERBOSE=1 timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-ginkgo-api --no-pmc --cg-iters 30 > $OUT/starved_$i.json 2> $OUT/starved_$i.err
+GKOC_ARENA_VERBOSE=1 timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu --no-ginkgo-api --no-pmc --cg-iters 30 > $OUT/starved_$i.json 2> $OUT/starved_$i.err
 line $OUT/starved_$i.json
 grep "survey" $OUT/starved_$i.err
 done | tee $OUT/starved.txt
