@@ -1,6 +1,6 @@
-"""Matrix formats on the Cdna4Executor: Dense, Csr, Ell, Sellp.
+"""Matrix formats on the Cdna4Executor: Dense, Csr, Ell, Sellp, Fbcsr.
 
-Host-side mirror of include/ginkgo/core/matrix/{dense,csr,ell,sellp}.hpp for
+Host-side mirror of include/ginkgo/core/matrix/{dense,csr,ell,sellp,fbcsr}.hpp for
 the hot path: same method names, argument meaning and error behaviour; every
 numerical method is one call into libgko_cdna4.so (no torch arithmetic).
 """
@@ -449,6 +449,148 @@ class Csr(_SparseBase):
              self.values, sets, cols, vals)
         return Sellp(self.exec, self.size, vals, cols, sets, lens, slice_size,
                      stride_factor)
+
+    def convert_to_fbcsr(self, block_size):
+        """Csr::convert_to(Fbcsr) with the given block size (csr::convert_to_fbcsr): block
+        columns ascending, entries of a present block that this matrix does not hold become
+        explicit zeros.  An unsorted matrix is sorted on a clone; this one is not modified."""
+        bs = _fbcsr_check_block_size(block_size, self.size)
+        ex, it = self.exec, IT[self.col_idxs.dtype]
+        src = self
+        if not self.is_sorted_by_column_index():
+            src = Csr(ex, self.size, self.values.clone(), self.col_idxs.clone(), self.row_ptrs,
+                      self.strategy).sort_by_column_index()
+        ptrs = ex.alloc((self.size[0] // bs + 1,), self.col_idxs.dtype, MEM_INDICES)
+        nb = C.c_int64(0)
+        call("gkoc_csr_convert_to_fbcsr_row_ptrs_" + it, ex.stream, self.size[0], self.size[1],
+             bs, src.row_ptrs, src.col_idxs, ptrs, C.byref(nb))
+        cols = ex.alloc((nb.value,), self.col_idxs.dtype, MEM_INDICES)
+        vals = ex.alloc((nb.value * bs * bs,), self.dtype, MEM_VALUES)
+        call("gkoc_csr_convert_to_fbcsr_" + self._suf(), ex.stream, self.size[0], self.size[1],
+             bs, src.row_ptrs, src.col_idxs, src.values, ptrs, cols, vals)
+        if src is not self:
+            ex.synchronize()        # the sorted clone is released on return
+        return Fbcsr(ex, self.size, bs, vals, cols, ptrs)
+
+
+def _fbcsr_check_block_size(block_size, size):
+    bs = int(block_size)
+    if bs < 1:
+        raise GkoError(f"Fbcsr: block size {bs} must be positive")
+    if bs > Fbcsr.MAX_BLOCK_SIZE:
+        raise _lib.NotSupported(f"Fbcsr: block size {bs}: the kernels cover 1..{Fbcsr.MAX_BLOCK_SIZE}")
+    if size[0] % bs or size[1] % bs:
+        raise DimensionMismatch(f"Fbcsr: size {tuple(size)} is not divisible by the block size {bs}")
+    return bs
+
+
+class Fbcsr(_SparseBase):
+    """fbcsr.hpp: fixed-block CSR.  row_ptrs (num_rows / bs + 1 entries) count blocks,
+    col_idxs holds one block column per block, values the bs x bs blocks in storage order,
+    each COLUMN-major: entry (i, j) of block k at k bs^2 + j bs + i
+    (acc::block_col_major<V, 3>, core/matrix/fbcsr.cpp).  Block sizes 1..8."""
+
+    MAX_BLOCK_SIZE = 8
+
+    def __init__(self, exec_, size, block_size, values, col_idxs, row_ptrs):
+        super().__init__(exec_, size)
+        bs = _fbcsr_check_block_size(block_size, self.size)
+        if row_ptrs.numel() != self.size[0] // bs + 1:
+            raise GkoError("Fbcsr: row_ptrs must have num_rows / block_size + 1 entries")
+        if values.numel() != col_idxs.numel() * bs * bs:
+            raise GkoError("Fbcsr: values must hold block_size^2 entries per block column index")
+        if col_idxs.dtype != row_ptrs.dtype:
+            raise GkoError("Fbcsr: index arrays must share one type")
+        self.block_size = bs
+        self.values, self.col_idxs, self.row_ptrs = values, col_idxs, row_ptrs
+
+    @staticmethod
+    def from_arrays(exec_, size, block_size, row_ptrs, col_idxs, values):
+        """host (or device) arrays in Ginkgo's layout: values flat, blocks column-major"""
+        if not isinstance(values, torch.Tensor):
+            values = np.ascontiguousarray(values)
+        return Fbcsr(exec_, size, block_size, exec_.to_device(values.reshape(-1), MEM_VALUES),
+                     exec_.to_device(col_idxs, MEM_INDICES), exec_.to_device(row_ptrs, MEM_INDICES))
+
+    @staticmethod
+    def from_scipy(exec_, a, index_dtype=np.int32):
+        """a scipy.sparse BSR matrix with square blocks; scipy's row-major blocks are
+        transposed into Ginkgo's column-major ones (block order and columns as they are)"""
+        r, c = a.blocksize
+        if r != c:
+            raise _lib.NotSupported(f"Fbcsr: blocks must be square, got {r} x {c}")
+        vals = np.ascontiguousarray(np.asarray(a.data).transpose(0, 2, 1)).reshape(-1)
+        return Fbcsr.from_arrays(exec_, a.shape, r, a.indptr.astype(index_dtype),
+                                 a.indices.astype(index_dtype), vals)
+
+    @staticmethod
+    def read(data, block_size):
+        """Fbcsr::read(device_matrix_data) = Csr::read, then convert_to_fbcsr"""
+        return Csr.read(data).convert_to_fbcsr(block_size)
+
+    @property
+    def dtype(self):
+        return self.values.dtype
+
+    def _suf(self):
+        return f"{VT[self.values.dtype]}_{IT[self.col_idxs.dtype]}"
+
+    def get_block_size(self):
+        return self.block_size
+
+    def get_num_stored_blocks(self):
+        return int(self.col_idxs.numel())
+
+    def get_num_stored_elements(self):
+        return int(self.values.numel())
+
+    def apply_impl(self, b, x):
+        bv, ldb, xv, ldx, nrhs = self._operands(b, x)
+        bs = self.block_size
+        call("gkoc_fbcsr_spmv_" + self._suf(), self.exec.stream, self.size[0] // bs,
+             self.size[1] // bs, bs, self.row_ptrs, self.col_idxs, self.values, bv, ldb,
+             xv, ldx, nrhs)
+
+    def apply_advanced_impl(self, alpha, b, beta, x):
+        bv, ldb, xv, ldx, nrhs = self._operands(b, x)
+        if alpha.dtype != self.dtype or beta.dtype != self.dtype:
+            raise _lib.NotSupported("Fbcsr: alpha and beta must have the matrix' value type")
+        bs = self.block_size
+        call("gkoc_fbcsr_advanced_spmv_" + self._suf(), self.exec.stream, self.size[0] // bs,
+             self.size[1] // bs, bs, alpha.values, self.row_ptrs, self.col_idxs, self.values,
+             bv, ldb, beta.values, xv, ldx, nrhs)
+
+    def convert_to_csr(self):
+        """fbcsr::convert_to_csr: bs^2 entries per stored block, explicit zeros included"""
+        ex, bs = self.exec, self.block_size
+        nnz = self.get_num_stored_elements()
+        idt = self.col_idxs.dtype
+        if idt == torch.int32 and nnz >= 2 ** 31:
+            raise GkoError("Fbcsr.convert_to_csr: the number of entries overflows int32")
+        ptrs = ex.alloc((self.size[0] + 1,), idt, MEM_INDICES)
+        cols, vals = ex.alloc((nnz,), idt, MEM_INDICES), ex.alloc((nnz,), self.dtype, MEM_VALUES)
+        call("gkoc_fbcsr_convert_to_csr_" + self._suf(), ex.stream, self.size[0] // bs, bs,
+             self.row_ptrs, self.col_idxs, self.values, ptrs, cols, vals)
+        return Csr(ex, self.size, vals, cols, ptrs)
+
+    def convert_to_dense(self):
+        out = Dense.create(self.exec, self.size, self.dtype).fill(0.0)
+        bs = self.block_size
+        call("gkoc_fbcsr_fill_in_dense_" + self._suf(), self.exec.stream, self.size[0] // bs,
+             self.size[1] // bs, bs, self.row_ptrs, self.col_idxs, self.values, out.values, out.ld)
+        return out
+
+    def extract_diagonal(self):
+        d = self.exec.zeros((min(self.size),), self.dtype)
+        call("gkoc_fbcsr_extract_diagonal_" + self._suf(), self.exec.stream, self.size[0],
+             self.size[1], self.block_size, self.row_ptrs, self.col_idxs, self.values, d)
+        return d
+
+    def is_sorted_by_column_index(self):
+        flag = C.c_int(1)
+        call("gkoc_fbcsr_is_sorted_by_column_index_" + self._suf(), self.exec.stream,
+             self.size[0] // self.block_size, self.row_ptrs, self.col_idxs, C.byref(flag))
+        return bool(flag.value)
 
 
 class Coo(_SparseBase):

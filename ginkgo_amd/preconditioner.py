@@ -19,7 +19,7 @@ import torch
 from ._lib import IT, VT, JacobiScheme, NotSupported, call
 from .base import LinOp
 from .executor import MEM_INDICES
-from .matrix import Csr
+from .matrix import Csr, Fbcsr
 
 
 def compute_storage_scheme(max_block_size, warp_size=64):
@@ -96,6 +96,13 @@ class JacobiFactory:
         return self
 
     def generate(self, system_matrix):
+        if isinstance(system_matrix, Fbcsr):
+            # Jacobi::generate takes any other matrix type through convert_to(Csr)
+            # (core/preconditioner/jacobi.cpp)
+            csr = system_matrix.convert_to_csr()
+            prec = Jacobi(self, csr)
+            csr.exec.synchronize()      # the converted copy is released on return
+            return prec
         return Jacobi(self, system_matrix)
 
 

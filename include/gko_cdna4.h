@@ -355,6 +355,71 @@ GKOC_DECL_SELLP(gkoc_c128, c128, int64_t, i64)
 GKOC_DECL_SELLP(gkoc_c64, c64, int32_t, i32)
 GKOC_DECL_SELLP(gkoc_c64, c64, int64_t, i64)
 
+/* ------------------------------------------------------------ Fbcsr (fixed-block CSR)
+ * fbcsr::spmv / advanced_spmv / convert_to_csr / fill_in_dense / extract_diagonal /
+ * is_sorted_by_column_index, csr::convert_to_fbcsr  (core/matrix/fbcsr_kernels.hpp,
+ * csr_kernels.hpp).  Storage of include/ginkgo/core/matrix/fbcsr.hpp: row_ptrs has
+ * n_block_rows + 1 entries and counts blocks, col_idxs one block column per block, values
+ * the blocks in storage order, each block_size x block_size block COLUMN-major: entry (i, j)
+ * of block k at k bs^2 + j bs + i (acc::block_col_major<V, 3>).  block_size 1..8; others:
+ * GKOC_E_NOT_SUPPORTED.  Every argument is checked before any HIP call.
+ * spmv: scalar row brow bs + i sums val(k, i, j) * b[col_idxs[k] bs + j] over the blocks of
+ * its block row in storage order, j ascending inside a block - bit-identical to the CSR
+ * reference on the expanded matrix, for every row length.  Advanced: (beta == 0 ? 0 :
+ * c beta) + (alpha val) b in the same order; beta == 0 never reads c.
+ * csr_convert_to_fbcsr_row_ptrs: the CSR must be sorted by column index and its sizes
+ * divisible by block_size (else GKOC_E_INVALID); fb_row_ptrs gets the block row pointers,
+ * *num_blocks_host (HOST memory, synchronises) the number of blocks.  csr_convert_to_fbcsr
+ * then fills fb_col_idxs / fb_vals: block columns ascending, entries of a present block that
+ * the CSR does not hold are explicit zeros.  fbcsr_convert_to_csr writes bs^2 entries per
+ * block (n_block_rows bs + 1 row pointers), each row in block order, then by column inside
+ * the block.  fill_in_dense: `out` zeroed by the caller, ld >= n_block_cols bs.
+ * *is_sorted_host is HOST memory.  Checked before any HIP call: block size, sizes, strides
+ * and every pointer whose length the host knows (row pointers, b, c, alpha, beta, out, diag,
+ * results).  NOT checked: col_idxs / vals / fb_col_idxs / fb_vals / csr_col_idxs /
+ * csr_vals - their length is the block count, which sits on the device. */
+#define GKOC_DECL_FBCSR(T, TN, I, IN)                                          \
+    int gkoc_fbcsr_spmv_##TN##_##IN(                                           \
+        gkoc_stream_t s, int64_t n_block_rows, int64_t n_block_cols,           \
+        int64_t block_size, const I* row_ptrs, const I* col_idxs,              \
+        const T* vals, const T* b, int64_t ldb, T* c, int64_t ldc,             \
+        int64_t nrhs);                                                         \
+    int gkoc_fbcsr_advanced_spmv_##TN##_##IN(                                  \
+        gkoc_stream_t s, int64_t n_block_rows, int64_t n_block_cols,           \
+        int64_t block_size, const T* alpha, const I* row_ptrs,                 \
+        const I* col_idxs, const T* vals, const T* b, int64_t ldb,             \
+        const T* beta, T* c, int64_t ldc, int64_t nrhs);                       \
+    int gkoc_csr_convert_to_fbcsr_##TN##_##IN(                                 \
+        gkoc_stream_t s, int64_t n_rows, int64_t n_cols, int64_t block_size,   \
+        const I* row_ptrs, const I* col_idxs, const T* vals,                   \
+        const I* fb_row_ptrs, I* fb_col_idxs, T* fb_vals);                     \
+    int gkoc_fbcsr_convert_to_csr_##TN##_##IN(                                 \
+        gkoc_stream_t s, int64_t n_block_rows, int64_t block_size,             \
+        const I* row_ptrs, const I* col_idxs, const T* vals,                   \
+        I* csr_row_ptrs, I* csr_col_idxs, T* csr_vals);                        \
+    int gkoc_fbcsr_fill_in_dense_##TN##_##IN(                                  \
+        gkoc_stream_t s, int64_t n_block_rows, int64_t n_block_cols,           \
+        int64_t block_size, const I* row_ptrs, const I* col_idxs,              \
+        const T* vals, T* out, int64_t ld);                                    \
+    int gkoc_fbcsr_extract_diagonal_##TN##_##IN(                               \
+        gkoc_stream_t s, int64_t n_rows, int64_t n_cols, int64_t block_size,   \
+        const I* row_ptrs, const I* col_idxs, const T* vals, T* diag);         \
+    int gkoc_fbcsr_is_sorted_by_column_index_##TN##_##IN(                      \
+        gkoc_stream_t s, int64_t n_block_rows, const I* row_ptrs,              \
+        const I* col_idxs, int* is_sorted_host);
+GKOC_DECL_FBCSR(double, f64, int32_t, i32)
+GKOC_DECL_FBCSR(double, f64, int64_t, i64)
+GKOC_DECL_FBCSR(float, f32, int32_t, i32)
+GKOC_DECL_FBCSR(float, f32, int64_t, i64)
+int gkoc_csr_convert_to_fbcsr_row_ptrs_i32(gkoc_stream_t s, int64_t n_rows, int64_t n_cols,
+                                           int64_t block_size, const int32_t* row_ptrs,
+                                           const int32_t* col_idxs, int32_t* fb_row_ptrs,
+                                           int64_t* num_blocks_host);
+int gkoc_csr_convert_to_fbcsr_row_ptrs_i64(gkoc_stream_t s, int64_t n_rows, int64_t n_cols,
+                                           int64_t block_size, const int64_t* row_ptrs,
+                                           const int64_t* col_idxs, int64_t* fb_row_ptrs,
+                                           int64_t* num_blocks_host);
+
 /* ---------------------------------------------------- format conversions
  * csr::convert_to_ell / convert_to_sellp, ell::compute_max_row_nnz,
  * sellp::compute_slice_sets, components::convert_ptrs_to_sizes,
