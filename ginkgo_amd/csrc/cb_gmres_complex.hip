@@ -433,6 +433,7 @@ int solve_impl(gkoc_stream_t s, int64_t rows, int64_t cols, const T* rnc, int64_
     cx_solve_upper<T><<<dim3(unsigned(ceildiv(cols, int64_t(64)))), dim3(64), 0, st>>>(cols, rnc, ld_rnc, hess, ldh, y, ldy,
                                                                                       fin);
     GKOC_LAUNCH_OK();
+    if (rows == 0) return GKOC_OK;   // y is all there is; a grid of zero blocks would be an error
     cx_qy<T, S><<<dim3(unsigned(ceildiv(rows * cols, int64_t(CXB)))), dim3(CXB), 0, st>>>(rows, cols, bases, st0, st1, y,
                                                                                           ldy, out, ldo, fin);
     GKOC_LAUNCH_OK();

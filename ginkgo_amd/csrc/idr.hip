@@ -258,9 +258,11 @@ int idr_initialize(gkoc_stream_t s_, int64_t nrhs, int64_t s, T* m, int64_t ldm,
     if (s == 0) return GKOC_OK;
     GKOC_REQUIRE(m && p && stop, GKOC_E_INVALID, "null pointer");
     const int64_t cnt = std::max<int64_t>(s * s * nrhs, nrhs);
-    idr_init_m_kernel<T><<<dim3(unsigned(ceildiv(cnt, idr_block))), dim3(idr_block), 0, st>>>(s, nrhs, m, ldm,
-                                                                                           stop);
-    GKOC_LAUNCH_OK();
+    if (cnt > 0) {   // no right-hand side: m (s x 0) and stop are empty, a grid of zero blocks is an error
+        idr_init_m_kernel<T><<<dim3(unsigned(ceildiv(cnt, idr_block))), dim3(idr_block), 0, st>>>(s, nrhs, m,
+                                                                                               ldm, stop);
+        GKOC_LAUNCH_OK();
+    }
     if (n == 0) return GKOC_OK;
     if (!deterministic) {
         // the reference draws the shadow vectors from a normal distribution with a random seed

@@ -530,7 +530,8 @@ GKOC_DECL_ASSEMBLY(float, f32, int64_t, i64)
     int gkoc_prefix_sum_nonnegative_##IN(gkoc_stream_t s, I* counts,           \
                                          int64_t n);                           \
     /* the same with the reference's overflow check (GKOC_E_OVERFLOW when a */ \
-    /* partial sum exceeds the type; synchronises the stream)              */ \
+    /* partial sum of entries 0 .. n-2 exceeds the type - the last entry is */ \
+    /* never added, so its value cannot overflow; synchronises the stream)  */ \
     int gkoc_prefix_sum_nonnegative_checked_##IN(gkoc_stream_t s, I* counts,   \
                                                  int64_t n);                   \
     int gkoc_fill_array_##IN(gkoc_stream_t s, I* data, int64_t n, I value);    \
@@ -606,7 +607,9 @@ int gkoc_dense_convert_f32_f64(gkoc_stream_t s, int64_t rows, int64_t cols,
  *   (Ginkgo's array<char>& tmp), at least gkoc_reduction_workspace_bytes().
  *   Reductions are deterministic (fixed tree for a given n, nrhs) but their
  *   summation order differs from the sequential reference: |err| <=
- *   1e-13 * sum|x_i y_i| in fp64 (tests/test_dense_gpu.py).
+ *   450 eps * sum|x_i y_i|, i.e. 1e-13 in fp64 (tests/test_dense_gpu.py:
+ *   test_dot_norm2_contract, and the same bound for compute_norm1 /
+ *   compute_mean in test_norm1_mean_random).
  * dense::row_gather  common/unified/matrix/dense_kernels.template.cpp:449-473 */
 size_t gkoc_reduction_workspace_bytes(int64_t n_rows, int64_t nrhs,
                                       size_t value_size);
