@@ -25,6 +25,7 @@
 #include <map>
 #include <mutex>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "common.hpp"
@@ -53,8 +54,7 @@ struct long_entry {
 std::map<std::tuple<int, const void*, int64_t>, long_entry> g_long_cache;
 std::atomic<int> g_long_cached{0};
 constexpr size_t long_cache_cap = 128;
-constexpr int64_t long_list_cap = 4096;
-constexpr int short_rows_default_layout = 0;      // (set by measurement: see launch_csr)      // more flagged segments than this: the matrix has no "few long rows"
+constexpr int64_t long_list_cap = 4096;      // more flagged segments than this: the matrix has no "few long rows"
 
 thread_local bool t_long_releasing = false;      // gkoc_free below comes back through csr_long_rows_forget
 
@@ -205,7 +205,263 @@ void csr_long_rows_forget(const void* ptr)
 
 namespace {
 
-template <typename T, typename I, bool ADV, int rows_per_seg = 64>
+// ---- the launch plan of the row-segment kernels (csr_spmv_pipe3_kernel, csr_spmv_multi_kernel) -------------
+template <int N>
+using int_c = std::integral_constant<int, N>;
+
+// 64-row segments (lane = row in the row phase).  Large matrices: 2 segments
+// = 128 rows per wavefront, whose 1 KB of results is written in one burst at
+// the end of the wave (mode 0x2000).  Below 65536 segments (4 M rows) the
+// grid is only a few rounds of the 5120 resident waves deep and the tail
+// dominates: one segment per wave then (+1 % at 2 M rows, +7 % at 0.9 M,
+// +15 % at 0.26 M rows).  In-order dispatch keeps the set of resident waves
+// on a compact window of rows, which is what lets the b-vector lines shared
+// by neighbouring rows hit in L2.
+// (round 3, measured again on 1 / 2 / 4 / 16.7 M rows, profiles/r03_experiments.txt: forcing one or
+// two segments per wave or 32-row segments changes nothing or loses: 2.1 M rows 139.8 us with
+// this rule, 142-147 us with the alternatives)
+struct segment_plan {
+    int64_t n_seg;      // 64-row segments of the matrix
+    int spw;            // segments per wave
+    int64_t n_waves;    // = workgroups
+};
+
+// forced_spw = 1 or 2: that many segments per wave whatever the size (any other value: the rule)
+int plan_segments(int64_t n_rows, segment_plan* plan, int64_t forced_spw = 0)
+{
+    const int64_t n_seg = ceildiv(n_rows, 64);
+    const int spw = (forced_spw == 1 || forced_spw == 2) ? int(forced_spw) : (n_seg < 65536 ? 1 : 2);
+    const int64_t n_waves = ceildiv(n_seg, spw);
+    GKOC_REQUIRE(n_waves < (int64_t(1) << 31), GKOC_E_NOT_SUPPORTED, "more than 2^31 row segments");
+    *plan = segment_plan{n_seg, spw, n_waves};
+    return GKOC_OK;
+}
+
+// the kernel's mode bits for spw segments per wave (spw << 12: csr_spmv_pipe.hpp DEFER) as a compile-time
+// constant: launch(int_c<0x1000>) or launch(int_c<0x2000>)
+template <typename F>
+void with_store_mode(int spw, F&& launch)
+{
+    if (spw == 2) {
+        launch(int_c<0x2000>{});
+    } else {
+        launch(int_c<0x1000>{});
+    }
+}
+
+// E-element vector loads need the array bases aligned like the vector types (vecT<V, E> / vecT<I, E>: true
+// for whole allocations; sub-views that are not take the scalar-load instantiation E = 1)
+template <typename V, typename I>
+bool streams_aligned(const V* vals, const I* cols, int E)
+{
+    return reinterpret_cast<uintptr_t>(vals) % (E * sizeof(V)) == 0 &&
+           reinterpret_cast<uintptr_t>(cols) % (E * sizeof(I)) == 0;
+}
+
+// Load layouts of the row-segment kernel, <E, U> = entries per lane and load x load groups in flight.
+template <typename T>
+struct pipe_layout {
+    // 32 B of values per lane and load: 4 doubles or 8 floats (ring = 8 KB); the layout of rounds 1-2 is <EV, 1>
+    static constexpr int EV = 32 / sizeof(T);
+    static constexpr int RINGV = 8192 / sizeof(T);
+    // Entries per lane and load x load groups in flight (ring 8 KB): 2 x 3 for double, 4 x 2 for
+    // float - 16 B of values per lane and load, 48 / 32 B in flight.  Measured in one process on L256
+    // (tools/f32_variants.py, profiles/r03_experiments.txt): double 4 x 1 (rounds 1-2) 985 us, 2 x 3
+    // 954, 2 x 4 960, 1 x 6 968, 4 x 2 980, 1 x 8 978, 1 x 4 986; float 8 x 1 (rounds 1-2) 847 us,
+    // 4 x 2 793, 4 x 3 823, 8 x 2 / 4 x 4 / 2 x 8 slower.  By size (tools/csr_layout_ab.py, double): 4.1 M rows
+    // 251 -> 246 us, 8.4 M 510 -> 495, 16.8 M 985 -> 953; the Flan-like matrix (81 per row) 272 both;
+    // 5-pt 4096^2 397 -> 405.
+    static constexpr int PE = sizeof(T) == 8 ? 2 : 4, PU = sizeof(T) == 8 ? 3 : 2;
+};
+
+// Three and more right-hand sides, fragment layout (csr_spmv_multi.hpp): the lanes of a gather cover whole
+// rows of b.  Small waves - 16 rows, 6 KB of LDS - so that 20+ of them are resident per CU.  L256
+// (profiles/r03_multi_rhs_256.txt): 3 / 4 / 8 columns 2.17 / 2.23 / 5.08 ms with the ring and row-ordered
+// kernels of round 2 -> 1.77 / 1.77 / 1.97 ms.  Measured variants: 32 / 64 rows per wave (12 / 24 KB: 2.2 -
+// 4.6 ms), 2 - 8 entries per step (+- 3 %; 3 for eight columns, 4 for four); two columns stay with the ring
+// kernel (launch_csr_pair: 1.46 ms, this layout 2.36 ms with 32-row waves).
+// Since round 5 the pipelined form, four segments per wave: L256 3 / 4 / 8 columns 1.87 / 1.90 / 2.10 ->
+// 1.76 / 1.79 / 2.00 ms (profiles/r05_multi_rhs_pmc.txt).  The variants GKOC_TUNE_CSR_MULTI_VARIANT used to
+// select - the kernel of rounds 3-4 with pairs of columns or two row groups per wave, other entries-per-step
+// and segments-per-wave choices, strided rounds, values handed over by the row below - were all measured slower
+// (that file and profiles/r06/r06_multi_rhs_baseline.txt) and are not launched any more.
+template <typename T, typename I, bool ADV>
+int launch_csr_columns(gkoc_stream_t s, int64_t n_rows, int64_t n_cols, const T* alpha, const I* row_ptrs,
+                       const I* col_idxs, const T* vals, const T* b, int64_t ldb, const T* beta, T* c,
+                       int64_t ldc, int64_t nrhs)
+{
+    const bool idx32 = n_cols * ldb < (int64_t(1) << 32);
+    const bool pairs_ok = reinterpret_cast<uintptr_t>(b) % (2 * sizeof(T)) == 0 && ldb % 2 == 0 &&
+                          reinterpret_cast<uintptr_t>(c) % (2 * sizeof(T)) == 0 && ldc % 2 == 0;
+    const int64_t chunk_rows = tune_value(GKOC_TUNE_MULTI_XCD_CHUNK_ROWS);
+    // chunks of NR columns, CPL columns per lane (64 * CPL / NR rows per segment), KU entries per step;
+    // pipelined: csr_spmv_frag_pipe_kernel with four segments per wave, else csr_spmv_frag_kernel
+    auto launch = [&](auto nr, auto cpl, auto ku, auto pipelined) -> int {
+        constexpr int NR = decltype(nr)::value, CPL = decltype(cpl)::value, KU = decltype(ku)::value;
+        constexpr bool PIPE = decltype(pipelined)::value;
+        constexpr int rows = 64 * CPL / NR, segs = PIPE ? 4 : 1;
+        const int64_t nwg = ceildiv(ceildiv(n_rows, rows), segs);
+        GKOC_REQUIRE(nwg < (int64_t(1) << 31), GKOC_E_NOT_SUPPORTED, "more than 2^31 waves");
+        const dim3 grid(static_cast<unsigned>(nwg)), block(64);
+        auto go = [&](auto idx) {
+            constexpr bool IDX32 = decltype(idx)::value;
+            if constexpr (PIPE) {
+                csr_spmv_frag_pipe_kernel<T, I, ADV, NR, CPL, KU, IDX32><<<grid, block, 0, as_stream(s)>>>(
+                    n_rows, row_ptrs, col_idxs, vals, b, ldb, c, ldc, static_cast<int>(nrhs), alpha, beta, segs,
+                    chunk_rows / (rows * segs));
+            } else {
+                csr_spmv_frag_kernel<T, I, ADV, NR, CPL, KU, IDX32><<<grid, block, 0, as_stream(s)>>>(
+                    n_rows, row_ptrs, col_idxs, vals, b, ldb, c, ldc, static_cast<int>(nrhs), alpha, beta,
+                    chunk_rows / rows);
+            }
+        };
+        if (idx32) {
+            go(std::true_type{});
+        } else {
+            go(std::false_type{});
+        }
+        GKOC_LAUNCH_OK();
+        return GKOC_OK;
+    };
+    // four lanes per row: one column each up to four columns, a pair of columns each beyond
+    if (nrhs <= 4) return launch(int_c<4>{}, int_c<1>{}, int_c<4>{}, std::true_type{});
+    if (pairs_ok) return launch(int_c<8>{}, int_c<2>{}, int_c<3>{}, std::true_type{});
+    // odd strides or unaligned b / c: eight lanes per row, one column each, the kernel of rounds 3-4
+    return launch(int_c<8>{}, int_c<1>{}, int_c<4>{}, std::false_type{});
+}
+
+// Two right-hand sides, vector loads possible: the row-segment walk of the single-column kernel with the two
+// products of an entry side by side in the LDS ring (csr_spmv_multi_kernel; 8 KB ring of 512
+// entries).  L256: 1.46 ms against 2.18 ms for one pass per column.
+template <typename T, typename I, bool ADV>
+int launch_csr_pair(gkoc_stream_t s, int64_t n_rows, const T* alpha, const I* row_ptrs, const I* col_idxs,
+                    const T* vals, const T* b, int64_t ldb, const T* beta, T* c, int64_t ldc)
+{
+    using lay = pipe_layout<T>;
+    segment_plan p;
+    GKOC_TRY(plan_segments(n_rows, &p));
+    const dim3 grid(static_cast<unsigned>(p.n_waves)), block(64);
+    const int b_vec_ok = reinterpret_cast<uintptr_t>(b) % (2 * sizeof(T)) == 0 && ldb % 2 == 0;
+    const int64_t xcd_chunk = tune_value(GKOC_TUNE_MULTI_XCD_CHUNK_ROWS) / (64 * p.spw);
+    auto launch = [&](auto e, auto u) {
+        csr_spmv_multi_kernel<T, I, ADV, decltype(e)::value, decltype(u)::value, lay::RINGV / 2, 2>
+            <<<grid, block, 0, as_stream(s)>>>(n_rows, p.n_seg, p.spw, row_ptrs, col_idxs, vals, b, ldb, c, ldc, 2,
+                                               alpha, beta, b_vec_ok, xcd_chunk);
+    };
+    // two entries per lane and load, two load groups in flight (more, smaller loads under way: the
+    // single-column kernel's lesson of round 3): L256 1.457 -> 1.38-1.40 ms = 55 % of 8 TB/s
+    // (profiles/r04_experiments.txt); GKOC_TUNE_CSR_LOAD_GROUPS = 1: four entries, one group
+    if (tune_value(GKOC_TUNE_CSR_LOAD_GROUPS) == 1) {
+        launch(int_c<lay::EV>{}, int_c<1>{});
+    } else {
+        launch(int_c<lay::EV / 2>{}, int_c<2>{});
+    }
+    GKOC_LAUNCH_OK();
+    return GKOC_OK;
+}
+
+// The hub rows' kernels run BEHIND the row-segment kernel on the caller's stream.  (Round 6 also ran them
+// BESIDE it - a side stream per calling stream, forked in front of the product and joined behind it by two
+// events; the two kernels write disjoint rows of c.  The heavy-tailed stand-in took 245.7 us that way
+// against 231.5 us in sequence, profiles/r06/r06_hub_rows_beside.txt: gone again.)
+template <typename T, typename I, bool ADV>
+int launch_hub_rows(hipStream_t st, const csr_long_info& lng, int64_t n_rows, const T* alpha, const I* row_ptrs,
+                    const I* col_idxs, const T* vals, const T* b, int64_t ldb, const T* beta, T* c, int64_t ldc)
+{
+    // (the chunk sums go to the CALLING stream's buffer: long_partial_for)
+    csr_flagged_segments_kernel<T, I, ADV><<<dim3(unsigned(lng.count * LONG_PARTS)), dim3(LONG_WG), 0, st>>>(
+        n_rows, row_ptrs, col_idxs, vals, b, ldb, c, ldc, alpha, beta, lng.list, static_cast<T*>(lng.partial));
+    GKOC_LAUNCH_OK();
+    csr_long_rows_fold_kernel<T, I, ADV><<<dim3(unsigned(lng.count)), dim3(64), 0, st>>>(
+        n_rows, row_ptrs, c, ldc, beta, lng.list, static_cast<const T*>(lng.partial));
+    GKOC_LAUNCH_OK();
+    return GKOC_OK;
+}
+
+// One right-hand side - and whatever the launchers above do not take: the kernel walks nrhs columns one
+// after the other.
+template <typename T, typename I, bool ADV>
+int launch_csr_single(gkoc_stream_t s, int64_t n_rows, const T* alpha, const I* row_ptrs, const I* col_idxs,
+                      const T* vals, const T* b, int64_t ldb, const T* beta, T* c, int64_t ldc, int64_t nrhs)
+{
+    using lay = pipe_layout<T>;
+    // rows far longer than the rest: their segments are left out here and done by many workgroups
+    // (csr_long_rows.hpp); one right-hand side
+    csr_long_info lng;
+    if (nrhs == 1 && tune_value(GKOC_TUNE_CSR_LONG_ROWS) != 0) {
+        GKOC_TRY((long_info_of<T, I>(s, n_rows, row_ptrs, &lng)));
+    }
+    const uint32_t* seg_skip = lng.count > 0 ? lng.bits : nullptr;
+    // GKOC_TUNE_CSR_SEGS_PER_WAVE forces 1 or 2 segments per wave (round 6 tried "up to eight for matrices
+    // with short rows" - the heavy-tailed stand-in 256 us with one, 261 with two, 276 with four, 320 with eight
+    // segments; 5-pt 4096^2 325 / 289 / 325 / 315; profiles/r06/r06_segments_per_wave.txt: the size rule
+    // stays, and the four / eight-segment variants - whose loop over runs of unflagged segments cost every
+    // variant of the kernel 12-16 VGPRs - are gone again)
+    segment_plan p;
+    GKOC_TRY(plan_segments(n_rows, &p, tune_value(GKOC_TUNE_CSR_SEGS_PER_WAVE)));
+    const dim3 grid(static_cast<unsigned>(p.n_waves)), block(64);
+    // XCD-contiguous wave order needs enough waves per XCD to keep the in-order
+    // window argument valid; below that the plain order is used
+    // ... and is the default for a matrix WITH HUB ROWS (flagged segments): its gathers go all over b, and with
+    // one contiguous eighth of the rows per XCD an L2 holds the lines of its own eighth instead of a share of
+    // everybody's.  Heavy-tailed stand-in 246.6 -> 226.0 us; the stencils lose 0.5-3 % with it (27-pt 256^3
+    // 982 -> 1003, 5-pt 4096^2 274 -> 282) and keep the plain order (profiles/r06/r06_waves_per_workgroup.txt).
+    // GKOC_TUNE_CSR_XCD_MAP: 1 = always, 2 = never.
+    const int64_t xcd_choice = tune_value(GKOC_TUNE_CSR_XCD_MAP);
+    const int xcd_map =
+        ((xcd_choice == 1 || (xcd_choice == 0 && lng.count > 0)) && p.n_waves >= 8 * 1024) ? 1 : 0;
+    // Measured and rejected on the Flan-like matrix and on L256 (profiles/r02_experiments,
+    // profiles/r02_flan_pmc): 16 / 32 KB rings with 2-4 load groups (fewer resident waves: 299-475 us
+    // against 288), 32-row segments (294), one or two entries per lane and load so that neighbouring
+    // lanes gather neighbouring columns (301-305).  What helped was the row-phase loop
+    // (csr_spmv_pipe.hpp): 295 -> 277 us.
+    // (round 6 also tried two / four / eight WAVES per workgroup, every wave with its own segments and ring - a
+    // grid of one-wave workgroups of short-row segments is paced by the dispatcher: 3.5 ns per wave chip-wide,
+    // profiles/r06_irregular_pmc.txt.  The pace is per wave, not per workgroup: heavy-tailed stand-in 247 / 241 /
+    // 246 / 299 us, every stencil 10-40 % slower; profiles/r06/r06_waves_per_workgroup.txt.)
+    const bool vec_ok = streams_aligned(vals, col_idxs, lay::EV);
+    const int64_t groups = tune_value(GKOC_TUNE_CSR_LOAD_GROUPS);
+    const bool long_float_rows = sizeof(T) == 4 && lng.nnz > 0 && lng.nnz >= 40 * n_rows;
+    with_store_mode(p.spw, [&](auto mode) {
+        auto launch = [&](auto e, auto u) {
+            csr_spmv_pipe3_kernel<T, I, ADV, 64, decltype(e)::value, decltype(u)::value, lay::RINGV, 1,
+                                  decltype(mode)::value><<<grid, block, 0, as_stream(s)>>>(
+                n_rows, p.n_seg, p.spw, row_ptrs, col_idxs, vals, b, ldb, c, ldc, static_cast<int>(nrhs), alpha,
+                beta, nullptr, xcd_map, static_cast<const I*>(nullptr), static_cast<int*>(nullptr), int64_t(0),
+                int64_t(0), static_cast<const uint32_t*>(nullptr), uint32_t(0), static_cast<const I*>(nullptr),
+                static_cast<const I*>(nullptr), static_cast<const T*>(nullptr), static_cast<uint32_t*>(nullptr),
+                uint32_t(0), 0, int64_t(-1), seg_skip);
+        };
+        if (!vec_ok) {
+            launch(int_c<1>{}, int_c<4>{});
+        } else if (groups == 3 || (groups == 0 && long_float_rows)) {
+            // float values and LONG rows (40 and more entries on average; the count comes with the first product's
+            // look at the row pointers): ONE entry per lane and load, eight load groups - neighbouring lanes then
+            // gather neighbouring entries of a row, whose columns come in runs (a 27-pt stencil with 2 / 3 / 5
+            // unknowns per node, 53 / 79 / 130 per row: 172 -> 165, 200 -> 182, 231 -> 207 us against four entries
+            // per lane; 7 and 27 per row lose 5-6 % with it, and for double all layouts are within 1.5 %:
+            // profiles/r06/r06_load_layouts.txt).  GKOC_TUNE_CSR_LOAD_GROUPS: 3 forces it, 4 = two entries x four
+            // groups, 1 = the wide loads.
+            launch(int_c<1>{}, int_c<8>{});
+        } else if (groups == 4) {
+            launch(int_c<2>{}, int_c<4>{});
+        } else if (groups == 1 || p.n_seg < 32768) {
+            // below 2 M rows the grid is a few rounds deep and the wider layout of rounds 1-2 is as fast or
+            // faster (64^3: 18.4 against 20.7 us; 1 - 2 M rows: equal); key 2 = 1 forces it for A/B runs
+            launch(int_c<lay::EV>{}, int_c<1>{});
+        } else {
+            launch(int_c<lay::PE>{}, int_c<lay::PU>{});
+        }
+    });
+    GKOC_LAUNCH_OK();
+    if (lng.count > 0) {
+        GKOC_TRY((launch_hub_rows<T, I, ADV>(as_stream(s), lng, n_rows, alpha, row_ptrs, col_idxs, vals, b, ldb,
+                                             beta, c, ldc)));
+    }
+    return GKOC_OK;
+}
+
+template <typename T, typename I, bool ADV>
 int launch_csr(gkoc_stream_t s, int64_t n_rows, int64_t n_cols, const T* alpha,
                const I* row_ptrs, const I* col_idxs, const T* vals, const T* b,
                int64_t ldb, const T* beta, T* c, int64_t ldc, int64_t nrhs)
@@ -217,274 +473,15 @@ int launch_csr(gkoc_stream_t s, int64_t n_rows, int64_t n_cols, const T* alpha,
     GKOC_REQUIRE(ldc >= nrhs && (n_cols == 0 || ldb >= nrhs), GKOC_E_INVALID,
                  "stride smaller than nrhs");
     if (ADV) GKOC_REQUIRE(alpha && beta, GKOC_E_INVALID, "null alpha/beta");
-    // 64-row segments (lane = row in the row phase).  Large matrices: 2 segments
-    // = 128 rows per wavefront, whose 1 KB of results is written in one burst at
-    // the end of the wave (mode 0x2000).  Below 65536 segments (4 M rows) the
-    // grid is only a few rounds of the 5120 resident waves deep and the tail
-    // dominates: one segment per wave then (+1 % at 2 M rows, +7 % at 0.9 M,
-    // +15 % at 0.26 M rows).  In-order dispatch keeps the set of resident waves
-    // on a compact window of rows, which is what lets the b-vector lines shared
-    // by neighbouring rows hit in L2.
-    const int64_t n_seg = ceildiv(n_rows, rows_per_seg);
-    // (round 3, measured again on 1 / 2 / 4 / 16.7 M rows, profiles/r03_experiments.txt: forcing one or
-    // two segments per wave or 32-row segments changes nothing or loses: 2.1 M rows 139.8 us with
-    // this rule, 142-147 us with the alternatives)
-    const int segs_per_wave = n_seg < 65536 ? 1 : 2;
-    const int64_t n_waves = ceildiv(n_seg, segs_per_wave);
-    GKOC_REQUIRE(n_waves < (int64_t(1) << 31), GKOC_E_NOT_SUPPORTED,
-                 "more than 2^31 row segments");
-    dim3 grid(static_cast<unsigned>(n_waves)), block(64);     // (the single-column path re-sizes it below)
-    // 32 B of values per lane and load: 4 doubles or 8 floats (ring = 8 KB)
-    constexpr int EV = 32 / sizeof(T);
-    constexpr int RINGV = 8192 / sizeof(T);
-    // EV-element vector loads need the array bases aligned like the vector types
-    // (vecT<T,EV> / vecT<I,EV>: true for whole allocations; sub-views that are not
-    // take the scalar-load instantiation E = 1)
-    const bool vec_ok =
-        reinterpret_cast<uintptr_t>(vals) % (EV * sizeof(T)) == 0 &&
-        reinterpret_cast<uintptr_t>(col_idxs) % (EV * sizeof(I)) == 0;
     if (nrhs >= 3) {
-        // several right-hand sides, fragment layout (csr_spmv_frag_kernel in csr_spmv_multi.hpp): the
-        // lanes of a gather cover whole rows of b.  Small waves - 16 rows, 6 KB of LDS - so that 20+
-        // of them are resident per CU.  L256 (profiles/r03_multi_rhs_256.txt): 3 / 4 / 8 columns
-        // 2.17 / 2.23 / 5.08 ms with the ring and row-ordered kernels of round 2 -> 1.77 / 1.77 /
-        // 1.97 ms.  Measured variants: 32 / 64 rows per wave (12 / 24 KB: 2.2 - 4.6 ms), 2 - 8 entries
-        // per step (+- 3 %; 3 for eight columns, 4 for four); two columns stay with the ring kernel
-        // below (1.46 ms, this layout 2.36 ms with 32-row waves).
-        const bool idx32 = n_cols * ldb < (int64_t(1) << 32);
-        const bool pairs_ok = reinterpret_cast<uintptr_t>(b) % (2 * sizeof(T)) == 0 && ldb % 2 == 0 &&
-                              reinterpret_cast<uintptr_t>(c) % (2 * sizeof(T)) == 0 && ldc % 2 == 0;
-        const int64_t chunk_rows = tune_value(GKOC_TUNE_MULTI_XCD_CHUNK_ROWS);
-#define GKOC_LAUNCH_CSR_FRAG(NR_, CPL_, KU_) GKOC_LAUNCH_CSR_FRAG_T(NR_, CPL_, 1, KU_)
-#define GKOC_LAUNCH_CSR_FRAG_T(NR_, CPL_, TT_, KU_)                                              \
-    do {                                                                                         \
-        constexpr int rows_ = 64 * CPL_ / NR_ * TT_;                                             \
-        const int64_t nwg = ceildiv(n_rows, rows_);                                              \
-        GKOC_REQUIRE(nwg < (int64_t(1) << 31), GKOC_E_NOT_SUPPORTED, "more than 2^31 waves");    \
-        const dim3 gf(static_cast<unsigned>(nwg));                                               \
-        if (idx32) {                                                                             \
-            csr_spmv_frag_kernel<T, I, ADV, NR_, CPL_, TT_, KU_, true>                           \
-                <<<gf, block, 0, as_stream(s)>>>(n_rows, row_ptrs, col_idxs, vals, b, ldb, c,    \
-                                                 ldc, static_cast<int>(nrhs), alpha, beta,       \
-                                                 chunk_rows / rows_);                            \
-        } else {                                                                                 \
-            csr_spmv_frag_kernel<T, I, ADV, NR_, CPL_, TT_, KU_, false>                          \
-                <<<gf, block, 0, as_stream(s)>>>(n_rows, row_ptrs, col_idxs, vals, b, ldb, c,    \
-                                                 ldc, static_cast<int>(nrhs), alpha, beta,       \
-                                                 chunk_rows / rows_);                            \
-        }                                                                                        \
-    } while (0)
-        const int64_t variant = tune_value(GKOC_TUNE_CSR_MULTI_VARIANT);
-#define GKOC_LAUNCH_CSR_FRAG_PIPE(NR_, CPL_, KU_, SEGS_) GKOC_LAUNCH_CSR_FRAG_PIPE_ST(NR_, CPL_, KU_, SEGS_, 1)
-#define GKOC_LAUNCH_CSR_FRAG_PIPE_ST(NR_, CPL_, KU_, SEGS_, ST_) GKOC_LAUNCH_CSR_FRAG_PIPE_NB(NR_, CPL_, KU_, SEGS_, ST_, false)
-#define GKOC_LAUNCH_CSR_FRAG_PIPE_NB(NR_, CPL_, KU_, SEGS_, ST_, NB_)                            \
-    do {                                                                                         \
-        constexpr int rows_ = 64 * CPL_ / NR_;                                                   \
-        const int64_t nwg = ceildiv(ceildiv(n_rows, rows_), SEGS_);                              \
-        GKOC_REQUIRE(nwg < (int64_t(1) << 31), GKOC_E_NOT_SUPPORTED, "more than 2^31 waves");    \
-        const dim3 gf(static_cast<unsigned>(nwg));                                               \
-        if (idx32) {                                                                             \
-            csr_spmv_frag_pipe_kernel<T, I, ADV, NR_, CPL_, KU_, true, ST_, NB_>                 \
-                <<<gf, block, 0, as_stream(s)>>>(n_rows, row_ptrs, col_idxs, vals, b, ldb, c,    \
-                                                 ldc, static_cast<int>(nrhs), alpha, beta,       \
-                                                 SEGS_, chunk_rows / (rows_ * SEGS_));           \
-        } else {                                                                                 \
-            csr_spmv_frag_pipe_kernel<T, I, ADV, NR_, CPL_, KU_, false, ST_, NB_>                \
-                <<<gf, block, 0, as_stream(s)>>>(n_rows, row_ptrs, col_idxs, vals, b, ldb, c,    \
-                                                 ldc, static_cast<int>(nrhs), alpha, beta,       \
-                                                 SEGS_, chunk_rows / (rows_ * SEGS_));           \
-        }                                                                                        \
-    } while (0)
-        // default (round 5): the pipelined form, four segments per wave - L256 3 / 4 / 8 columns 1.87 / 1.90 /
-        // 2.10 -> 1.76 / 1.79 / 2.00 ms (profiles/r05_multi_rhs_pmc.txt); GKOC_TUNE_CSR_MULTI_VARIANT: 9 = the
-        // kernel of rounds 3-4, 1 .. 3 its layout variants, >= 10 the pipeline's own (segments per wave x 10
-        // + 1000 x entries-per-step choice)
-        const int segs = variant >= 10 ? int(variant % 1000 / 10) : 4;
-        const bool pipe = variant == 0 || variant >= 10;
-        if (pipe && nrhs <= 4) {
-            if (variant / 1000 == 5) GKOC_LAUNCH_CSR_FRAG_PIPE_NB(4, 1, 4, segs, 1, true);
-            else if (variant / 1000 == 6) GKOC_LAUNCH_CSR_FRAG_PIPE_NB(4, 1, 3, segs, 1, true);
-            else if (variant / 1000 == 7) GKOC_LAUNCH_CSR_FRAG_PIPE_NB(4, 1, 2, segs, 1, true);
-            else if (variant / 1000 == 1) GKOC_LAUNCH_CSR_FRAG_PIPE(4, 1, 2, segs);
-            else if (variant / 1000 == 3) GKOC_LAUNCH_CSR_FRAG_PIPE_ST(4, 1, 3, segs, 3);
-            else if (variant / 1000 == 4) GKOC_LAUNCH_CSR_FRAG_PIPE_ST(4, 1, 2, segs, 3);
-            else if (variant / 1000 == 2) GKOC_LAUNCH_CSR_FRAG_PIPE(4, 1, 3, segs);
-            else GKOC_LAUNCH_CSR_FRAG_PIPE(4, 1, 4, segs);
-            GKOC_LAUNCH_OK();
-            return GKOC_OK;
-        }
-        if (pipe && pairs_ok) {
-            if (variant / 1000 == 5) GKOC_LAUNCH_CSR_FRAG_PIPE_NB(8, 2, 3, segs, 1, true);
-            else if (variant / 1000 == 6) GKOC_LAUNCH_CSR_FRAG_PIPE_NB(8, 2, 4, segs, 1, true);
-            else if (variant / 1000 == 7) GKOC_LAUNCH_CSR_FRAG_PIPE_NB(8, 2, 2, segs, 1, true);
-            else if (variant / 1000 == 1) GKOC_LAUNCH_CSR_FRAG_PIPE(8, 2, 2, segs);
-            else if (variant / 1000 == 3) GKOC_LAUNCH_CSR_FRAG_PIPE_ST(8, 2, 3, segs, 3);
-            else if (variant / 1000 == 4) GKOC_LAUNCH_CSR_FRAG_PIPE_ST(8, 2, 2, segs, 3);
-            else if (variant / 1000 == 2) GKOC_LAUNCH_CSR_FRAG_PIPE(8, 2, 4, segs);
-            else GKOC_LAUNCH_CSR_FRAG_PIPE(8, 2, 3, segs);
-            GKOC_LAUNCH_OK();
-            return GKOC_OK;
-        }
-        if (nrhs <= 4 && pairs_ok && variant == 1) {
-            GKOC_LAUNCH_CSR_FRAG(4, 2, 3);          // two lanes per row, a pair of columns each: 32-row waves
-        } else if (nrhs <= 4 && pairs_ok && variant == 2) {
-            GKOC_LAUNCH_CSR_FRAG(4, 2, 4);
-        } else if (nrhs <= 4 && pairs_ok && variant == 3) {
-            GKOC_LAUNCH_CSR_FRAG(4, 2, 2);
-        } else if (nrhs <= 4) {
-            GKOC_LAUNCH_CSR_FRAG(4, 1, 4);          // four lanes per row, one column each
-        } else if (pairs_ok && variant == 1) {
-            GKOC_LAUNCH_CSR_FRAG(8, 2, 4);
-        } else if (pairs_ok && variant == 2) {
-            GKOC_LAUNCH_CSR_FRAG_T(8, 2, 2, 2);     // 32-row waves, two groups side by side
-        } else if (pairs_ok && variant == 3) {
-            GKOC_LAUNCH_CSR_FRAG(8, 2, 5);
-        } else if (pairs_ok) {
-            GKOC_LAUNCH_CSR_FRAG(8, 2, 3);          // four lanes per row, a pair of columns each
-        } else {
-            GKOC_LAUNCH_CSR_FRAG(8, 1, 4);
-        }
-#undef GKOC_LAUNCH_CSR_FRAG
-#undef GKOC_LAUNCH_CSR_FRAG_T
-#undef GKOC_LAUNCH_CSR_FRAG_PIPE
-#undef GKOC_LAUNCH_CSR_FRAG_PIPE_ST
-#undef GKOC_LAUNCH_CSR_FRAG_PIPE_NB
-        GKOC_LAUNCH_OK();
-        return GKOC_OK;
+        return launch_csr_columns<T, I, ADV>(s, n_rows, n_cols, alpha, row_ptrs, col_idxs, vals, b, ldb, beta, c,
+                                             ldc, nrhs);
     }
-    if (nrhs == 2 && vec_ok) {
-        // two right-hand sides: the row-segment walk of the single-column kernel with the two
-        // products of an entry side by side in the LDS ring (csr_spmv_multi_kernel; 8 KB ring of 512
-        // entries).  L256: 1.46 ms against 2.18 ms for one pass per column.
-        const int b_vec_ok = reinterpret_cast<uintptr_t>(b) % (2 * sizeof(T)) == 0 && ldb % 2 == 0;
-        // two entries per lane and load, two load groups in flight (more, smaller loads under way: the
-        // single-column kernel's lesson of round 3): L256 1.457 -> 1.38-1.40 ms = 55 % of 8 TB/s
-        // (profiles/r04_experiments.txt); GKOC_TUNE_CSR_LOAD_GROUPS = 1: four entries, one group
-        if (tune_value(GKOC_TUNE_CSR_LOAD_GROUPS) == 1) {
-            csr_spmv_multi_kernel<T, I, ADV, EV, 1, RINGV / 2, 2><<<grid, block, 0, as_stream(s)>>>(
-                n_rows, n_seg, segs_per_wave, row_ptrs, col_idxs, vals, b, ldb, c, ldc,
-                static_cast<int>(nrhs), alpha, beta, b_vec_ok,
-                tune_value(GKOC_TUNE_MULTI_XCD_CHUNK_ROWS) / (64 * segs_per_wave));
-        } else {
-            csr_spmv_multi_kernel<T, I, ADV, EV / 2, 2, RINGV / 2, 2><<<grid, block, 0, as_stream(s)>>>(
-                n_rows, n_seg, segs_per_wave, row_ptrs, col_idxs, vals, b, ldb, c, ldc,
-                static_cast<int>(nrhs), alpha, beta, b_vec_ok,
-                tune_value(GKOC_TUNE_MULTI_XCD_CHUNK_ROWS) / (64 * segs_per_wave));
-        }
-        GKOC_LAUNCH_OK();
-        return GKOC_OK;
+    if (nrhs == 2 && streams_aligned(vals, col_idxs, pipe_layout<T>::EV)) {
+        return launch_csr_pair<T, I, ADV>(s, n_rows, alpha, row_ptrs, col_idxs, vals, b, ldb, beta, c, ldc);
     }
-    // rows far longer than the rest: their segments are left out here and done by many workgroups
-    // (csr_long_rows.hpp); one right-hand side, 64-row segments
-    csr_long_info lng;
-    if (nrhs == 1 && rows_per_seg == 64 && tune_value(GKOC_TUNE_CSR_LONG_ROWS) != 0) {
-        GKOC_TRY((long_info_of<T, I>(s, n_rows, row_ptrs, &lng)));
-    }
-    const uint32_t* seg_skip = lng.count > 0 ? lng.bits : nullptr;
-    // the hub rows' kernels run BEHIND the row-segment kernel on the caller's stream.  (Round 6 also ran them
-    // BESIDE it - a side stream per calling stream, forked in front of the product and joined behind it by two
-    // events; the two kernels write disjoint rows of c.  The heavy-tailed stand-in took 245.7 us that way
-    // against 231.5 us in sequence, profiles/r06/r06_hub_rows_beside.txt: gone again.)
-    auto hub_kernels = [&](hipStream_t st) {
-        // (the chunk sums go to the CALLING stream's buffer: long_partial_for)
-        csr_flagged_segments_kernel<T, I, ADV><<<dim3(unsigned(lng.count * LONG_PARTS)), dim3(LONG_WG), 0, st>>>(
-            n_rows, row_ptrs, col_idxs, vals, b, ldb, c, ldc, alpha, beta, lng.list, static_cast<T*>(lng.partial));
-        GKOC_LAUNCH_OK();
-        csr_long_rows_fold_kernel<T, I, ADV><<<dim3(unsigned(lng.count)), dim3(64), 0, st>>>(
-            n_rows, row_ptrs, c, ldc, beta, lng.list, static_cast<const T*>(lng.partial));
-        GKOC_LAUNCH_OK();
-        return int(GKOC_OK);
-    };
-    // GKOC_TUNE_CSR_SEGS_PER_WAVE forces 1 or 2 segments per wave (round 6 tried "up to eight for matrices
-    // with short rows" - the heavy-tailed stand-in 256 us with one, 261 with two, 276 with four, 320 with eight
-    // segments; 5-pt 4096^2 325 / 289 / 325 / 315; profiles/r06/r06_segments_per_wave.txt: the size rule above
-    // stays, and the four / eight-segment variants - whose loop over runs of unflagged segments cost every
-    // variant of the kernel 12-16 VGPRs - are gone again)
-    int spw = segs_per_wave;
-    const int64_t forced_spw = tune_value(GKOC_TUNE_CSR_SEGS_PER_WAVE);
-    if (forced_spw == 1 || forced_spw == 2) spw = int(forced_spw);
-    const int64_t n_waves_1 = ceildiv(n_seg, spw);
-    GKOC_REQUIRE(n_waves_1 < (int64_t(1) << 31), GKOC_E_NOT_SUPPORTED, "more than 2^31 row segments");
-    grid = dim3(static_cast<unsigned>(n_waves_1));
-#define GKOC_LAUNCH_PIPE3(E_, U_, MODE_)                                       \
-    csr_spmv_pipe3_kernel<T, I, ADV, rows_per_seg, E_, U_, RINGV, 1, MODE_>    \
-        <<<grid, block, 0, as_stream(s)>>>(                                    \
-            n_rows, n_seg, spw, row_ptrs, col_idxs, vals, b, ldb, c,           \
-            ldc, static_cast<int>(nrhs), alpha, beta, nullptr, xcd_map,        \
-            static_cast<const I*>(nullptr), static_cast<int*>(nullptr),        \
-            int64_t(0), int64_t(0), static_cast<const uint32_t*>(nullptr),     \
-            uint32_t(0), static_cast<const I*>(nullptr),                       \
-            static_cast<const I*>(nullptr), static_cast<const T*>(nullptr),    \
-            static_cast<uint32_t*>(nullptr), uint32_t(0), 0, int64_t(-1),      \
-            seg_skip)
-    // XCD-contiguous wave order needs enough waves per XCD to keep the in-order
-    // window argument valid; below that the plain order is used
-    // ... and is the default for a matrix WITH HUB ROWS (flagged segments): its gathers go all over b, and with
-    // one contiguous eighth of the rows per XCD an L2 holds the lines of its own eighth instead of a share of
-    // everybody's.  Heavy-tailed stand-in 246.6 -> 226.0 us; the stencils lose 0.5-3 % with it (27-pt 256^3
-    // 982 -> 1003, 5-pt 4096^2 274 -> 282) and keep the plain order (profiles/r06/r06_waves_per_workgroup.txt).
-    // GKOC_TUNE_CSR_XCD_MAP: 1 = always, 2 = never.
-    const int64_t xcd_choice = tune_value(GKOC_TUNE_CSR_XCD_MAP);
-    const int xcd_map =
-        ((xcd_choice == 1 || (xcd_choice == 0 && lng.count > 0)) && n_waves_1 >= 8 * 1024) ? 1 : 0;
-    // Measured and rejected on the Flan-like matrix and on L256 (profiles/r02_experiments,
-    // profiles/r02_flan_pmc): 16 / 32 KB rings with 2-4 load groups (fewer resident waves: 299-475 us
-    // against 288), 32-row segments (294), one or two entries per lane and load so that neighbouring
-    // lanes gather neighbouring columns (301-305).  What helped was the row-phase loop
-    // (csr_spmv_pipe.hpp): 295 -> 277 us.
-    // Entries per lane and load x load groups in flight (ring 8 KB): 2 x 3 for double, 4 x 2 for
-    // float - 16 B of values per lane and load, 48 / 32 B in flight.  Measured in one process on L256
-    // (tools/f32_variants.py, profiles/r03_experiments.txt): double 4 x 1 (rounds 1-2) 985 us, 2 x 3
-    // 954, 2 x 4 960, 1 x 6 968, 4 x 2 980, 1 x 8 978, 1 x 4 986; float 8 x 1 (rounds 1-2) 847 us,
-    // 4 x 2 793, 4 x 3 823, 8 x 2 / 4 x 4 / 2 x 8 slower.  By size (tools/csr_layout_ab.py, double): 4.1 M rows
-    // 251 -> 246 us, 8.4 M 510 -> 495, 16.8 M 985 -> 953; the Flan-like matrix (81 per row) 272 both;
-    // 5-pt 4096^2 397 -> 405.
-    constexpr int PE = sizeof(T) == 8 ? 2 : 4, PU = sizeof(T) == 8 ? 3 : 2;
-    // (round 6 also tried two / four / eight WAVES per workgroup, every wave with its own segments and ring - a
-    // grid of one-wave workgroups of short-row segments is paced by the dispatcher: 3.5 ns per wave chip-wide,
-    // profiles/r06_irregular_pmc.txt.  The pace is per wave, not per workgroup: heavy-tailed stand-in 247 / 241 /
-    // 246 / 299 us, every stencil 10-40 % slower; profiles/r06/r06_waves_per_workgroup.txt.)
-    if (vec_ok) {
-        // below 2 M rows the grid is a few rounds deep and the wider layout of rounds 1-2 is as fast or
-        // faster (64^3: 18.4 against 20.7 us; 1 - 2 M rows: equal); key 1 forces it for A/B runs
-        // float values and LONG rows (40 and more entries on average; the count comes with the first product's
-        // look at the row pointers): ONE entry per lane and load, eight load groups - neighbouring lanes then
-        // gather neighbouring entries of a row, whose columns come in runs (a 27-pt stencil with 2 / 3 / 5
-        // unknowns per node, 53 / 79 / 130 per row: 172 -> 165, 200 -> 182, 231 -> 207 us against four entries
-        // per lane; 7 and 27 per row lose 5-6 % with it, and for double all layouts are within 1.5 %:
-        // profiles/r06/r06_load_layouts.txt).  GKOC_TUNE_CSR_LOAD_GROUPS: 3 forces it, 4 = two entries x four
-        // groups, 1 = the wide loads.
-        const int64_t lay = tune_value(GKOC_TUNE_CSR_LOAD_GROUPS);
-        const bool long_float_rows = sizeof(T) == 4 && lng.nnz > 0 && lng.nnz >= 40 * n_rows;
-        if (lay == 3 || (lay == 0 && long_float_rows)) {
-            if (spw == 2) GKOC_LAUNCH_PIPE3(1, 8, 0x2000);
-            else GKOC_LAUNCH_PIPE3(1, 8, 0x1000);
-        } else if (lay == 4) {
-            if (spw == 2) GKOC_LAUNCH_PIPE3(2, 4, 0x2000);
-            else GKOC_LAUNCH_PIPE3(2, 4, 0x1000);
-        } else if (tune_value(GKOC_TUNE_CSR_LOAD_GROUPS) == 1 || n_seg < 32768) {
-            if (spw == 2) {
-                GKOC_LAUNCH_PIPE3(EV, 1, 0x2000);
-            } else {
-                GKOC_LAUNCH_PIPE3(EV, 1, 0x1000);
-            }
-        } else if (spw == 2) {
-            GKOC_LAUNCH_PIPE3(PE, PU, 0x2000);
-        } else {
-            GKOC_LAUNCH_PIPE3(PE, PU, 0x1000);
-        }
-    } else {
-        if (spw == 2) {
-            GKOC_LAUNCH_PIPE3(1, 4, 0x2000);
-        } else {
-            GKOC_LAUNCH_PIPE3(1, 4, 0x1000);
-        }
-    }
-#undef GKOC_LAUNCH_PIPE3
-#undef GKOC_LAUNCH_PIPE3X
-    GKOC_LAUNCH_OK();
-    if (lng.count > 0) GKOC_TRY(hub_kernels(as_stream(s)));
-    return GKOC_OK;
+    // (two columns whose matrix streams are not aligned for vector loads: one pass per column)
+    return launch_csr_single<T, I, ADV>(s, n_rows, alpha, row_ptrs, col_idxs, vals, b, ldb, beta, c, ldc, nrhs);
 }
 
 // The distributed product in ONE kernel (csr_spmv_pipe.hpp, GATE): the interior rows of the rank's
@@ -530,14 +527,9 @@ int launch_csr_gated(gkoc_stream_t s, int64_t n_rows, const I* row_ptrs, const I
     GKOC_REQUIRE(gated_fits(n_rows, head_rows, tail_rows), GKOC_E_NOT_SUPPORTED,
                  "more boundary rows than may wait on the device at once (gkoc_csr_spmv_gated_fits): "
                  "use the join-based product");
-    constexpr int EV = 32 / sizeof(T);
-    constexpr int RINGV = 8192 / sizeof(T);
-    auto aligned = [](const void* v, const void* i) {
-        return reinterpret_cast<uintptr_t>(v) % (EV * sizeof(T)) == 0 &&
-               reinterpret_cast<uintptr_t>(i) % (EV * sizeof(I)) == 0;
-    };
-    GKOC_REQUIRE(aligned(vals, col_idxs) && aligned(bnd_vals, bnd_cols), GKOC_E_NOT_SUPPORTED,
-                 "values / column indices not aligned for vector loads");
+    using lay = pipe_layout<T>;
+    GKOC_REQUIRE(streams_aligned(vals, col_idxs, lay::EV) && streams_aligned(bnd_vals, bnd_cols, lay::EV),
+                 GKOC_E_NOT_SUPPORTED, "values / column indices not aligned for vector loads");
     const int64_t n_int = ceildiv(n_rows - head_rows - tail_rows, 64);
     const int64_t n_bnd = ceildiv(head_rows + tail_rows, 64);
     GKOC_REQUIRE(n_int + n_bnd < (int64_t(1) << 31), GKOC_E_NOT_SUPPORTED, "more than 2^31 row segments");
@@ -548,13 +540,7 @@ int launch_csr_gated(gkoc_stream_t s, int64_t n_rows, const I* row_ptrs, const I
                      "workspace too small (gkoc_x_workspace_bytes(n_rows + 128))");
         partial = static_cast<T*>(work);
     }
-    const dim3 grid(static_cast<unsigned>(n_int + n_bnd)), block(64);
-    constexpr int PE = sizeof(T) == 8 ? 2 : 4, PU = sizeof(T) == 8 ? 3 : 2;
-#define GKOC_LAUNCH_GATED(E_, U_, MODE_)                                                           \
-    csr_spmv_pipe3_kernel<T, I, false, 64, E_, U_, RINGV, 1, MODE_><<<grid, block, 0, as_stream(s)>>>( \
-        n_rows, n_int + n_bnd, 1, row_ptrs, col_idxs, vals, b, 1, c, 1, 1, nullptr, nullptr, partial, 0, \
-        nullptr, nullptr, head_rows, tail_rows, gate, epoch, bnd_ptrs, bnd_cols, bnd_vals, fork_word,    \
-        fork_number, gate_fence, bnd_first)
+    const dim3 grid(static_cast<unsigned>(n_int + n_bnd)), block(64);      // one segment per wave
     // the cheap gate (no agent-scope acquire for a wave that did not wait) rests on the halo lying on
     // 128-byte lines of its own: b on a line boundary and the halo at a multiple of 128 bytes behind it
     // (the documented layout: n_rows rounded up to 32 entries).  A b that is not aligned cannot have that.
@@ -573,18 +559,26 @@ int launch_csr_gated(gkoc_stream_t s, int64_t n_rows, const I* row_ptrs, const I
     // 32-byte load per lane and stream, profiles/r04_dist_sim_variants.txt); GKOC_TUNE_CSR_LOAD_GROUPS = 1
     // selects the other
     const bool wide = tune_value(GKOC_TUNE_CSR_LOAD_GROUPS) == 1;
-    if (dot_out) {
+    // mode: GATE | one segment per wave (0x11000), | 0x40 with the dot product
+    auto launch = [&](auto mode) {
+        auto go = [&](auto e, auto u) {
+            csr_spmv_pipe3_kernel<T, I, false, 64, decltype(e)::value, decltype(u)::value, lay::RINGV, 1,
+                                  decltype(mode)::value><<<grid, block, 0, as_stream(s)>>>(
+                n_rows, n_int + n_bnd, 1, row_ptrs, col_idxs, vals, b, 1, c, 1, 1, nullptr, nullptr, partial, 0,
+                nullptr, nullptr, head_rows, tail_rows, gate, epoch, bnd_ptrs, bnd_cols, bnd_vals, fork_word,
+                fork_number, gate_fence, bnd_first);
+        };
         if (wide) {
-            GKOC_LAUNCH_GATED(EV, 1, 0x11040);
+            go(int_c<lay::EV>{}, int_c<1>{});
         } else {
-            GKOC_LAUNCH_GATED(PE, PU, 0x11040);
+            go(int_c<lay::PE>{}, int_c<lay::PU>{});
         }
-    } else if (wide) {
-        GKOC_LAUNCH_GATED(EV, 1, 0x11000);
+    };
+    if (dot_out) {
+        launch(int_c<0x11040>{});
     } else {
-        GKOC_LAUNCH_GATED(PE, PU, 0x11000);
+        launch(int_c<0x11000>{});
     }
-#undef GKOC_LAUNCH_GATED
     GKOC_LAUNCH_OK();
     if (dot_out) {
         // ONE fold launch whatever the count (<= 2^31 / 64 partial sums would still be one block's
@@ -621,37 +615,28 @@ int launch_csr_mixed(gkoc_stream_t s, int64_t n_rows, int64_t n_cols, const T* a
     GKOC_REQUIRE(ldc >= nrhs && (n_cols == 0 || ldb >= nrhs), GKOC_E_INVALID,
                  "stride smaller than nrhs");
     if (ADV) GKOC_REQUIRE(alpha && beta, GKOC_E_INVALID, "null alpha/beta");
-    const int64_t n_seg = ceildiv(n_rows, 64);
-    const int segs_per_wave = n_seg < 65536 ? 1 : 2;
-    const int64_t n_waves = ceildiv(n_seg, segs_per_wave);
-    GKOC_REQUIRE(n_waves < (int64_t(1) << 31), GKOC_E_NOT_SUPPORTED, "more than 2^31 row segments");
-    const dim3 grid(static_cast<unsigned>(n_waves)), block(64);
+    using lay = pipe_layout<T>;
+    segment_plan p;
+    GKOC_TRY(plan_segments(n_rows, &p));
+    const dim3 grid(static_cast<unsigned>(p.n_waves)), block(64);
     // four entries per lane and load (16 B of values, 16 B of columns); eight need 129 VGPRs
     // (three waves per SIMD)
-    constexpr int EV = 32 / sizeof(T);
-    constexpr int RINGV = 8192 / sizeof(T);
-    const bool vec_ok = reinterpret_cast<uintptr_t>(vals) % (EV * sizeof(V)) == 0 &&
-                        reinterpret_cast<uintptr_t>(col_idxs) % (EV * sizeof(I)) == 0;
-#define GKOC_LAUNCH_MIXED(E_, U_, MODE_)                                                        \
-    csr_spmv_pipe3_kernel<T, I, ADV, 64, E_, U_, RINGV, 1, MODE_, V><<<grid, block, 0, as_stream(s)>>>( \
-        n_rows, n_seg, segs_per_wave, row_ptrs, col_idxs, vals, b, ldb, c, ldc, static_cast<int>(nrhs), \
-        alpha, beta, nullptr, 0)
-    if (vec_ok) {
-        if (segs_per_wave == 2) {
+    const bool vec_ok = streams_aligned(vals, col_idxs, lay::EV);
+    with_store_mode(p.spw, [&](auto mode) {
+        auto launch = [&](auto e, auto u) {
+            csr_spmv_pipe3_kernel<T, I, ADV, 64, decltype(e)::value, decltype(u)::value, lay::RINGV, 1,
+                                  decltype(mode)::value, V><<<grid, block, 0, as_stream(s)>>>(
+                n_rows, p.n_seg, p.spw, row_ptrs, col_idxs, vals, b, ldb, c, ldc, static_cast<int>(nrhs), alpha,
+                beta, nullptr, 0);
+        };
+        if (vec_ok) {
             // (round 3: 2 x 1, 2 x 2, 1 x 2, 1 x 4, 4 x 2 entries x groups all lose, 1000 - 1440 us
             // against 879)
-            GKOC_LAUNCH_MIXED(EV, 1, 0x2000);
+            launch(int_c<lay::EV>{}, int_c<1>{});
         } else {
-            GKOC_LAUNCH_MIXED(EV, 1, 0x1000);
+            launch(int_c<1>{}, int_c<4>{});
         }
-    } else {
-        if (segs_per_wave == 2) {
-            GKOC_LAUNCH_MIXED(1, 4, 0x2000);
-        } else {
-            GKOC_LAUNCH_MIXED(1, 4, 0x1000);
-        }
-    }
-#undef GKOC_LAUNCH_MIXED
+    });
     GKOC_LAUNCH_OK();
     return GKOC_OK;
 }
@@ -692,47 +677,35 @@ int launch_csr_dot(gkoc_stream_t s, int64_t n, const I* row_ptrs,
             }
         }
     }
-    constexpr int rows_per_seg = 64;
-    const int64_t n_seg = ceildiv(n, rows_per_seg);
     // one segment per wave below 4 M rows, as in the plain kernel (a rank's share of a
     // strong-scaling run is that small: 2.1 M rows at 8 ranks, 255 -> 24x us per CG iteration)
-    const int segs_per_wave = n_seg < 65536 ? 1 : 2;
-    const int64_t n_waves = ceildiv(n_seg, segs_per_wave);
-    GKOC_REQUIRE(n_waves < (int64_t(1) << 31), GKOC_E_NOT_SUPPORTED,
-                 "more than 2^31 row segments");
+    using lay = pipe_layout<T>;
+    segment_plan p;
+    GKOC_TRY(plan_segments(n, &p));
     T* partial = static_cast<T*>(work);
     T* scratch = partial + (fused_workspace_bytes(n, sizeof(T)) / sizeof(T) - fold_chunks);
-    dim3 grid(static_cast<unsigned>(n_waves)), block(64);
-    const bool vec_ok =
-        reinterpret_cast<uintptr_t>(vals) % (4 * sizeof(T)) == 0 &&
-        reinterpret_cast<uintptr_t>(col_idxs) % (4 * sizeof(I)) == 0;  // E = 4 below
-    const int xcd_map = (tune_value(GKOC_TUNE_CSR_XCD_MAP) == 1 && n_waves >= 8 * 1024) ? 1 : 0;
-    constexpr int PE = sizeof(T) == 8 ? 2 : 4, PU = sizeof(T) == 8 ? 3 : 2;   // as in launch_csr
+    const dim3 grid(static_cast<unsigned>(p.n_waves)), block(64);
+    const bool vec_ok = streams_aligned(vals, col_idxs, 4);      // (for four entries whatever the type)
+    const int xcd_map = (tune_value(GKOC_TUNE_CSR_XCD_MAP) == 1 && p.n_waves >= 8 * 1024) ? 1 : 0;
     // four waves per SIMD, like the plain product: the dot's registers (and, since round 6, the loop over runs
     // of unflagged segments) had taken the double / int32 kernel to 133 VGPRs = three waves - 985 -> 1107 us on
     // L256 (profiles/r06/r06_bench_kernel_stats_regression.csv); with the bound the compiler stays at 128
     constexpr int DOT_WPS = sizeof(I) == 4 ? 4 : 1;      // (64-bit indices: 161 VGPRs, the bound would spill)
-#define GKOC_LAUNCH_DOT(E_, U_, MODE_)                                               \
-    csr_spmv_pipe3_kernel<T, I, false, rows_per_seg, E_, U_, 1024, DOT_WPS, MODE_>   \
-        <<<grid, block, 0, as_stream(s)>>>(n, n_seg, segs_per_wave, row_ptrs, col_idxs, \
-                                           vals, b, 1, c, 1, 1, nullptr, nullptr,    \
-                                           partial, xcd_map)
-    if (vec_ok) {
-        if (segs_per_wave == 2) {
-            GKOC_LAUNCH_DOT(PE, PU, 0x2040);
+    with_store_mode(p.spw, [&](auto mode) {
+        auto launch = [&](auto e, auto u) {
+            // (mode | 0x40: every wave also emits its part of <b, c>)
+            csr_spmv_pipe3_kernel<T, I, false, 64, decltype(e)::value, decltype(u)::value, 1024, DOT_WPS,
+                                  (decltype(mode)::value | 0x40)><<<grid, block, 0, as_stream(s)>>>(
+                n, p.n_seg, p.spw, row_ptrs, col_idxs, vals, b, 1, c, 1, 1, nullptr, nullptr, partial, xcd_map);
+        };
+        if (vec_ok) {
+            launch(int_c<lay::PE>{}, int_c<lay::PU>{});
         } else {
-            GKOC_LAUNCH_DOT(PE, PU, 0x1040);
+            launch(int_c<1>{}, int_c<4>{});
         }
-    } else {
-        if (segs_per_wave == 2) {
-            GKOC_LAUNCH_DOT(1, 4, 0x2040);
-        } else {
-            GKOC_LAUNCH_DOT(1, 4, 0x1040);
-        }
-    }
-#undef GKOC_LAUNCH_DOT
+    });
     GKOC_LAUNCH_OK();
-    return fold_partials<T>(s, n_waves, partial, scratch, dot_out, false);
+    return fold_partials<T>(s, p.n_waves, partial, scratch, dot_out, false);
 }
 
 // ---- diagonal extraction / sortedness / per-row sort ---------------------
@@ -890,35 +863,30 @@ int csr_spmv_complex(gkoc_stream_t s, int64_t n_rows, int64_t nrhs, const I* row
     // with null arrays / a null b: the thread-per-row kernel never touches them, this one's idle lanes read b[0]
     if (col_idxs == nullptr || vals == nullptr || b == nullptr) return GKOC_E_NOT_SUPPORTED;
     constexpr int E = sizeof(T) == 16 ? 1 : 2, U = sizeof(T) == 16 ? 4 : 2;
-    constexpr int RINGV = 8192 / sizeof(T);
-    if (reinterpret_cast<uintptr_t>(vals) % (E * sizeof(T)) != 0 ||
-        reinterpret_cast<uintptr_t>(col_idxs) % (E * sizeof(I)) != 0 ||
-        reinterpret_cast<uintptr_t>(b) % sizeof(T) != 0 || reinterpret_cast<uintptr_t>(c) % sizeof(T) != 0) {
+    if (!streams_aligned(vals, col_idxs, E) || reinterpret_cast<uintptr_t>(b) % sizeof(T) != 0 ||
+        reinterpret_cast<uintptr_t>(c) % sizeof(T) != 0) {
         return GKOC_E_NOT_SUPPORTED;
     }
-    const int64_t n_seg = ceildiv(n_rows, 64);
-    const int spw = n_seg >= 65536 ? 2 : 1;
-    const int64_t n_waves = ceildiv(n_seg, spw);
-    GKOC_REQUIRE(n_waves < (int64_t(1) << 31), GKOC_E_NOT_SUPPORTED, "more than 2^31 row segments");
-    const dim3 grid(static_cast<unsigned>(n_waves)), block(64);
+    segment_plan p;
+    GKOC_TRY(plan_segments(n_rows, &p));
+    const dim3 grid(static_cast<unsigned>(p.n_waves)), block(64);
     // four waves per SIMD where the kernel is within a few registers of it (complex<double>, 32-bit indices: 132)
     constexpr int CX_WPS = sizeof(I) == 4 ? 4 : 1;
-#define GKOC_LAUNCH_CX(ADV_, MODE_)                                                                 \
-    csr_spmv_pipe3_kernel<T, I, ADV_, 64, E, U, RINGV, (ADV_ ? 1 : CX_WPS), MODE_><<<grid, block, 0, as_stream(s)>>>( \
-        n_rows, n_seg, spw, row_ptrs, col_idxs, vals, b, ldb, c, ldc, static_cast<int>(nrhs), alpha, beta)
-    if (alpha != nullptr) {
-        GKOC_REQUIRE(beta != nullptr, GKOC_E_INVALID, "alpha and beta go together");
-        if (spw == 2) {
-            GKOC_LAUNCH_CX(true, 0x2000);
+    if (alpha != nullptr) GKOC_REQUIRE(beta != nullptr, GKOC_E_INVALID, "alpha and beta go together");
+    with_store_mode(p.spw, [&](auto mode) {
+        auto launch = [&](auto advanced) {
+            constexpr bool ADV = decltype(advanced)::value;
+            csr_spmv_pipe3_kernel<T, I, ADV, 64, E, U, pipe_layout<T>::RINGV, (ADV ? 1 : CX_WPS),
+                                  decltype(mode)::value><<<grid, block, 0, as_stream(s)>>>(
+                n_rows, p.n_seg, p.spw, row_ptrs, col_idxs, vals, b, ldb, c, ldc, static_cast<int>(nrhs), alpha,
+                beta);
+        };
+        if (alpha != nullptr) {
+            launch(std::true_type{});
         } else {
-            GKOC_LAUNCH_CX(true, 0x1000);
+            launch(std::false_type{});
         }
-    } else if (spw == 2) {
-        GKOC_LAUNCH_CX(false, 0x2000);
-    } else {
-        GKOC_LAUNCH_CX(false, 0x1000);
-    }
-#undef GKOC_LAUNCH_CX
+    });
     GKOC_LAUNCH_OK();
     return GKOC_OK;
 }

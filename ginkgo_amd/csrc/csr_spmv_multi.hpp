@@ -9,9 +9,10 @@
 //     stream); lane = E consecutive nonzeros gathers the two values b[col, j0..j0+2)
 //     as one 16 B load, the two products of a nonzero sit next to each other in the
 //     LDS ring, lane = row adds them in k order per column;
-//   * csr_spmv_frag_kernel, three and more columns (chunks of 4 or 8): 16-row waves
-//     with the segment staged in LDS and several lanes per row, so that the lanes of
-//     one gather instruction cover whole rows of b (see there).
+//   * csr_spmv_frag_pipe_kernel, three and more columns (chunks of 4 or 8): 16-row segments
+//     staged in LDS and several lanes per row, so that the lanes of one gather instruction
+//     cover whole rows of b; csr_spmv_frag_kernel is its unpipelined form, which still serves
+//     five and more columns with odd strides or unaligned b / c (see there).
 // In both, every (row, column) sum is formed in the reference's order with separate
 // multiply and add => bit-identical per column to the sequential reference and to the
 // single-column kernel.  Columns beyond nrhs in the last chunk are not stored.
@@ -95,8 +96,8 @@ __device__ __forceinline__ void fmt_row_sum_multi(T (&sum)[NR], int64_t len, int
 
 // CSR, several right-hand sides, FRAGMENT layout (the CSR form of fmt_spmv_frag_kernel in
 // formats.hip): the wave's ROWS-row segment is staged in LDS with coalesced loads as above, then
-// NR / 2 neighbouring lanes share a row, each owning two neighbouring columns, and the wave walks
-// TT groups of 128 / NR rows side by side, KU entries per step.  The lanes of one gather
+// NR / CPL neighbouring lanes share a row, each owning CPL neighbouring columns, and the wave walks
+// its 64 * CPL / NR rows KU entries per step.  The lanes of one gather
 // instruction then cover whole rows of b - for banded / stencil matrices 32 (four columns) or 16
 // (eight) consecutive rows, one contiguous run - where lane = row reads 16 B per lane from 64
 // different rows, and it is the vector L1's line-access rate, not HBM, that bounds the lane = row
@@ -105,7 +106,7 @@ __device__ __forceinline__ void fmt_row_sum_multi(T (&sum)[NR], int64_t len, int
 // column) sum is formed by ONE lane in entry order, separate multiply and add: bit-identical to
 // the reference.  No branches in the entry loop: an entry past the end of a row reads entry 0 of
 // the segment and row 0 of b, and its product is not added.
-template <typename T, typename I, bool ADV, int NR, int CPL, int TT, int KU, bool IDX32>
+template <typename T, typename I, bool ADV, int NR, int CPL, int KU, bool IDX32>
 __global__ __launch_bounds__(64) void csr_spmv_frag_kernel(
     int64_t n_rows, const I* __restrict__ row_ptrs, const I* __restrict__ cols,
     const T* __restrict__ vals, const T* __restrict__ b, int64_t ldb, T* __restrict__ c,
@@ -115,8 +116,7 @@ __global__ __launch_bounds__(64) void csr_spmv_frag_kernel(
     static_assert(NR == 2 || NR == 4 || NR == 8, "chunks of 2, 4 or 8 columns");
     static_assert(CPL == 1 || CPL == 2, "one or two columns per lane");
     constexpr int LPR = NR / CPL;     // lanes per row
-    constexpr int RPP = 64 / LPR;     // rows per group
-    constexpr int ROWS = RPP * TT;    // rows per wave
+    constexpr int ROWS = 64 / LPR;    // rows per wave
     constexpr int CAP = ROWS * 32;    // staged entries (12 B each)
     using BV = vecT<T, CPL>;
     __shared__ __attribute__((aligned(16))) T lv[CAP];
@@ -145,19 +145,13 @@ __global__ __launch_bounds__(64) void csr_spmv_frag_kernel(
         }
         wave_lds_sync();
     }
-    int64_t row[TT];
-    int rs[TT], len[TT];
-    int maxlen = 0;
-#pragma unroll
-    for (int t = 0; t < TT; ++t) {
-        row[t] = row0 + rl + RPP * t;
-        const int64_t r = row[t] < last ? row[t] : last;
-        const int64_t a = row_ptrs[r];
-        const int64_t e = row[t] < last ? int64_t(row_ptrs[r + 1]) : a;
-        rs[t] = int(a - K0);
-        len[t] = int(e - a);
-        maxlen = len[t] > maxlen ? len[t] : maxlen;
-    }
+    const int64_t row = row0 + rl;
+    const int64_t r = row < last ? row : last;
+    const int64_t a = row_ptrs[r];
+    const int64_t e = row < last ? int64_t(row_ptrs[r + 1]) : a;
+    const int rs = int(a - K0);
+    const int len = int(e - a);
+    const int maxlen = len > 0 ? len : 0;
     int wave_maxlen = maxlen;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -171,52 +165,41 @@ __global__ __launch_bounds__(64) void csr_spmv_frag_kernel(
         // (ldb is even where pairs are used, so ldb > nrhs when nrhs is odd); a lane without
         // columns reads the first ones
         const int jl = ncol >= 1 ? jc : 0;
-        T sum[TT][CPL];
+        T sum[CPL];
 #pragma unroll
-        for (int t = 0; t < TT; ++t) {
-#pragma unroll
-            for (int q = 0; q < CPL; ++q) {
-                sum[t][q] = T(0);
-                if (ADV && beta != T(0) && row[t] < last && q < ncol) {
-                    sum[t][q] = c[row[t] * ldc + jc + q] * beta;
-                }
-            }
+        for (int q = 0; q < CPL; ++q) {
+            sum[q] = T(0);
+            if (ADV && beta != T(0) && row < last && q < ncol) sum[q] = c[row * ldc + jc + q] * beta;
         }
-        // entries [kb, ke) of every row, entry k of the lane's row t at LDS slot base[t] + k
-        auto walk = [&](auto tiled_tag, int kb, int ke, const int (&base)[TT]) {
+        // entries [kb, ke) of every row, entry k of the lane's row at LDS slot base + k
+        auto walk = [&](auto tiled_tag, int kb, int ke, int base) {
             constexpr bool TILED = decltype(tiled_tag)::value;
             const int kend = TILED && ke < maxlen ? ke : maxlen;
             for (int k = kb; k < kend; k += KU) {
-                BV x[KU][TT];
-                T vv[KU][TT];
-                bool ok[KU][TT];
+                BV x[KU];
+                T vv[KU];
+                bool ok[KU];
 #pragma unroll
                 for (int u = 0; u < KU; ++u) {
-#pragma unroll
-                    for (int t = 0; t < TT; ++t) {
-                        ok[u][t] = k + u < len[t] && (!TILED || k + u < ke);
-                        const int at = ok[u][t] ? base[t] + k + u : 0;
-                        const I cc = lc[at];
-                        vv[u][t] = lv[at];
-                        const I ce = ok[u][t] ? cc : I(0);
-                        if (IDX32) {
-                            const uint32_t off = uint32_t(ce) * uint32_t(ldb) + uint32_t(jl);
-                            x[u][t] = *reinterpret_cast<const BV*>(b + off);
-                        } else {
-                            x[u][t] = *reinterpret_cast<const BV*>(b + int64_t(ce) * ldb + jl);
-                        }
+                    ok[u] = k + u < len && (!TILED || k + u < ke);
+                    const int at = ok[u] ? base + k + u : 0;
+                    const I cc = lc[at];
+                    vv[u] = lv[at];
+                    const I ce = ok[u] ? cc : I(0);
+                    if (IDX32) {
+                        const uint32_t off = uint32_t(ce) * uint32_t(ldb) + uint32_t(jl);
+                        x[u] = *reinterpret_cast<const BV*>(b + off);
+                    } else {
+                        x[u] = *reinterpret_cast<const BV*>(b + int64_t(ce) * ldb + jl);
                     }
                 }
 #pragma unroll
                 for (int u = 0; u < KU; ++u) {
+                    const T av = ADV ? alpha * vv[u] : vv[u];
 #pragma unroll
-                    for (int t = 0; t < TT; ++t) {
-                        const T a = ADV ? alpha * vv[u][t] : vv[u][t];
-#pragma unroll
-                        for (int q = 0; q < CPL; ++q) {
-                            const T nx = sum[t][q] + a * x[u][t].v[q];
-                            sum[t][q] = ok[u][t] ? nx : sum[t][q];
-                        }
+                    for (int q = 0; q < CPL; ++q) {
+                        const T nx = sum[q] + av * x[u].v[q];
+                        sum[q] = ok[u] ? nx : sum[q];
                     }
                 }
             }
@@ -227,34 +210,28 @@ __global__ __launch_bounds__(64) void csr_spmv_frag_kernel(
             for (int c0 = 0; c0 < wave_maxlen; c0 += 32) {
                 wave_lds_sync();   // the previous round has been read
                 for (int i = lane; i < CAP; i += 64) {
-                    const int64_t r = row0 + (i >> 5);
-                    if (r < last) {
-                        const int64_t a = row_ptrs[r];
-                        if (a + c0 + (i & 31) < int64_t(row_ptrs[r + 1])) {
-                            lv[i] = vals[a + c0 + (i & 31)];
-                            lc[i] = cols[a + c0 + (i & 31)];
+                    const int64_t sr = row0 + (i >> 5);
+                    if (sr < last) {
+                        const int64_t ra = row_ptrs[sr];
+                        if (ra + c0 + (i & 31) < int64_t(row_ptrs[sr + 1])) {
+                            lv[i] = vals[ra + c0 + (i & 31)];
+                            lc[i] = cols[ra + c0 + (i & 31)];
                         }
                     }
                 }
                 wave_lds_sync();
-                int base[TT];
-#pragma unroll
-                for (int t = 0; t < TT; ++t) base[t] = 32 * (rl + RPP * t) - c0;
-                walk(std::true_type{}, c0, c0 + 32, base);
+                walk(std::true_type{}, c0, c0 + 32, 32 * rl - c0);
             }
         }
+        if (row < last && ncol > 0) {
+            T* __restrict__ cp = c + row * ldc + jc;
+            if (ncol == CPL) {
+                BV q;
 #pragma unroll
-        for (int t = 0; t < TT; ++t) {
-            if (row[t] < last && ncol > 0) {
-                T* __restrict__ cp = c + row[t] * ldc + jc;
-                if (ncol == CPL) {
-                    BV q;
-#pragma unroll
-                    for (int i = 0; i < CPL; ++i) q.v[i] = sum[t][i];
-                    *reinterpret_cast<BV*>(cp) = q;
-                } else {
-                    cp[0] = sum[t][0];
-                }
+                for (int i = 0; i < CPL; ++i) q.v[i] = sum[i];
+                *reinterpret_cast<BV*>(cp) = q;
+            } else {
+                cp[0] = sum[0];
             }
         }
     }
@@ -276,8 +253,12 @@ __global__ __launch_bounds__(64) void csr_spmv_frag_kernel(
 // order, separate multiply and add - bit-identical to the kernel above and to the reference.  A segment
 // with more than CAP entries takes the rounds of the kernel above (not pipelined).
 //
-// NB (round 6): a value of b that the row BELOW has just gathered is taken from that row's lanes instead of
-// the memory system.  In a banded / stencil matrix entry k of row r and entry k - 1 of row r + 1 are the same
+// NB (round 6; measured slower - 2.39-2.84 ms against 1.76-2.05 on L256 with 3 / 4 / 8 columns,
+// profiles/r06/r06_multi_rhs_baseline.txt, DESIGN.md 0 item 4 - and not instantiated any more.  The code stays:
+// without it the compiler allocates the registers of the kernels that ARE launched differently, 99-100 -> 102
+// VGPRs for float / int32 with eight columns): a value of b that the row BELOW has just gathered is taken from
+// that row's lanes instead of the memory system.
+// In a banded / stencil matrix entry k of row r and entry k - 1 of row r + 1 are the same
 // column (r + 1 + dx - 1 = r + dx): the 16 rows of a wave ask for the same 15 rows of b again with every step
 // through a run of neighbouring columns, and the in-order vector L1 stalls on every one of those hits while
 // the line is still on its way (TCP_PENDING_STALL_CYCLES 44 %, 0.59 line accesses per cycle and CU where the
@@ -287,7 +268,7 @@ __global__ __launch_bounds__(64) void csr_spmv_frag_kernel(
 // still issues its load - branch-free, the compiler keeps all loads of a round in flight - but from row 0 of
 // b, one line for all of them: a gather instruction touches 2 lines instead of 8.  The values are the same
 // numbers whichever way they come: the sums keep the reference's bits.
-template <typename T, typename I, bool ADV, int NR, int CPL, int KU, bool IDX32, int ST = 1, bool NB = false>
+template <typename T, typename I, bool ADV, int NR, int CPL, int KU, bool IDX32, bool NB = false>
 __global__ __launch_bounds__(64) void csr_spmv_frag_pipe_kernel(
     int64_t n_rows, const I* __restrict__ row_ptrs, const I* __restrict__ cols,
     const T* __restrict__ vals, const T* __restrict__ b, int64_t ldb, T* __restrict__ c,
@@ -448,53 +429,6 @@ __global__ __launch_bounds__(64) void csr_spmv_frag_pipe_kernel(
                     if constexpr (NB) xlast = x[KU - 1];
                 };
                 if (kb >= kend) return;
-                if constexpr (ST > 1) {
-                    // STRIDED rounds.  Neighbouring entries of a row of a banded / stencil matrix are
-                    // neighbouring rows of b, and the 16 rows of the wave make the gathers of entries k and
-                    // k + 1 overlap in 15 of their 16 rows: the second gather hits lines that are still on
-                    // their way, and the vector L1 - in order - stalls on such a hit until the data is back
-                    // (TCP_PENDING_STALL_CYCLES = 44 % of the cycles, profiles/r05_multi_rhs_pmc.txt).  So
-                    // a round asks for entries k, k + ST, k + 2 ST, ... (different lines), waits for them,
-                    // and only then for k + 1, k + 1 + ST, ... - which now HIT.  The products are added in
-                    // entry order afterwards: the same sums.
-                    for (int k = kb; k < kend; k += KU * ST) {
-                        BV x[ST][KU];
-                        T vv[ST][KU];
-                        bool ok[ST][KU];
-#pragma unroll
-                        for (int st = 0; st < ST; ++st) {
-#pragma unroll
-                            for (int u = 0; u < KU; ++u) {
-                                const int kk = k + st + ST * u;
-                                ok[st][u] = kk < len && kk < klimit;
-                                const int at = ok[st][u] ? base + kk : 0;
-                                const I cc = lc[at];
-                                vv[st][u] = lv[at];
-                                const I ce = ok[st][u] ? cc : I(0);
-                                if (IDX32) {
-                                    const uint32_t off = uint32_t(ce) * uint32_t(ldb) + uint32_t(jl);
-                                    x[st][u] = *reinterpret_cast<const BV*>(b + off);
-                                } else {
-                                    x[st][u] = *reinterpret_cast<const BV*>(b + int64_t(ce) * ldb + jl);
-                                }
-                            }
-                            if (st + 1 < ST) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                        }
-#pragma unroll
-                        for (int u = 0; u < KU; ++u) {
-#pragma unroll
-                            for (int st = 0; st < ST; ++st) {
-                                const T av = ADV ? alpha * vv[st][u] : vv[st][u];
-#pragma unroll
-                                for (int q = 0; q < CPL; ++q) {
-                                    const T nx = sum[q] + av * x[st][u].v[q];
-                                    sum[q] = ok[st][u] ? nx : sum[q];
-                                }
-                            }
-                        }
-                    }
-                    return;
-                }
                 request(kb, x0, v0, ok0, nb0);
                 int k = kb;
                 while (true) {

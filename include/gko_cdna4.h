@@ -174,8 +174,7 @@ int gkoc_arena_probe(const void* x, size_t x_bytes, void* y, int read_kb_per_wav
                                       xcd_chunked_block); 0: every 8th workgroup (plain dispatch order) */
 #define GKOC_TUNE_CSR_LOAD_GROUPS 2 /* csr::spmv, one column: 0 (default) two entries per lane and load, three load
                                       groups in flight (float: four entries, two groups); 1: four (eight) entries,
-                                      one group - the layout of rounds 1-2, kept for A/B measurements; 2: the
-                                      default layout also where the size rule picks the other (small products);
+                                      one group - the layout of rounds 1-2, kept for A/B measurements;
                                       3: one entry per lane and load, eight groups - since round 6 what 0 picks for
                                       float values with 40 and more entries per row; 4: two entries, four groups */
 #define GKOC_TUNE_GATE_FENCE 7      /* one-kernel distributed product (gkoc_csr_spmv_gated_*): 0 (default) only a
@@ -193,17 +192,22 @@ int gkoc_arena_probe(const void* x, size_t x_bytes, void* y, int read_kb_per_wav
                                       jacobi::simple_apply(M, r -> z), the next step_2 runs as ONE kernel with that
                                       application (x, r exist when step_2 returns as always; z = M r is written
                                       early, the application call that follows launches nothing); 0: off */
-#define GKOC_TUNE_CSR_MULTI_VARIANT 11 /* csr::spmv with three to eight right-hand sides: layout variants kept for A/B
-                                      measurements (csrc/csr_spmv.hip); 0 = the default chosen by measurement */
+#define GKOC_TUNE_CSR_MULTI_VARIANT 11 /* (not read any more) csr::spmv with three and more right-hand sides: the
+                                      kernel of rounds 3-4 and its layouts, other entries-per-step and
+                                      segments-per-wave choices of the pipelined kernel, strided rounds and
+                                      values handed over by the row below - none was faster than the default, the
+                                      variants are gone (profiles/r05_multi_rhs_pmc.txt,
+                                      profiles/r06/r06_multi_rhs_baseline.txt) */
 #define GKOC_TUNE_CSR_LONG_ROWS 12   /* csr::spmv, one right-hand side: 1 (default) the 64-row segments that hold a row
                                       longer than GKOC_CSR_LONG_ROW are found once per matrix (one scan of the row
                                       pointers, remembered per (row_ptrs, n_rows)) and multiplied by many workgroups
                                       each (csrc/csr_long_rows.hpp) instead of by one wave; 0: one wave, as before.
-                                      Two products with the SAME matrix must not run at the same time on two streams
-                                      when it has such rows (they share the chunk sums' scratch) */
+                                      The chunk sums go to a buffer per (matrix, stream): products with the SAME
+                                      matrix may run at the same time on several streams */
 #define GKOC_TUNE_CSR_SEGS_PER_WAVE 13 /* csr::spmv, one right-hand side: 64-row segments a wave walks.  0 (default): two
-                                      from 4 M rows on, one below; 1, 2: that many (round 6 tried four and eight
-                                      on rows of a dozen entries: never faster - profiles/r06/) */
+                                      from 4 M rows on, one below; 1, 2: that many.  Only 1 and 2 are honoured, any
+                                      other value is the rule (round 6 tried four and eight on rows of a dozen
+                                      entries: never faster - profiles/r06/) */
 #define GKOC_TUNE_CSR_SHORT_ROWS 14 /* (not read any more) round 6's experiments on matrices with a dozen entries per
                                       row - smaller rings and load groups, non-temporal / agent-scope gathers, two
                                       to eight waves per workgroup: none was faster than the launcher's rule, the

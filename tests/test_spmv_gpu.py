@@ -458,11 +458,12 @@ def _short_rows_with_hubs(rng, n, ncols, hubs):
 
 @pytest.mark.parametrize("spw", [0, 1, 2, 4, 8])
 def test_csr_short_rows_several_segments_per_wave(gexec, oracle, spw):
-    """round 6: matrices with short rows give a wave up to eight 64-row segments (GKOC_TUNE_CSR_SEGS_PER_WAVE,
-    0 = the launcher's rule).  Segments with a row beyond GKOC_CSR_LONG_ROW are left to the flagged-segments
-    kernel - here they sit at the start, in the middle and at the end of an eight-segment wave, and two of them
-    are neighbours - and the ordinary rows next to a hub (170 and 3000 entries among them) keep the reference's
-    bits through the products-in-LDS path.  c = A b and c = alpha A b + beta c."""
+    """GKOC_TUNE_CSR_SEGS_PER_WAVE: 1 and 2 force that many 64-row segments per wave, 0 is the launcher's rule,
+    and 4 and 8 (round 6's variants for short rows, gone again) fall back to the rule.  Segments with a row beyond
+    GKOC_CSR_LONG_ROW are left to the flagged-segments kernel - here they sit at the start, in the middle and
+    towards the end of the matrix, and two of them are neighbours - and the ordinary rows next to a hub (170 and
+    3000 entries among them) keep the reference's bits through the products-in-LDS path.  c = A b and
+    c = alpha A b + beta c."""
     import ginkgo_amd as g
     rng = np.random.default_rng(100 + spw)
     n, ncols = 64 * 37 + 11, 20000
@@ -555,10 +556,11 @@ def test_csr_long_rows_two_streams_at_once(gexec, oracle):
 @pytest.mark.parametrize("variant", [5040, 6040, 7040, 5020])
 @pytest.mark.parametrize("nrhs", [3, 4, 8])
 def test_csr_multi_rhs_neighbour_reuse_variants(gexec, oracle, variant, nrhs):
-    """round 6 (csr_spmv_frag_pipe_kernel NB): a value of b the row below has just gathered is taken from that
-    row's lanes - decided on the column indices, so any matrix may come: a banded one (where it applies almost
-    everywhere), a random one (almost nowhere), rows of different lengths, empty rows, one past the staging
-    capacity; every column bit-identical to the sequential reference"""
+    """three and more right-hand sides (csr_spmv_frag_pipe_kernel) on a banded matrix with empty rows and rows
+    with holes and on a random one with rows of different lengths, empty rows and one past the staging
+    capacity; every column bit-identical to the sequential reference.  (Written for round 6's neighbour-reuse
+    variants of GKOC_TUNE_CSR_MULTI_VARIANT; the key is not read any more, so every value pins the default
+    kernel on these matrices.)"""
     import ginkgo_amd as g
     rng = np.random.default_rng(variant + nrhs)
     n = 16 * 40 + 5
