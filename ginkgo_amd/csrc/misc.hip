@@ -325,11 +325,10 @@ extern "C" int gkoc_fill_array_small(gkoc_stream_t s, void* data, int64_t n, int
 
 // csr::spgemm_reuse / advanced_spgemm_reuse / spgeam_numeric (core/matrix/csr_kernels.hpp:60-92;
 // reference/matrix/csr_kernels.cpp:304-436, :474-499): the values of a product or sum whose
-// sparsity pattern exists already.  One lane per row of C, entries added in the reference's
-// order.  The position of a column in C's row is found by bisection of its (sorted) column
-// indices - Ginkgo's per-row lookup structures (bitmaps / hash tables, csr_lookup.hpp) are
-// consumed by device kernels only, so this backend keeps none (build_lookup_offsets /
-// build_lookup of the binding write empty ones).
+// sparsity pattern exists already.  One lane per row of C (grid-stride over the rows), entries
+// added in the reference's order.  The position of a column in C's row is found by bisection of
+// its (sorted) column indices; the per-row lookup tables that csr_lookup.hip builds (bitmaps /
+// hash tables, csr_lookup.hpp) serve Ginkgo's factorisations and are not consulted here.
 namespace gkoc {
 namespace {
 
@@ -360,25 +359,26 @@ __global__ __launch_bounds__(256) void spgemm_reuse_kernel(
     const I* __restrict__ d_cols, const T* __restrict__ d_vals, const I* __restrict__ c_ptrs,
     const I* __restrict__ c_cols, T* __restrict__ c_vals)
 {
-    const int64_t row = int64_t(blockIdx.x) * 256 + threadIdx.x;
-    if (row >= n_rows) return;
-    const int64_t cb = c_ptrs[row], ce = c_ptrs[row + 1];
-    for (int64_t k = cb; k < ce; ++k) c_vals[k] = T(0);
     const bool adv = alpha != nullptr;
     const T va = adv ? alpha[0] : T(1);
-    for (int64_t an = a_ptrs[row]; an < a_ptrs[row + 1]; ++an) {
-        const int64_t ac = a_cols[an];
-        const T av = a_vals[an];
-        for (int64_t bn = b_ptrs[ac]; bn < b_ptrs[ac + 1]; ++bn) {
-            const int64_t pos = find_col<I>(c_cols, cb, ce, b_cols[bn]);
-            if (pos >= 0) c_vals[pos] += adv ? va * av * b_vals[bn] : av * b_vals[bn];
+    const T vb = adv ? beta[0] : T(0);
+    GKOC_FOR(row, n_rows)
+    {
+        const int64_t cb = c_ptrs[row], ce = c_ptrs[row + 1];
+        for (int64_t k = cb; k < ce; ++k) c_vals[k] = T(0);
+        for (int64_t an = a_ptrs[row]; an < a_ptrs[row + 1]; ++an) {
+            const int64_t ac = a_cols[an];
+            const T av = a_vals[an];
+            for (int64_t bn = b_ptrs[ac]; bn < b_ptrs[ac + 1]; ++bn) {
+                const int64_t pos = find_col<I>(c_cols, cb, ce, b_cols[bn]);
+                if (pos >= 0) c_vals[pos] += adv ? va * av * b_vals[bn] : av * b_vals[bn];
+            }
         }
-    }
-    if (adv) {
-        const T vb = beta[0];
-        for (int64_t dn = d_ptrs[row]; dn < d_ptrs[row + 1]; ++dn) {
-            const int64_t pos = find_col<I>(c_cols, cb, ce, d_cols[dn]);
-            if (pos >= 0) c_vals[pos] += vb * d_vals[dn];
+        if (adv) {
+            for (int64_t dn = d_ptrs[row]; dn < d_ptrs[row + 1]; ++dn) {
+                const int64_t pos = find_col<I>(c_cols, cb, ce, d_cols[dn]);
+                if (pos >= 0) c_vals[pos] += vb * d_vals[dn];
+            }
         }
     }
 }
@@ -391,20 +391,21 @@ __global__ __launch_bounds__(256) void spgeam_numeric_kernel(
     const I* __restrict__ b_cols, const T* __restrict__ b_vals, const I* __restrict__ c_ptrs,
     T* __restrict__ c_vals)
 {
-    const int64_t row = int64_t(blockIdx.x) * 256 + threadIdx.x;
-    if (row >= n_rows) return;
     const T va = alpha[0], vb = beta[0];
-    int64_t ia = a_ptrs[row], ib = b_ptrs[row], out = c_ptrs[row];
-    const int64_t ea = a_ptrs[row + 1], eb = b_ptrs[row + 1], ec = c_ptrs[row + 1];
-    while ((ia < ea || ib < eb) && out < ec) {
-        const int64_t ca = ia < ea ? int64_t(a_cols[ia]) : INT64_MAX;
-        const int64_t cbv = ib < eb ? int64_t(b_cols[ib]) : INT64_MAX;
-        const int64_t col = ca < cbv ? ca : cbv;
-        const T av = ca == col ? a_vals[ia] : T(0);
-        const T bv = cbv == col ? b_vals[ib] : T(0);
-        c_vals[out++] = va * av + vb * bv;
-        ia += ca == col;
-        ib += cbv == col;
+    GKOC_FOR(row, n_rows)
+    {
+        int64_t ia = a_ptrs[row], ib = b_ptrs[row], out = c_ptrs[row];
+        const int64_t ea = a_ptrs[row + 1], eb = b_ptrs[row + 1], ec = c_ptrs[row + 1];
+        while ((ia < ea || ib < eb) && out < ec) {
+            const int64_t ca = ia < ea ? int64_t(a_cols[ia]) : INT64_MAX;
+            const int64_t cbv = ib < eb ? int64_t(b_cols[ib]) : INT64_MAX;
+            const int64_t col = ca < cbv ? ca : cbv;
+            const T av = ca == col ? a_vals[ia] : T(0);
+            const T bv = cbv == col ? b_vals[ib] : T(0);
+            c_vals[out++] = va * av + vb * bv;
+            ia += ca == col;
+            ib += cbv == col;
+        }
     }
 }
 

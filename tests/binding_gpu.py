@@ -1,7 +1,10 @@
 """Device buffers for the tests that call gkoc_* entry points directly (tests/test_idr_gpu.py,
-test_cb_gmres_gpu.py, test_dense_gpu.py): any numpy dtype travels as bytes, strided operands are cut out of
-a padded array whose padding keeps a canary."""
+test_cb_gmres_gpu.py, test_dense_gpu.py, test_csr_struct_gpu.py, test_csr_diag_gpu.py): any numpy dtype
+travels as bytes, strided operands are cut out of a padded array whose padding keeps a canary, flat outputs
+are followed by one."""
 import ctypes as C
+import os
+import re
 
 import numpy as np
 
@@ -47,3 +50,38 @@ def same_bits(a, b):
 def sync():
     import torch
     torch.cuda.synchronize()
+
+
+def call(name, *args):
+    from ginkgo_amd._lib import call as lib_call
+    lib_call(name, *args)
+
+
+class DevCsr:
+    """a Csr matrix (or pattern) on the device in index type it, with the host arrays it was made from"""
+
+    def __init__(self, gexec, it, ptrs, cols, vals=None):
+        self.host = [np.asarray(ptrs).astype(it), np.asarray(cols).astype(it)] + \
+            ([np.ascontiguousarray(vals)] if vals is not None else [])
+        self.dev = [Dev(gexec, h) for h in self.host]
+
+    def unchanged(self):
+        return all(same_bits(d.get(), h) for d, h in zip(self.dev, self.host))
+
+
+def out_buf(gexec, n, t, fill=np.nan, tail=3):
+    """device array of n entries `fill` followed by `tail` canaries"""
+    a = np.full(n + tail, fill, t)
+    a[n:] = CANARY
+    return Dev(gexec, a)
+
+
+def tail_ok(got, n):
+    return np.all(got[n:] == got.dtype.type(CANARY))
+
+
+def grid_cap_rows():
+    """256 * 4 * max_stream_blocks (csrc/common.hpp): the number of threads the capped launchers start"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    text = open(os.path.join(root, "ginkgo_amd", "csrc", "common.hpp")).read()
+    return 256 * 4 * int(re.search(r"constexpr\s+int\s+max_stream_blocks\s*=\s*(\d+)\s*;", text).group(1))
