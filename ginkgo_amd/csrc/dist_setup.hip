@@ -38,12 +38,16 @@ struct w16 {
     uint64_t a, b;
 };
 
-// RAII-less scratch helper: allocations are handed back in stream order by release()
+// scratch helper: allocations are handed back in stream order by release(), or when the set goes
+// out of scope (an error return between get() and release())
 struct scratch_set {
     hipStream_t st;
     void* ptrs[12];
     int n = 0;
     explicit scratch_set(hipStream_t s) : st(s) {}
+    scratch_set(const scratch_set&) = delete;
+    scratch_set& operator=(const scratch_set&) = delete;
+    ~scratch_set() { release(); }
     template <typename T>
     int get(T** p, int64_t count)
     {
@@ -452,6 +456,7 @@ int build_mapping_fill(gkoc_stream_t s, const gkoc_partition* part, void* state,
         mapping_fill_kernel<L, G><<<dim3(grid_of(ms->n)), dim3(256), 0, st>>>(
             ms->n, ms->parts, static_cast<const G*>(ms->gids), ms->pos_u, ms->pos_p, view_of<L, G>(part),
             part_ids_out, remote_local, remote_global, starts_next);
+        if (hipGetLastError() != hipSuccess) rc = GKOC_E_INVALID;
         mapping_sizes_kernel<<<dim3(grid_of(ms->n_part_unique)), dim3(256), 0, st>>>(
             ms->n_part_unique, ms->n_unique, starts_next, remote_sizes);
         if (hipGetLastError() != hipSuccess) rc = GKOC_E_INVALID;
@@ -490,6 +495,12 @@ __global__ __launch_bounds__(256) void map_to_local_kernel(
     GKOC_GRID_STRIDE(i, n)
     {
         const G gid = gids[i];
+        // a query outside [bounds[0], bounds[num_ranges]) is in no index space (find_range would
+        // answer num_ranges, one past pids)
+        if (p.num_ranges <= 0 || gid < p.bounds[0] || gid >= p.bounds[p.num_ranges]) {
+            out[i] = invalid;
+            continue;
+        }
         const int64_t rr = find_range(gid, p.bounds, p.num_ranges);
         const int32_t pid = p.pids[rr];
         L res = invalid;

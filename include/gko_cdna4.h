@@ -1268,7 +1268,17 @@ GKOC_DECL_MISC_I(int64_t, i64)
  * values are moved as words of value_size = 4, 8 or 16 bytes (float, double, complex<float>,
  * complex<double>).  Suffixes: <L>_<G> = local / global index type (i32_i32, i32_i64, i64_i64).
  * Outputs whose length depends on the data come from a _count call (sizes to the host, an opaque
- * state that the matching _fill call consumes and releases). */
+ * state that the matching _fill call consumes and releases).  A _count call on empty input
+ * (nnz / n = 0) gives state = NULL and zero sizes; a _fill call with state = NULL does nothing
+ * and returns GKOC_OK.  A state that is not filled goes back through gkoc_dist_separate_state_free /
+ * gkoc_index_map_mapping_state_free (NULL is fine); a state is filled or freed exactly once.
+ * PRECONDITION on ids: every global row / column / received index handed to separate_local_nonlocal,
+ * vector_build_local, build_mapping and count_non_owning_entries lies in
+ * [range_bounds[0], range_bounds[num_ranges]) of the partition it is looked up in; the kernels do
+ * not check it (an id at or above the last bound would read part_ids[num_ranges]).  The one
+ * exception is map_to_local, whose input is a query: see there.
+ * A value_size other than 4, 8 or 16 returns GKOC_E_NOT_SUPPORTED and writes nothing
+ * (separate_local_nonlocal_fill still releases its state). */
 typedef struct gkoc_partition {
     int64_t num_ranges;
     int32_t num_parts;
@@ -1289,13 +1299,21 @@ typedef struct gkoc_partition {
         size_t value_size, const gkoc_partition* row_part, const gkoc_partition* col_part,          \
         void* state, L* local_rows, L* local_cols, void* local_vals, L* non_local_rows,             \
         G* non_local_cols, void* non_local_vals);                                                   \
-    /* distributed_vector::build_local (vector_kernels.hpp:23-33) */                                \
+    /* distributed_vector::build_local (vector_kernels.hpp:23-33): local_values[lrow * ld + col]   \
+     * = value for the entries whose row local_part owns; everything else of local_values is left   \
+     * as it is.  The (row, col) pairs must be distinct: duplicates are written concurrently and   \
+     * which of them stays is not defined (the reference keeps the last one). */                    \
     int gkoc_dist_vector_build_local_##LN##_##GN(                                                   \
         gkoc_stream_t s, int64_t nnz, const G* rows, const G* cols, const void* vals,               \
         size_t value_size, const gkoc_partition* part, int32_t local_part, void* local_values,      \
         int64_t ld);                                                                                \
     /* index_map::build_mapping / map_to_local / map_to_global (index_map_kernels.hpp:40-102);      \
-     * index_space: 0 local, 1 non_local, 2 combined */                                             \
+     * index_space: 0 local, 1 non_local, 2 combined.  build_mapping: the unique received ids       \
+     * ordered by (owning part, id), the parts that occur and the number of ids of each;            \
+     * remote_local_idxs = the owner's local index.  map_to_local answers -1 for an id that is not  \
+     * in the index space, and also for an id outside [range_bounds[0], range_bounds[num_ranges])   \
+     * (checked before the partition is read); map_to_global answers -1 for a local id that is      \
+     * negative or not below the size of the index space. */                                        \
     int gkoc_index_map_build_mapping_count_##LN##_##GN(                                             \
         gkoc_stream_t s, int64_t n, const G* recv_connections, const gkoc_partition* part,          \
         void** state, int64_t* n_unique, int64_t* n_part_unique);                                   \
@@ -1330,7 +1348,11 @@ GKOC_DECL_DIST_LG(int64_t, i64, int64_t, i64)
                                                G* range_bounds, int32_t* part_ids);                 \
     int gkoc_partition_build_ranges_from_global_size_##GN(gkoc_stream_t s, int32_t num_parts,       \
                                                           G global_size, G* ranges);                \
-    /* partition_helpers (partition_helpers_kernels.hpp): (start, end) pairs per part */            \
+    /* partition::build_from_contiguous / build_from_mapping: range_bounds[0] = 0; with            \
+     * num_ranges = 0 / n = 0 that is all they write.                                               \
+     * partition_helpers (partition_helpers_kernels.hpp): (start, end) pairs per part.              \
+     * sort_by_range_start is STABLE: pairs with equal starts keep their input order (and their    \
+     * part ids travel with them); check_consecutive_ranges is true for 0 or 1 pair. */             \
     int gkoc_partition_helpers_sort_by_range_start_##GN(gkoc_stream_t s, int64_t num_parts,         \
                                                         G* range_start_ends, int32_t* part_ids);    \
     int gkoc_partition_helpers_check_consecutive_ranges_##GN(gkoc_stream_t s, int64_t num_parts,    \

@@ -1,5 +1,5 @@
 """Device buffers for the tests that call gkoc_* entry points directly (tests/test_idr_gpu.py,
-test_cb_gmres_gpu.py, test_dense_gpu.py, test_csr_struct_gpu.py, test_csr_diag_gpu.py): any numpy dtype
+test_cb_gmres_gpu.py, test_dense_gpu.py, test_csr_struct_gpu.py, test_csr_diag_gpu.py, test_dist_partition_gpu.py, test_dist_index_gpu.py): any numpy dtype
 travels as bytes, strided operands are cut out of a padded array whose padding keeps a canary, flat outputs
 are followed by one."""
 import ctypes as C
@@ -85,3 +85,37 @@ def grid_cap_rows():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     text = open(os.path.join(root, "ginkgo_amd", "csrc", "common.hpp")).read()
     return 256 * 4 * int(re.search(r"constexpr\s+int\s+max_stream_blocks\s*=\s*(\d+)\s*;", text).group(1))
+
+
+SENTINEL = -99
+
+
+def head_of(out, n, k, fill=SENTINEL):
+    """the first k entries of an out_buf of n entries, after checking that entries k .. n still hold `fill`
+    bit for bit and that the canaries behind them are intact"""
+    got = out.get()
+    assert tail_ok(got, n)
+    assert same_bits(got[k:n], np.full(n - k, fill, got.dtype)), "written beyond what the operation defines"
+    return got[:k]
+
+
+class PartitionStruct(C.Structure):
+    """gkoc_partition of include/gko_cdna4.h: a host struct of device pointers"""
+    _fields_ = [("num_ranges", C.c_int64), ("num_parts", C.c_int32), ("range_bounds", C.c_void_p),
+                ("part_ids", C.c_void_p), ("range_starting_indices", C.c_void_p), ("part_sizes", C.c_void_p)]
+
+
+class DevPartition:
+    """a partition (bounds, pids, starts, sizes, num_parts on the host) on the device with local index type
+    lt and global index type gt; `ref` is what a const gkoc_partition* parameter takes"""
+
+    def __init__(self, gexec, lt, gt, part):
+        assert part.bounds.max(initial=0) <= np.iinfo(gt).max and part.sizes.max(initial=0) <= np.iinfo(lt).max
+        self.host = [part.bounds.astype(gt), part.pids.astype(np.int32), part.starts.astype(lt),
+                     part.sizes.astype(lt)]
+        self.dev = [Dev(gexec, h) for h in self.host]
+        self.struct = PartitionStruct(len(part.pids), part.num_parts, *[d.t.data_ptr() for d in self.dev])
+        self.ref = C.byref(self.struct)
+
+    def unchanged(self):
+        return all(same_bits(d.get(), h) for d, h in zip(self.dev, self.host))
