@@ -8,7 +8,7 @@
 // to complex vectors works on their real views, but residual checks, updates and reductions of the
 // complex vectors themselves go through these kernels.  Plain 2-D indexed kernels (strided views,
 // per-column scalars), reductions as a fixed two-level tree per column; complex products as
-// (ac - bd, ad + bc) with separate multiplies and adds, quotients through the conjugate.
+// (ac - bd, ad + bc) with separate multiplies and adds, quotients by Smith's scaled method.
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
@@ -34,11 +34,17 @@ template <typename R>
 __device__ __forceinline__ cx<R> operator*(cx<R> a, R b) { return {a.re * b, a.im * b}; }
 template <typename R>
 __device__ __forceinline__ cx<R> operator/(cx<R> a, R b) { return {a.re / b, a.im / b}; }
+// Smith's scaled quotient, operation for operation the one of complex_type.hpp: |b|^2 is never formed, so a
+// divisor of modulus 1e-25 (or 1e25) in float divides like any other
 template <typename R>
 __device__ __forceinline__ cx<R> operator/(cx<R> a, cx<R> b)
 {
-    const R d = b.re * b.re + b.im * b.im;
-    return {(a.re * b.re + a.im * b.im) / d, (a.im * b.re - a.re * b.im) / d};
+    if ((b.re < R(0) ? -b.re : b.re) >= (b.im < R(0) ? -b.im : b.im)) {
+        const R r = b.im / b.re, den = b.re + b.im * r;
+        return {(a.re + a.im * r) / den, (a.im - a.re * r) / den};
+    }
+    const R r = b.re / b.im, den = b.re * r + b.im;
+    return {(a.re * r + a.im) / den, (a.im * r - a.re) / den};
 }
 template <typename R>
 __device__ __forceinline__ cx<R> conj_of(cx<R> a) { return {a.re, -a.im}; }
@@ -331,8 +337,9 @@ __global__ __launch_bounds__(256) void cx_invert_kernel(int64_t n, const cx<R>* 
 {
     GKOC_FOR2(i, n)
     {
-        const cx<R> v = is_zero(d[i]) ? cx<R>{R(1), R(0)} : d[i];
-        inv[i] = cx<R>{R(1), R(0)} / v;
+        // a zero entry inverts as one: (1, +0), written as such
+        const cx<R> one{R(1), R(0)};
+        inv[i] = is_zero(d[i]) ? one : one / d[i];
     }
 }
 

@@ -1634,9 +1634,13 @@ GKOC_DECL_RWAS(double, f64, int32_t, i32)
 GKOC_DECL_RWAS(double, f64, int64_t, i64)
 GKOC_DECL_RWAS(float, f32, int32_t, i32)
 GKOC_DECL_RWAS(float, f32, int64_t, i64)
-/* scalar Jacobi and Diagonal products on complex values: jacobi::{invert_diagonal (a zero entry
- * inverts as one), simple_scalar_apply, scalar_apply}, diagonal::{apply_to_csr, right_apply_to_csr}
- * (core/preconditioner/jacobi_kernels.hpp:42-81, core/matrix/diagonal_kernels.hpp:33-43) */
+/* scalar Jacobi and Diagonal products on complex values: jacobi::{invert_diagonal, simple_scalar_apply,
+ * scalar_apply}, diagonal::{apply_to_csr, right_apply_to_csr}
+ * (core/preconditioner/jacobi_kernels.hpp:42-81, core/matrix/diagonal_kernels.hpp:33-43).
+ * invert_diagonal: inv[i] = 1 / diag[i]; an entry whose two parts are both zero (either sign) is
+ * replaced by one first, so it inverts as (1, +0); a NaN is not zero.  The quotients of this group, of
+ * gkoc_cdense_inv_scale_* with a complex scalar and of gkoc_ccsr_scale_by_diagonal_* mode 1 are Smith's
+ * scaled quotient (csrc/complex_type.hpp): |diag|^2 is never formed */
 #define GKOC_DECL_CJAC(P, TN)                                                                          \
     int gkoc_cjacobi_invert_diagonal_##TN(gkoc_stream_t s, int64_t n, const P* diag, P* inv);          \
     /* alpha == NULL: x = diag b (row-wise); else x = beta x + alpha b diag */                         \
@@ -1655,7 +1659,9 @@ GKOC_DECL_CCSR_SCALE(gkoc_c64, c64, int32_t, i32)
 GKOC_DECL_CCSR_SCALE(gkoc_c64, c64, int64_t, i64)
 /* Coo with complex values (coo::spmv2 / advanced_spmv2; spmv / advanced_spmv clear or scale c
  * first): c += [alpha] A b entry by entry with atomic adds - the one place where the summation
- * order is not fixed */
+ * order is not fixed.  c is read and added to, never cleared: what it held on entry is part of the
+ * result, entries of rows without a stored entry keep their bits; several entries with the same
+ * (row, column) all count */
 #define GKOC_DECL_CCOO(P, TN, I, IN)                                                                   \
     int gkoc_ccoo_spmv2_##TN##_##IN(gkoc_stream_t s, int64_t nnz, int64_t nrhs, const I* rows,         \
                                     const I* cols, const P* vals, const P* alpha, const P* b,          \
@@ -1869,7 +1875,9 @@ int gkoc_fill_array_small(gkoc_stream_t s, void* data, int64_t n, int elem_bytes
     int gkoc_sellp_fill_in_dense_##TN##_##IN(gkoc_stream_t s, int64_t n_rows, int64_t slice_size,     \
                                              const uint64_t* slice_sets, const I* cols,               \
                                              const T* vals, T* out, int64_t ld);                      \
-    /* diag[r] = first stored (r, r) for r < n; rows without one keep what diag held */               \
+    /* diag[r] = first stored (r, r) for r < n; rows without one keep what diag held.  A slot counts  \
+     * by its column alone, whatever its value: an explicit zero stored at (r, r) is the diagonal,    \
+     * padding (column -1) never is, in whatever row it sits */                                        \
     int gkoc_ell_extract_diagonal_##TN##_##IN(gkoc_stream_t s, int64_t n, int64_t ell_k,              \
                                               int64_t stride, const I* cols, const T* vals,           \
                                               T* diag);                                               \

@@ -1,5 +1,6 @@
 """Device buffers for the tests that call gkoc_* entry points directly (tests/test_idr_gpu.py,
-test_cb_gmres_gpu.py, test_dense_gpu.py, test_csr_struct_gpu.py, test_csr_diag_gpu.py, test_dist_partition_gpu.py, test_dist_index_gpu.py): any numpy dtype
+test_cb_gmres_gpu.py, test_dense_gpu.py, test_csr_struct_gpu.py, test_csr_diag_gpu.py, test_dist_partition_gpu.py, test_dist_index_gpu.py,
+test_cdense_gpu.py, test_format_helpers_gpu.py, test_array_components_gpu.py): any numpy dtype
 travels as bytes, strided operands are cut out of a padded array whose padding keeps a canary, flat outputs
 are followed by one."""
 import ctypes as C
@@ -97,6 +98,40 @@ def head_of(out, n, k, fill=SENTINEL):
     assert tail_ok(got, n)
     assert same_bits(got[k:n], np.full(n - k, fill, got.dtype)), "written beyond what the operation defines"
     return got[:k]
+
+
+class _C128(C.Structure):
+    _fields_ = [("re", C.c_double), ("im", C.c_double)]
+
+
+class _C64(C.Structure):
+    _fields_ = [("re", C.c_float), ("im", C.c_float)]
+
+
+def by_value(v):
+    """a numpy scalar as the ctypes object that passes it BY VALUE with its bits intact (NaN payloads
+    included): float32 / float64 / int32 / int64 / gkoc_c64 / gkoc_c128"""
+    a = np.ascontiguousarray(v).reshape(1)
+    ct = {"float64": C.c_double, "float32": C.c_float, "int32": C.c_int32, "int64": C.c_int64,
+          "complex128": _C128, "complex64": _C64}[a.dtype.name]
+    return ct.from_buffer_copy(a.tobytes())
+
+
+def canaries_ok(a, cols):
+    """the padding columns of a `padded` array still hold the canary"""
+    return bool(np.all(a[:, cols:] == a.dtype.type(CANARY)))
+
+
+def raises_invalid(name, *args):
+    """the call is refused with GKOC_E_INVALID (-1) before any launch"""
+    import re
+    from ginkgo_amd._lib import GkoError
+    try:
+        call(name, *args)
+    except GkoError as e:
+        m = re.search(r"failed with status (-?\d+):", str(e))
+        return m is not None and int(m.group(1)) == -1
+    return False
 
 
 class PartitionStruct(C.Structure):

@@ -15,13 +15,18 @@ from test_abi import ROOT, declared_symbols
 LEDGER = os.path.join(ROOT, "tests", "abi_not_reached.txt")
 _SUFFIX = re.compile(r"(_(f64|f32|c128|c64|i32|i64|u64))+$")
 # families this repository tests directly (tests/test_idr_gpu.py, test_cb_gmres_gpu.py, test_dense_gpu.py,
-# test_csr_struct_gpu.py, test_csr_diag_gpu.py, test_dist_partition_gpu.py, test_dist_index_gpu.py)
+# test_csr_struct_gpu.py, test_csr_diag_gpu.py, test_dist_partition_gpu.py, test_dist_index_gpu.py,
+# test_cdense_gpu.py, test_format_helpers_gpu.py, test_array_components_gpu.py)
 MUST_BE_REACHED = ("idr", "cb_gmres", "dense_simple_apply", "dense_apply", "dense_convert", "compute_norm1",
                    "compute_mean", "reduce_add_array", "prefix_sum", "csr_spgemm_reuse", "csr_spgeam_numeric",
                    "in_index_set", "from_index_set", "csr_build_lookup", "csr_row_wise_absolute_sum",
                    "ccsr_row_scan", "gkoc_diagonal_", "gkoc_sparsity_csr_", "gkoc_partition_", "gkoc_index_map_",
                    "gkoc_dist_separate_", "gkoc_dist_vector_build_local", "gkoc_assembly_count_non_owning",
-                   "gkoc_assembly_fill_send_buffers")
+                   "gkoc_assembly_fill_send_buffers", "gkoc_cdense_", "gkoc_ccsr_scale_by_diagonal", "gkoc_ccoo_spmv2",
+                   "gkoc_cjacobi_", "gkoc_ell_copy", "gkoc_ell_extract_diagonal", "gkoc_sellp_extract_diagonal",
+                   "gkoc_dense_absolute", "gkoc_dense_fill_in_matrix_data", "gkoc_dense_add_scaled_identity_real",
+                   "gkoc_jacobi_initialize_precisions", "gkoc_fill_array", "gkoc_convert_precision", "gkoc_conj_array",
+                   "gkoc_narrow_i64_to_i32", "gkoc_x_residual_norm_then_cg_step_1")
 
 
 def stem(name):
