@@ -1,4 +1,6 @@
-"""Jacobi preconditioner (scalar and block) - mirror of
+"""Jacobi (scalar and block) and Sor / Gauss-Seidel preconditioners.
+
+Jacobi - mirror of
 include/ginkgo/core/preconditioner/jacobi.hpp and
 core/preconditioner/jacobi.cpp:150-165 (apply) / :328-404 (generate).
 
@@ -10,6 +12,12 @@ invert_diagonal + simple_scalar_apply).  Adaptive precision
 (`with_storage_optimization`) is supported for fp64 and fp32 values: block-wise and
 autodetected precisions for any max_block_size <= 32, one fixed reduced
 precision for all blocks for max_block_size in {2, 4, 8, 16}.
+
+Sor / GaussSeidel - mirror of include/ginkgo/core/preconditioner/{sor,gauss_seidel}.hpp:
+`Sor.build().with_relaxation_factor(1.2).with_symmetric(False).on(exec).generate(A)` builds the
+weighted factor(s) on the device (factorization::initialize_row_ptrs_l_u,
+sor::initialize_weighted_l / _l_u) and applies them with the level-scheduled triangular solvers of
+triangular.py: z = L^-1 r, or z = U^-1 L^-1 r for the symmetric form (SSOR).
 """
 import ctypes as C
 
@@ -18,8 +26,9 @@ import torch
 
 from ._lib import IT, VT, JacobiScheme, NotSupported, call
 from .base import LinOp
-from .executor import MEM_INDICES
-from .matrix import Csr, Fbcsr
+from .executor import MEM_INDICES, MEM_VALUES
+from .matrix import Csr, Dense, Fbcsr
+from .triangular import LowerTrs, UpperTrs
 
 
 def compute_storage_scheme(max_block_size, warp_size=64):
@@ -302,3 +311,122 @@ class Jacobi(LinOp):
              C.c_uint32(self.max_block_size), self.scheme, self.block_pointers,
              self.blocks, alpha.values, b.values, b.ld, beta.values, x.values,
              x.ld, b.size[1])
+
+
+class SorFactory:
+    def __init__(self, cls=None):
+        self.cls = cls or Sor
+        self.relaxation_factor = 1.2
+        self.symmetric = False
+        self.skip_sorting = False
+        self.exec = None
+
+    def with_relaxation_factor(self, v):
+        self.relaxation_factor = float(v)
+        return self
+
+    def with_symmetric(self, v):
+        self.symmetric = bool(v)
+        return self
+
+    def with_skip_sorting(self, v):
+        self.skip_sorting = bool(v)
+        return self
+
+    def on(self, exec_):
+        self.exec = exec_
+        return self
+
+    def generate(self, system_matrix):
+        if isinstance(system_matrix, Fbcsr):
+            # any other matrix type goes through convert_to(Csr), as for Jacobi
+            csr = system_matrix.convert_to_csr()
+            prec = self.cls(self, csr)
+            csr.exec.synchronize()      # the converted copy is released on return
+            return prec
+        return self.cls(self, system_matrix)
+
+
+class _GaussSeidelFactory(SorFactory):
+    def __init__(self):
+        super().__init__(GaussSeidel)
+        self.relaxation_factor = 1.0
+
+    def with_relaxation_factor(self, v):
+        raise NotSupported("GaussSeidel has the relaxation factor 1; use Sor for another one")
+
+
+class Sor(LinOp):
+    """M = L_w = D/w + L_A, or with_symmetric(True) the SSOR matrix
+    L_w U_w = (D/w + L_A) w/(2-w) D^-1 (D/w + U_A); `l` / `u` are the generated Csr factors
+    (`u` is None when not symmetric), apply is one or two triangular solves."""
+
+    @staticmethod
+    def build():
+        return SorFactory()
+
+    def __init__(self, factory, a):
+        if not isinstance(a, Csr):
+            raise NotSupported(f"{type(self).__name__}.generate needs a Csr system matrix")
+        if a.size[0] != a.size[1]:
+            from ._lib import DimensionMismatch
+            raise DimensionMismatch(f"{type(self).__name__} needs a square matrix")
+        if a.dtype not in VT:
+            raise NotSupported(f"{type(self).__name__}: real value types only")
+        super().__init__(factory.exec or a.exec, a.size)
+        ex = self.exec
+        self.relaxation_factor = factory.relaxation_factor
+        self.symmetric = factory.symmetric
+        self.dtype = a.dtype
+        it = IT[a.col_idxs.dtype]
+        suf = f"{VT[a.dtype]}_{it}"
+        n = a.size[0]
+        if not factory.skip_sorting and not a.is_sorted_by_column_index():
+            a = Csr(ex, a.size, a.values.clone(), a.col_idxs.clone(),
+                    a.row_ptrs, a.strategy).sort_by_column_index()
+        idx = a.row_ptrs.dtype
+        l_rp = ex.alloc((n + 1,), idx, MEM_INDICES)
+        u_rp = ex.alloc((n + 1,), idx, MEM_INDICES) if self.symmetric else None
+        call("gkoc_factorization_initialize_row_ptrs_l_u_" + it, ex.stream, n, a.row_ptrs, a.col_idxs,
+             l_rp, u_rp)
+        l_nnz = int(l_rp[-1].item())
+        l_ci, l_v = ex.alloc((l_nnz,), idx, MEM_INDICES), ex.alloc((l_nnz,), a.dtype, MEM_VALUES)
+        weight = C.c_double(self.relaxation_factor)
+        if self.symmetric:
+            u_nnz = int(u_rp[-1].item())
+            u_ci, u_v = ex.alloc((u_nnz,), idx, MEM_INDICES), ex.alloc((u_nnz,), a.dtype, MEM_VALUES)
+            call("gkoc_sor_initialize_weighted_l_u_" + suf, ex.stream, n, a.row_ptrs, a.col_idxs,
+                 a.values, weight, l_rp, l_ci, l_v, u_rp, u_ci, u_v)
+            self.u = Csr(ex, a.size, u_v, u_ci, u_rp)
+            self._u_solver = UpperTrs.build().on(ex).generate(self.u)
+        else:
+            call("gkoc_sor_initialize_weighted_l_" + suf, ex.stream, n, a.row_ptrs, a.col_idxs, a.values,
+                 weight, l_rp, l_ci, l_v)
+            self.u = self._u_solver = None
+        self.l = Csr(ex, a.size, l_v, l_ci, l_rp)
+        self._l_solver = LowerTrs.build().on(ex).generate(self.l)
+        # the vector between the two solves: allocated here, not inside a captured iteration
+        self._tmp = Dense.create(ex, (n, 1), a.dtype) if self.symmetric else None
+
+    def apply_impl(self, b, x):
+        if not self.symmetric:
+            self._l_solver.apply(b, x)
+            return
+        if self._tmp.size != b.size or self._tmp.dtype != b.dtype:
+            self._tmp = Dense.create(self.exec, b.size, b.dtype)
+        self._l_solver.apply(b, self._tmp)
+        self._u_solver.apply(self._tmp, x)
+
+    def apply_advanced_impl(self, alpha, b, beta, x):
+        xc = x.clone()
+        self.apply_impl(b, xc)
+        x.scale(beta)
+        x.add_scaled(alpha, xc)
+
+
+class GaussSeidel(Sor):
+    """Sor with the relaxation factor 1 (preconditioner::GaussSeidel)."""
+
+    @staticmethod
+    def build():
+        return _GaussSeidelFactory()

@@ -2498,6 +2498,64 @@ int gkoc_comm_topology_get(gkoc_comm_t comm, gkoc_comm_topology* out);
  * Process-wide.  Raised to 2 by any communicator that comes up with a peer on another device. */
 int gkoc_gate_fence_policy(int set, int* now);
 
+/* ------------------------------------- triangular solves (solver::LowerTrs / UpperTrs), Sor set-up
+ * lower_trs / upper_trs::{generate, solve} (core/solver/{lower,upper}_trs_kernels.hpp;
+ * reference/solver/{lower,upper}_trs_kernels.cpp).  A solve is the reference's loop, bit for bit (f64 and
+ * f32): for every right-hand side j and row = 0 .. n-1 (upper: n-1 .. 0), t = b(row, j); for k ascending
+ * over the row's entries in storage order, col < row (upper: col > row): t = t - vals[k] * x(col, j) (a
+ * separate multiply and subtract), col == row: diag = vals[k]; x(row, j) = unit_diag ? t : t / diag.
+ * Columns need not be sorted; entries on the other side of the diagonal are ignored (by generate as
+ * well, so the full matrix may be passed); a missing diagonal counts as 1; unit_diag ignores a stored one.
+ * generate (once per sparsity pattern; synchronises the stream): level[row] = 1 + max level of the rows it
+ * depends on (0 without any), rows grouped by level, ascending inside a level, kept on the device; the
+ * levels are computed on the host.  solve enqueues kernels on the stream and nothing else (no allocation,
+ * no synchronisation, no copy - it may be captured into a graph): one launch per level with more than W
+ * rows, one single-workgroup launch per maximal run of levels with at most W rows each.  No kernel waits
+ * for another workgroup; a dependency across workgroups is a kernel boundary.  info: host outputs (any
+ * may be NULL); levels: level_ptrs_host[n_levels + 1], level_rows_host[n_rows].
+ * GKOC_E_INVALID before any device work: negative sizes, null pointers where a size is non-zero, ldb / ldx
+ * < nrhs, a structure of the other triangle or of another n_rows, weight outside (0, 2).
+ * factorization::initialize_row_ptrs_l_u (reference/factorization/factorization_kernels.cpp): row
+ * pointers of L (strictly-lower entries + 1 per row) and U (strictly-upper + 1; u_row_ptrs may be NULL).
+ * sor::initialize_weighted_l / _l_u (reference/preconditioner/sor_kernels.cpp), w = T(weight), all
+ * arithmetic in T: L = A's strictly-lower entries in storage order, then the diagonal a_ii / w, last;
+ * U = the diagonal 1 / (2 - w), first, then (w * a_ij) / ((2 - w) * a_ii) for A's strictly-upper entries
+ * in storage order; a missing a_ii counts as 1.  L U = (D/w + L_A) w/(2-w) D^-1 (D/w + U_A), the SSOR matrix. */
+typedef struct gkoc_trs_struct_s* gkoc_trs_struct_t;
+int gkoc_trs_struct_destroy(gkoc_trs_struct_t t);
+int gkoc_trs_struct_info(gkoc_trs_struct_t t, int64_t* n_rows, int* is_upper, int64_t* n_levels,
+                         int64_t* n_launches, int64_t* wide_threshold);
+int gkoc_trs_struct_levels(gkoc_trs_struct_t t, int64_t* level_ptrs_host, int64_t* level_rows_host);
+#define GKOC_DECL_TRS_I(I, IN)                                                                               \
+    int gkoc_lower_trs_generate_##IN(gkoc_stream_t s, int64_t n_rows, const I* row_ptrs, const I* col_idxs,  \
+                                     gkoc_trs_struct_t* out);                                                \
+    int gkoc_upper_trs_generate_##IN(gkoc_stream_t s, int64_t n_rows, const I* row_ptrs, const I* col_idxs,  \
+                                     gkoc_trs_struct_t* out);                                                \
+    int gkoc_factorization_initialize_row_ptrs_l_u_##IN(gkoc_stream_t s, int64_t n_rows, const I* row_ptrs,  \
+                                                        const I* col_idxs, I* l_row_ptrs, I* u_row_ptrs);
+GKOC_DECL_TRS_I(int32_t, i32)
+GKOC_DECL_TRS_I(int64_t, i64)
+#define GKOC_DECL_TRS(T, TN, I, IN)                                                                          \
+    int gkoc_lower_trs_solve_##TN##_##IN(gkoc_stream_t s, gkoc_trs_struct_t t, int unit_diag,                \
+                                         int64_t n_rows, int64_t nrhs, const I* row_ptrs,                    \
+                                         const I* col_idxs, const T* vals, const T* b, int64_t ldb, T* x,    \
+                                         int64_t ldx);                                                       \
+    int gkoc_upper_trs_solve_##TN##_##IN(gkoc_stream_t s, gkoc_trs_struct_t t, int unit_diag,                \
+                                         int64_t n_rows, int64_t nrhs, const I* row_ptrs,                    \
+                                         const I* col_idxs, const T* vals, const T* b, int64_t ldb, T* x,    \
+                                         int64_t ldx);                                                       \
+    int gkoc_sor_initialize_weighted_l_##TN##_##IN(gkoc_stream_t s, int64_t n_rows, const I* rp,             \
+                                                   const I* ci, const T* v, double weight, const I* l_rp,    \
+                                                   I* l_ci, T* l_v);                                         \
+    int gkoc_sor_initialize_weighted_l_u_##TN##_##IN(gkoc_stream_t s, int64_t n_rows, const I* rp,           \
+                                                     const I* ci, const T* v, double weight,                 \
+                                                     const I* l_rp, I* l_ci, T* l_v, const I* u_rp,          \
+                                                     I* u_ci, T* u_v);
+GKOC_DECL_TRS(double, f64, int32_t, i32)
+GKOC_DECL_TRS(double, f64, int64_t, i64)
+GKOC_DECL_TRS(float, f32, int32_t, i32)
+GKOC_DECL_TRS(float, f32, int64_t, i64)
+
 #ifdef __cplusplus
 }
 #endif
