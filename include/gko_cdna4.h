@@ -203,7 +203,17 @@ int gkoc_arena_probe(const void* x, size_t x_bytes, void* y, int read_kb_per_wav
                                       pointers, remembered per (row_ptrs, n_rows)) and multiplied by many workgroups
                                       each (csrc/csr_long_rows.hpp) instead of by one wave; 0: one wave, as before.
                                       The chunk sums go to a buffer per (matrix, stream): products with the SAME
-                                      matrix may run at the same time on several streams */
+                                      matrix may run at the same time on several streams.
+                                      Stream capture: a product captured into a hipGraph takes the many-workgroup
+                                      kernels only if the capturing stream has multiplied the matrix before (its
+                                      flags and the stream's chunk buffer exist then; inside a capture nothing is
+                                      scanned or allocated, one wave sums a long row).  Such a graph holds the
+                                      addresses of the flags and of the chunk buffer, which live as long as the
+                                      matrix is remembered: LIFETIME RULE - replay the graph only while the matrix'
+                                      row_ptrs allocation is alive (gkoc_free forgets the matrix and frees both) and
+                                      while fewer than 128 other matrices have had their first product since THIS
+                                      matrix had its own (128 matrices are remembered; the one met first makes room,
+                                      however often it has been multiplied since).  Capture again after either. */
 #define GKOC_TUNE_CSR_SEGS_PER_WAVE 13 /* csr::spmv, one right-hand side: 64-row segments a wave walks.  0 (default): two
                                       from 4 M rows on, one below; 1, 2: that many.  Only 1 and 2 are honoured, any
                                       other value is the rule (round 6 tried four and eight on rows of a dozen
