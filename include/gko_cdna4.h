@@ -706,7 +706,14 @@ GKOC_DECL_CG(gkoc_c64, c64)
  * (core/solver/gmres.cpp:352-363, :540-545); final_iter_nums is a size_type
  * (uint64) array; residual_norm is 1 x nrhs.  multi_dot: hessenberg_col(d,k) =
  * <basis_d(:,k), next_krylov(:,k)> for d < num_dots, deterministic tree
- * (tolerance 1e-13); everything else is bit-identical to the reference. */
+ * (tolerance 1e-13); everything else is bit-identical to the reference.
+ * multi_dot writes rows 0 .. num_dots - 1 of hessenberg_col and leaves every other row, row num_dots
+ * (the norm's place) included, alone; rows = 0 gives +0.  hessenberg_qr skips a column whose
+ * stop_status has stopped: its rotations, its Hessenberg entries, its residual norms and its
+ * final_iter_nums keep their bits.  multi_axpy and solve_krylov skip a finalized column:
+ * before_preconditioner and y keep their bits there; solve_krylov writes rows 0 ..
+ * final_iter_nums[k] - 1 of y only.  multi_axpy then finalizes the stopped columns.
+ * Complex value types: products are (ac - bd, ad + bc), quotients Smith's, the modulus hypot. */
 size_t gkoc_gmres_multi_dot_workspace_bytes(int64_t rows, int64_t nrhs,
                                             int64_t num_dots, size_t value_size);
 /* (R = remove_complex<T>: residual_norm is real also for complex value types) */
@@ -1398,10 +1405,14 @@ int gkoc_partition_has_ordered_parts(gkoc_stream_t s, int64_t num_ranges, const 
 size_t gkoc_x_workspace_bytes(int64_t n, size_t value_size);
 /* gkoc_x_gmres_multi_sub_scaled: next_krylov -= sum_{d<num} h(d,:) * basis_d, the
  * num dense::sub_scaled calls of the classical Gram-Schmidt update
- * (gmres.cpp:222-236) in one pass, term by term in d order => bit-identical. */
+ * (gmres.cpp:222-236) in one pass, term by term in d order => bit-identical.
+ * As dense::sub_scaled does, a scalar that is zero skips its term only when nrhs == 1; with more
+ * columns 0 * basis_d is subtracted like any other term (a NaN or infinity of basis_d reaches
+ * next_krylov, and -0.0 - (-0.0) turns a -0.0 of next_krylov into +0.0). */
 /* gkoc_x_gmres_mgs_step: one modified Gram-Schmidt step fused with the next dot
  * (gmres.cpp:176-190): next_krylov -= h_cur * basis_cur (bit-identical to
- * dense::sub_scaled), h_next = <basis_next, next_krylov> (tree sum). */
+ * dense::sub_scaled; h_cur == 0 leaves next_krylov alone), h_next = <basis_next, next_krylov>
+ * (conjugate on basis_next; tree sum of the updated next_krylov; rows = 0 gives +0). */
 /* Optional last argument of the fused PipeCg step kernels (NULL: neither).
  * wait_word / wait_number: every workgroup waits until *wait_word has reached wait_number before
  * it reads the scalars - the word that gkoc_gate_open sets on the exchange's stream behind the
