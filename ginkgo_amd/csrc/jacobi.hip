@@ -1,9 +1,10 @@
-// Block-Jacobi preconditioner on gfx950: block detection, inversion, apply.
+// Block-Jacobi preconditioner on gfx950: block detection, inversion, apply, transposes.
 //
-// Replaces gko::kernels::hip::jacobi::{find_blocks, generate, simple_apply,
-// apply} (decl core/preconditioner/jacobi_kernels.hpp:18-86; semantics
+// Replaces gko::kernels::hip::jacobi::{find_blocks, generate, simple_apply, apply,
+// transpose_jacobi, conj_transpose_jacobi, initialize_precisions}
+// (decl core/preconditioner/jacobi_kernels.hpp:18-103; semantics
 // reference/preconditioner/jacobi_kernels.cpp:47-118 (find_blocks), :125-411
-// (extract / Gauss-Jordan / generate), :419-531 (apply); stock GPU versions
+// (extract / Gauss-Jordan / generate), :419-531 (apply), :528-627 (transposes); stock GPU versions
 // common/cuda_hip/preconditioner/jacobi_kernels.cpp:58-270,
 // jacobi_generate_kernels.instantiate.cpp, jacobi_simple_apply_kernels*.cpp).
 //
@@ -18,14 +19,49 @@
 //     (bs + 2) * n values for uniform blocks of size bs.  No MFMA: at nrhs = 1
 //     the arithmetic intensity is 0.2 flop/B.
 //  => results are bit-identical to the reference (same k order, multiply and
-//     add kept separate).
-//  * find_blocks is fully parallel (the stock GPU backend runs two <<<1,1>>>
-//    kernels over all rows): natural blocks and the greedy agglomeration are
-//    both "follow next[] from row 0" chains, marked by pointer doubling in
-//    ceil(log2 n) passes.  block_pointers are integer-exact.
-//  * generate: one SUB-lane sub-wavefront per block (SUB = max_block_size
-//    rounded up to a power of two), block staged in LDS, lane = row; pivoting
-//    and operation order as in the reference => bit-identical inverse blocks.
+//     add kept separate; the matrix-core kernel for many columns excepted).
+//
+// The file, in the order a reader needs it, and which entry point lands where:
+//  1. Block detection.  gkoc_jacobi_find_blocks_*: fully parallel (the stock GPU backend runs
+//     two <<<1,1>>> kernels over all rows): natural blocks and the greedy agglomeration are
+//     both "follow next[] from row 0" chains, marked by pointer doubling in ceil(log2 n)
+//     passes.  block_pointers are integer-exact.
+//  2. Storage scheme, storage types and precision rules: the layout predicates, the reduced
+//     types stored<PREC> with load_stored / store_stored, the rules per value type
+//     (storage_kind, reduction_rules), and the two helpers that turn a runtime block_offset /
+//     precision into a template argument (with_block_offset, with_precision).
+//  3. Generate: one SUB-lane sub-wavefront per block (SUB = max_block_size rounded up to a
+//     power of two), block staged in LDS, lane = row; pivoting and operation order as in the
+//     reference => bit-identical inverse blocks.
+//       gkoc_jacobi_generate_*                  jacobi_generate_kernel
+//       gkoc_jacobi_generate_adaptive_*         jacobi_generate_adaptive_any_kernel (all four
+//                                               value types)
+//       gkoc_jacobi_convert_storage_f64         jacobi_convert_storage_kernel
+//  4. Apply.
+//     a. the tuned kernels (double / float in full storage, double in reduced storage):
+//       gkoc_jacobi_{simple_apply,apply}_{f64,f32}_*
+//                                               jacobi_apply_fixed_kernel (one column, wide layout),
+//                                               jacobi_apply_fixed_multi_kernel (2 .. 8 columns),
+//                                               jacobi_apply_mfma_kernel (f64, block_offset 8, from 9),
+//                                               jacobi_apply_kernel (any other layout / strides)
+//       gkoc_x_jacobi_simple_apply_dot_*        jacobi_apply_fixed_kernel<DOT>
+//       gkoc_x_cg_step_2_jacobi_apply_*         jacobi_step2_apply_kernel
+//       gkoc_x_pipe_cg_steps_jacobi_*           jacobi_pipe_steps_kernel
+//       gkoc_jacobi_apply_stored_f64_*          jacobi_apply_fixed_kernel<PREC>
+//       gkoc_jacobi_apply_adaptive_f64_*        jacobi_apply_fixed_kernel<PREC = -1>, else
+//                                               jacobi_apply_kernel<STORED>
+//     b. lane = (block, row) for the other value types and storages:
+//       gkoc_jacobi_{simple_apply,apply}_{c64,c128}_*, gkoc_jacobi_apply_adaptive_{f32,c64,c128}_*
+//                                               jacobi_apply_lanes_any_kernel
+//     c. thread per row: what b. does not take, and GKOC_TUNE_JACOBI_LANES = 1
+//                                               jacobi_apply_rows_any_kernel
+//  5. Transposes.
+//       gkoc_jacobi_transpose_{f64,f32}_*       jacobi_transpose_kernel (moves the stored bytes)
+//       gkoc_cjacobi_transpose_*, gkoc_jacobi_transpose_adaptive_{f32,c64,c128}_*
+//                                               jacobi_transpose_adaptive_any_kernel (load / store)
+//  6. The C ABI (include/gko_cdna4.h).
+#include <type_traits>
+
 #include "common.hpp"
 #include "scan.hpp"
 #include "fused.hpp"
@@ -33,7 +69,9 @@
 namespace gkoc {
 namespace {
 
-// ------------------------------------------------------------- find_blocks
+// =========================================================================================
+// 1. Block detection
+// =========================================================================================
 template <typename I>
 __global__ __launch_bounds__(256) void same_pattern_kernel(
     int64_t n, const I* __restrict__ row_ptrs, const I* __restrict__ cols,
@@ -209,13 +247,291 @@ int find_blocks_impl(gkoc_stream_t s, int64_t n, const I* row_ptrs,
     return GKOC_OK;
 }
 
-// ---------------------------------------------------------------- generate
-template <typename T>
-__device__ __forceinline__ T gabs(T v)
+// =========================================================================================
+// 2. Storage scheme, storage types and precision rules
+// =========================================================================================
+// the layout the tuned kernels are written for: block_offset a power of two up to 16, a group is
+// one 64-wide panel (what Jacobi::compute_storage_scheme gives for max_block_size 1, 2, 4, 8, 16)
+inline bool wide_group_layout(const gkoc_jacobi_scheme& sc)
 {
-    return v < T(0) ? -v : v;
+    const int64_t bo = sc.block_offset;
+    return bo >= 1 && bo <= 16 && (bo & (bo - 1)) == 0 && (bo << sc.group_power) == 64;
 }
 
+// lanes per block = the power of two at or above block_offset
+// (Jacobi::compute_storage_scheme, include/ginkgo/core/preconditioner/jacobi.hpp: a group holds
+// max_block_stride / that power blocks; max_block_stride = 64 on this device)
+inline int subwarp_of(const gkoc_jacobi_scheme& sc)
+{
+    int sub = 1;
+    while (sub < sc.block_offset) sub <<= 1;
+    return sub;
+}
+
+inline bool wave_group_layout(const gkoc_jacobi_scheme& sc)
+{
+    return sc.block_offset >= 1 && sc.block_offset <= 32 &&
+           (int64_t(subwarp_of(sc)) << sc.group_power) == 64;
+}
+
+// storage groups per wave of the tuned single-column kernels: two, one where a row of the group's
+// blocks (block_offset values) fills 128 B
+constexpr int groups_per_wave(int64_t block_offset, size_t value_size)
+{
+    return block_offset * int64_t(value_size) >= 128 ? 1 : 2;
+}
+template <typename T>
+constexpr int groups_per_wave(int64_t block_offset)
+{
+    return groups_per_wave(block_offset, sizeof(T));
+}
+
+// calls f(std::integral_constant<int, BO>{}) with the block_offset of a wide layout: the tuned
+// kernels take it as a template argument
+template <typename F>
+void with_block_offset(int64_t block_offset, F&& f)
+{
+    switch (int(block_offset)) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    default: f(std::integral_constant<int, 16>{}); break;
+    }
+}
+
+// Reduced-precision block storage (adaptive block-Jacobi with a fixed
+// storage_optimization; include/ginkgo/core/preconditioner/jacobi.hpp, the types of
+// core/preconditioner/jacobi_utils.hpp:15-37 for ValueType = double).  The stored
+// blocks are widened to double on load and the product runs in double, exactly like
+// reference apply_block with its default_converter.  PREC = the precision_reduction
+// byte (preserving << 4 | nonpreserving):
+//   0x01 float (round to nearest)            0x02 half (via float, round to nearest
+//   0x10 upper 32 bits of the double              even; values below the smallest
+//   0x11 upper 16 bits of the float               normal half become signed zero,
+//   0x20 upper 16 bits of the double              like gko::half, half.hpp:405-433)
+// A group keeps its place (group_offset is in doubles); its reduced entries sit at
+// the same element index of the narrower type, i.e. in the first part of the group.
+template <int PREC>
+struct stored;
+template <>
+struct stored<0x01> {
+    using type = float;
+    __device__ static double load(type v) { return double(v); }
+    __device__ static type store(double v) { return float(v); }
+};
+template <>
+struct stored<0x10> {
+    using type = uint32_t;
+    __device__ static double load(type v) { return __longlong_as_double((long long)(uint64_t(v) << 32)); }
+    __device__ static type store(double v) { return uint32_t(uint64_t(__double_as_longlong(v)) >> 32); }
+};
+template <>
+struct stored<0x20> {
+    using type = uint16_t;
+    __device__ static double load(type v) { return __longlong_as_double((long long)(uint64_t(v) << 48)); }
+    __device__ static type store(double v) { return uint16_t(uint64_t(__double_as_longlong(v)) >> 48); }
+};
+template <>
+struct stored<0x11> {
+    using type = uint16_t;
+    __device__ static double load(type v) { return double(__uint_as_float(uint32_t(v) << 16)); }
+    __device__ static type store(double v) { return uint16_t(__float_as_uint(float(v)) >> 16); }
+};
+template <>
+struct stored<0x02> {
+    using type = uint16_t;
+    __device__ static double load(type h)
+    {
+        // the hardware conversion, except that subnormal halves read as signed zero
+        // (gko::half does not decode them, half.hpp:444-446)
+        _Float16 hv;
+        __builtin_memcpy(&hv, &h, 2);
+        const float f = (h & 0x7c00u) == 0 ? __uint_as_float(uint32_t(h & 0x8000u) << 16) : float(hv);
+        return double(f);
+    }
+    __device__ static type store(double v)
+    {
+        const uint32_t f = __float_as_uint(float(v));
+        const uint16_t sign = uint16_t((f >> 16) & 0x8000u);
+        const uint32_t e = (f >> 23) & 0xffu, m = f & 0x007fffffu;
+        if (e == 0xffu) return uint16_t(sign | 0x7c00u | (m ? 0x03ffu : 0u));
+        if (e <= 112u) return sign;                      // below the normal half range
+        if (e - 112u >= 31u) return uint16_t(sign | 0x7c00u);
+        const uint16_t res = uint16_t(sign | ((e - 112u) << 10) | (m >> 13));
+        const uint32_t tail = m & 0x1fffu;
+        return uint16_t(res + ((tail > 0x1000u || (tail == 0x1000u && (res & 1u))) ? 1u : 0u));
+    }
+};
+
+// runtime-selected storage type (one precision per storage group)
+__device__ __forceinline__ double load_stored(int prec, const double* group, int64_t idx)
+{
+    switch (prec) {
+    case 0x01: return stored<0x01>::load(reinterpret_cast<const float*>(group)[idx]);
+    case 0x02: return stored<0x02>::load(reinterpret_cast<const uint16_t*>(group)[idx]);
+    case 0x10: return stored<0x10>::load(reinterpret_cast<const uint32_t*>(group)[idx]);
+    case 0x11: return stored<0x11>::load(reinterpret_cast<const uint16_t*>(group)[idx]);
+    case 0x20: return stored<0x20>::load(reinterpret_cast<const uint16_t*>(group)[idx]);
+    default: return group[idx];
+    }
+}
+
+__device__ __forceinline__ void store_stored(int prec, double* group, int64_t idx, double v)
+{
+    switch (prec) {
+    case 0x01: reinterpret_cast<float*>(group)[idx] = stored<0x01>::store(v); break;
+    case 0x02: reinterpret_cast<uint16_t*>(group)[idx] = stored<0x02>::store(v); break;
+    case 0x10: reinterpret_cast<uint32_t*>(group)[idx] = stored<0x10>::store(v); break;
+    case 0x11: reinterpret_cast<uint16_t*>(group)[idx] = stored<0x11>::store(v); break;
+    case 0x20: reinterpret_cast<uint16_t*>(group)[idx] = stored<0x20>::store(v); break;
+    default: group[idx] = v; break;
+    }
+}
+
+inline bool known_precision(int prec)
+{
+    return prec == 0x01 || prec == 0x02 || prec == 0x10 || prec == 0x11 || prec == 0x20;
+}
+
+// calls f(std::integral_constant<int, PREC>{}) with a known_precision() as a template argument
+template <typename F>
+void with_precision(int prec, F&& f)
+{
+    switch (prec) {
+    case 0x01: f(std::integral_constant<int, 0x01>{}); break;
+    case 0x02: f(std::integral_constant<int, 0x02>{}); break;
+    case 0x10: f(std::integral_constant<int, 0x10>{}); break;
+    case 0x11: f(std::integral_constant<int, 0x11>{}); break;
+    default: f(std::integral_constant<int, 0x20>{}); break;
+    }
+}
+
+// Adaptive / block-wise storage precision for every value type (the VT instantiations of
+// jacobi::generate / apply / transpose the reference compiles, core/preconditioner/
+// jacobi_kernels.hpp:30-103).  The rules are the reference's, per component type
+// R = remove_complex<T> (core/preconditioner/jacobi_utils.hpp:104-176, include/ginkgo/core/base/
+// math.hpp:365-383, :546-582):
+//   R = double: the five reduced types above (float, half, the upper 32 / 16 bits of the double,
+//               the upper 16 bits of the float);
+//   R = float:  reduce_precision<float> = half and nothing below it, truncate_type<float> = the
+//               upper 16 bits and nothing below them, so the five precision_reduction values fall
+//               on two 16-bit types: (0,1) (0,2) (1,1) -> half, (1,0) (2,0) -> upper 16 bits.
+// A complex value is stored as its two parts in the reduced type.
+template <typename T>
+struct is_cplx {
+    static constexpr bool value = false;
+};
+template <typename R>
+struct is_cplx<gkoc_cplx<R>> {
+    static constexpr bool value = true;
+};
+
+// precision_reduction byte -> storage kind in the codes of stored<> (0 = the value type itself)
+template <typename R>
+__host__ __device__ __forceinline__ int storage_kind(int p);
+template <>
+__host__ __device__ __forceinline__ int storage_kind<double>(int p)
+{
+    return (p == 0x01 || p == 0x02 || p == 0x10 || p == 0x11 || p == 0x20) ? p : 0;
+}
+template <>
+__host__ __device__ __forceinline__ int storage_kind<float>(int p)
+{
+    return (p == 0x01 || p == 0x02 || p == 0x11) ? 0x02 : (p == 0x10 || p == 0x20) ? 0x11 : 0;
+}
+
+template <typename R>
+__device__ __forceinline__ R load_part(int kind, const void* group, int64_t i)
+{
+    if (kind == 0) return reinterpret_cast<const R*>(group)[i];
+    return R(load_stored(kind, reinterpret_cast<const double*>(group), i));
+}
+template <typename R>
+__device__ __forceinline__ void store_part(int kind, void* group, int64_t i, R v)
+{
+    if (kind == 0) {
+        reinterpret_cast<R*>(group)[i] = v;
+    } else {
+        store_stored(kind, reinterpret_cast<double*>(group), i, double(v));
+    }
+}
+template <typename R>
+__device__ __forceinline__ R round_part(int kind, R v)
+{
+    switch (kind) {
+    case 0x01: return R(stored<0x01>::load(stored<0x01>::store(double(v))));
+    case 0x02: return R(stored<0x02>::load(stored<0x02>::store(double(v))));
+    case 0x10: return R(stored<0x10>::load(stored<0x10>::store(double(v))));
+    case 0x11: return R(stored<0x11>::load(stored<0x11>::store(double(v))));
+    case 0x20: return R(stored<0x20>::load(stored<0x20>::store(double(v))));
+    default: return v;
+    }
+}
+
+template <typename R>
+__device__ __forceinline__ R load_value(int kind, const R* group, int64_t idx)
+{
+    return load_part<R>(kind, group, idx);
+}
+template <typename R>
+__device__ __forceinline__ gkoc_cplx<R> load_value(int kind, const gkoc_cplx<R>* group, int64_t idx)
+{
+    return {load_part<R>(kind, group, 2 * idx), load_part<R>(kind, group, 2 * idx + 1)};
+}
+template <typename R>
+__device__ __forceinline__ void store_value(int kind, R* group, int64_t idx, R v)
+{
+    store_part<R>(kind, group, idx, v);
+}
+template <typename R>
+__device__ __forceinline__ void store_value(int kind, gkoc_cplx<R>* group, int64_t idx, gkoc_cplx<R> v)
+{
+    store_part<R>(kind, group, 2 * idx, v.re);
+    store_part<R>(kind, group, 2 * idx + 1, v.im);
+}
+template <typename R>
+__device__ __forceinline__ R round_value(int kind, R v)
+{
+    return round_part<R>(kind, v);
+}
+template <typename R>
+__device__ __forceinline__ gkoc_cplx<R> round_value(int kind, gkoc_cplx<R> v)
+{
+    return {round_part<R>(kind, v.re), round_part<R>(kind, v.im)};
+}
+
+// the unit round-offs get_supported_storage_reductions compares with (jacobi_utils.hpp:118-146;
+// float_traits<>::eps, core/base/extended_float.hpp): p2n0, p1n1, p0n2, p1n0, p0n1, the value
+// type's own, and the storage kinds the two verificators round to
+template <typename R>
+struct reduction_rules;
+template <>
+struct reduction_rules<double> {
+    static constexpr double p2n0 = 1.0 / 16, p1n1 = 1.0 / 128, p0n2 = 1.0 / 2048, p1n0 = 1.0 / 1048576,
+                            p0n1 = 1.0 / 16777216, own = 1.0 / 9007199254740992.0;
+    static constexpr int verify1 = 0x01, verify2 = 0x02;
+};
+template <>
+struct reduction_rules<float> {
+    static constexpr float p2n0 = 1.0f / 128, p1n1 = 1.0f / 2048, p0n2 = 1.0f / 2048, p1n0 = 1.0f / 128,
+                           p0n1 = 1.0f / 2048, own = 1.0f / 16777216;
+    static constexpr int verify1 = 0x02, verify2 = 0x02;
+};
+
+// jacobi::initialize_precisions: the source bytes, repeated
+__global__ void tile_bytes_kernel(int64_t n, const uint8_t* __restrict__ src, int64_t src_n,
+                                  uint8_t* __restrict__ dst)
+{
+    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+    for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
+        dst[i] = src[i % src_n];
+    }
+}
+
+// =========================================================================================
+// 3. Generate: full storage, adaptive storage, conversion of full storage to one reduced type
+// =========================================================================================
 // In-place Gauss-Jordan inversion with column pivoting of the bs x bs block held
 // row-major (leading dimension ld) in LDS, one SUB-lane sub-wavefront per block, lane =
 // row r; operation order of reference invert_block (:175-240) => bit-identical.  perm is
@@ -331,11 +647,235 @@ __global__ __launch_bounds__(64) void jacobi_generate_kernel(
     }
 }
 
-// entry idx of a storage group held in reduced precision (defined with the storage types below)
-__device__ double load_stored_any(int prec, const double* group, int64_t idx);
-__device__ inline float load_stored_any(int, const float* group, int64_t idx) { return group[idx]; }
+template <typename T, typename I>
+int launch_generate(gkoc_stream_t s, const I* row_ptrs, const I* cols,
+                    const T* vals, int64_t num_blocks, uint32_t max_bs,
+                    gkoc_jacobi_scheme scheme, const I* block_ptrs, T* blocks)
+{
+    if (num_blocks <= 0) return GKOC_OK;
+    GKOC_REQUIRE(max_bs >= 1 && max_bs <= 64, GKOC_E_NOT_SUPPORTED,
+                 "max_block_size must be in [1, 64]");
+    int sub = 1;
+    while (sub < int(max_bs)) sub *= 2;
+    const int per_wave = 64 / sub;
+    const size_t lds = size_t(per_wave) * sub * (sub + 1) * sizeof(T);
+    jacobi_generate_kernel<T, I>
+        <<<dim3(unsigned(ceildiv(num_blocks, per_wave))), dim3(64), lds,
+           as_stream(s)>>>(row_ptrs, cols, vals, num_blocks, sub, scheme,
+                           block_ptrs, blocks);
+    GKOC_LAUNCH_OK();
+    return GKOC_OK;
+}
 
-// ------------------------------------------------------------------- apply
+// reference compute_inf_norm (reference/components/matrix_operations.hpp:22-37) applied to
+// the ROW-major block as the reference applies it (element i + j * bs = row j, column i):
+// lane r sums |B(j, r)| over j in order (|z| of a complex entry), the maximum over the lanes is
+// order-free
+template <typename T>
+__device__ __forceinline__ real_t<T> block_norm_any(const T* Bm, int ld, int bs, int r, int sub)
+{
+    using R = real_t<T>;
+    R t = R(0);
+    if (r < bs) {
+        for (int j = 0; j < bs; ++j) t += abs_v(Bm[j * ld + r]);
+    }
+    for (int off = 1; off < sub; off <<= 1) {
+        const R o = __shfl_xor(t, off, 64);
+        t = o > t ? o : t;
+    }
+    return t;
+}
+
+// validate_precision_reduction_feasibility<ReducedType> (reference :280-307) for a storage kind:
+// round the inverse to the reduced type, invert that in the value type, the condition number must
+// be >= 1 and * eps(value type) < 1e-3.  Tm: scratch block in LDS.
+template <typename T>
+__device__ __forceinline__ bool feasible_any(int kind, const T* Bm, T* Tm, int ld, int bs, int r, int g,
+                                             int sub, int max_bs)
+{
+    using R = real_t<T>;
+    if (r < bs) {
+        for (int j = 0; j < bs; ++j) Tm[r * ld + j] = round_value(kind, Bm[r * ld + j]);
+    }
+    wave_lds_sync();
+    R cond = block_norm_any<T>(Tm, ld, bs, r, sub);
+    int perm = r;
+    const bool ok = gauss_jordan_lds<T>(Tm, ld, bs, r, g, sub, max_bs, perm);
+    cond *= block_norm_any<T>(Tm, ld, bs, r, sub);
+    wave_lds_sync();
+    return ok && cond >= R(1) && cond * reduction_rules<R>::own < R(1e-3);
+}
+
+// adaptive generate (reference/preconditioner/jacobi_kernels.cpp:313-411), one wave per storage
+// group (64-wide groups: 64/SUB blocks).
+// precisions[blk] in: requested precision_reduction byte (0xff = autodetect); out: the
+// precision of the group = get_optimal_storage_reduction of the AND of the blocks'
+// descriptors (core/preconditioner/jacobi_utils.hpp:104-176).  conditioning[blk] =
+// norm(block) * norm(inverse).
+// AUTO_NEEDS_COND: what an autodetect request means when the caller passes no conditioning array.
+// true (float, complex<float>, complex<double>): autodetect needs the condition numbers
+// (reference :347: "... && cond"), so the request reads as "keep the value type".  false (double):
+// the array is only an output, the block is autodetected all the same.
+// dynamic LDS: 2 * (64/SUB) * SUB * ld values
+template <typename T, typename I, bool AUTO_NEEDS_COND>
+__global__ __launch_bounds__(64) void jacobi_generate_adaptive_any_kernel(
+    const I* __restrict__ row_ptrs, const I* __restrict__ cols, const T* __restrict__ vals,
+    int64_t num_blocks, int sub, int ld, gkoc_jacobi_scheme scheme, const I* __restrict__ block_ptrs,
+    real_t<T> accuracy, uint8_t* __restrict__ precisions, real_t<T>* __restrict__ conditioning,
+    T* __restrict__ blocks)
+{
+    using R = real_t<T>;
+    using rules = reduction_rules<R>;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    T* lds = reinterpret_cast<T*>(lds_raw);
+    const int lane = threadIdx.x;
+    const int per_wave = 64 / sub;
+    const int g = lane / sub;
+    const int r = lane % sub;
+    T* Bm = lds + int64_t(g) * sub * ld;
+    T* Tm = lds + int64_t(per_wave) * sub * ld + int64_t(g) * sub * ld;
+    const int64_t blk = int64_t(blockIdx.x) * per_wave + g;
+    int64_t start = 0;
+    int bs = 0;
+    if (blk < num_blocks) {
+        start = block_ptrs[blk];
+        bs = int(block_ptrs[blk + 1] - start);
+    }
+    if (r < bs) {
+        for (int j = 0; j < bs; ++j) Bm[r * ld + j] = T(0);
+        const int64_t a = row_ptrs[start + r], e = row_ptrs[start + r + 1];
+        for (int64_t k = a; k < e; ++k) {
+            const int64_t c = int64_t(cols[k]) - start;
+            if (c >= 0 && c < bs) Bm[r * ld + c] = vals[k];
+        }
+    }
+    const int max_bs = wave_max(bs);
+    wave_lds_sync();
+    R cond = block_norm_any<T>(Bm, ld, bs, r, sub);
+    int perm = r;
+    gauss_jordan_lds<T>(Bm, ld, bs, r, g, sub, max_bs, perm);
+    cond *= block_norm_any<T>(Bm, ld, bs, r, sub);
+    int request = blk < num_blocks ? int(precisions[blk]) : -1;
+    if (AUTO_NEEDS_COND && request == 0xff && conditioning == nullptr) request = 0;
+    uint32_t desc = 0xffffffffu;           // blocks past the end do not restrict the group
+    const bool any_auto = __ballot(request == 0xff) != 0;
+    bool v1 = false, v2 = false;
+    if (any_auto) {                        // wave-uniform: the inversions run in lock step
+        v1 = feasible_any<T>(rules::verify1, Bm, Tm, ld, bs, r, g, sub, max_bs);
+        v2 = rules::verify2 == rules::verify1
+                 ? v1
+                 : feasible_any<T>(rules::verify2, Bm, Tm, ld, bs, r, g, sub, max_bs);
+    }
+    if (request == 0xff) {
+        // get_supported_storage_reductions: the verificators are pure, so evaluating them
+        // eagerly and replaying the short-circuit logic gives the same set
+        int verified1 = 2;
+        desc = 0;
+        if (cond * rules::p2n0 < accuracy) desc |= 0x04;
+        if (cond * rules::p1n1 < accuracy) {
+            verified1 = v1 ? 1 : 0;
+            if (v1) desc |= 0x02;
+        }
+        if (cond * rules::p0n2 < accuracy && verified1 != 0 && v2) desc |= 0x01;
+        if (cond * rules::p1n0 < accuracy) desc |= 0x10;
+        if (cond * rules::p0n1 < accuracy) {
+            if (verified1 == 2) verified1 = v1 ? 1 : 0;
+            if (verified1 == 1) desc |= 0x08;
+        }
+    } else if (request >= 0) {
+        desc = request == 0x01 ? 0x08u : request == 0x02 ? 0x01u : request == 0x10 ? 0x10u
+             : request == 0x11 ? 0x02u : request == 0x20 ? 0x04u : 0u;
+    }
+    for (int off = 1; off < 64; off <<= 1) desc &= __shfl_xor(desc, off, 64);
+    const int p = (desc & 0x01) ? 0x02 : (desc & 0x02) ? 0x11 : (desc & 0x04) ? 0x20
+                : (desc & 0x08) ? 0x01 : (desc & 0x10) ? 0x10 : 0x00;
+    if (blk < num_blocks && r == 0) {
+        precisions[blk] = uint8_t(p);
+        if (conditioning) conditioning[blk] = cond;
+    }
+    const int kind = storage_kind<R>(p);
+    const int64_t gsize = int64_t(1) << scheme.group_power;
+    const int64_t stride = scheme.block_offset << scheme.group_power;
+    T* group = blocks + scheme.group_offset * (blk >> scheme.group_power);
+    const int64_t boff = scheme.block_offset * (blk & (gsize - 1));
+    for (int j = 0; j < max_bs; ++j) {
+        const int pj = __shfl(perm, g * sub + j, 64);
+        if (r < bs && j < bs) store_value(kind, group, boff + r + int64_t(pj) * stride, Bm[r * ld + j]);
+    }
+}
+
+template <typename T, typename I, bool AUTO_NEEDS_COND>
+int launch_generate_adaptive_any(gkoc_stream_t s, const I* row_ptrs, const I* cols, const T* vals,
+                                 int64_t num_blocks, uint32_t max_bs, gkoc_jacobi_scheme scheme,
+                                 const I* block_ptrs, real_t<T> accuracy, uint8_t* precisions,
+                                 real_t<T>* conditioning, T* blocks)
+{
+    if (num_blocks <= 0) return GKOC_OK;
+    GKOC_REQUIRE(row_ptrs && cols && vals && block_ptrs && precisions && blocks, GKOC_E_INVALID,
+                 "null pointer");
+    GKOC_REQUIRE(wave_group_layout(scheme) && max_bs >= 1 && max_bs <= uint64_t(scheme.block_offset),
+                 GKOC_E_NOT_SUPPORTED,
+                 "adaptive block-Jacobi needs max_block_size <= 32 and groups that fill a wavefront "
+                 "(max_block_stride 64)");
+    const int sub = subwarp_of(scheme);
+    const int per_wave = 64 / sub;
+    // rows padded by one entry against bank conflicts where two blocks per lane group fit in 64 KB
+    // (all but complex<double> with 32 lanes per block)
+    int ld = sub + 1;
+    if (2 * size_t(per_wave) * sub * ld * sizeof(T) > 65536) ld = sub;
+    const size_t lds = 2 * size_t(per_wave) * sub * ld * sizeof(T);
+    jacobi_generate_adaptive_any_kernel<T, I, AUTO_NEEDS_COND>
+        <<<dim3(unsigned(ceildiv(num_blocks, per_wave))), dim3(64), lds, as_stream(s)>>>(
+            row_ptrs, cols, vals, num_blocks, sub, ld, scheme, block_ptrs, accuracy, precisions,
+            conditioning, blocks);
+    GKOC_LAUNCH_OK();
+    return GKOC_OK;
+}
+
+// in place: the group's double entries become PREC entries at the same element index
+template <int PREC, int BO>
+__global__ __launch_bounds__(64) void jacobi_convert_storage_kernel(int64_t num_groups,
+                                                                    int64_t group_offset,
+                                                                    double* blocks)
+{
+    using S = typename stored<PREC>::type;
+    const int64_t group = blockIdx.x;
+    if (group >= num_groups) return;
+    double* gp = blocks + group_offset * group;
+    double v[BO];
+#pragma unroll
+    for (int c = 0; c < BO; ++c) v[c] = gp[c * 64 + threadIdx.x];
+    // every lane has its loads back before any narrow entry is written
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    S* sp = reinterpret_cast<S*>(gp);
+#pragma unroll
+    for (int c = 0; c < BO; ++c) sp[c * 64 + threadIdx.x] = stored<PREC>::store(v[c]);
+}
+
+int launch_convert_storage(gkoc_stream_t s, int64_t num_blocks, gkoc_jacobi_scheme scheme,
+                           double* blocks, int prec)
+{
+    if (prec == 0 || num_blocks <= 0) return GKOC_OK;
+    GKOC_REQUIRE(known_precision(prec), GKOC_E_NOT_SUPPORTED, "unknown storage precision");
+    GKOC_REQUIRE(blocks, GKOC_E_INVALID, "null pointer");
+    GKOC_REQUIRE(wide_group_layout(scheme), GKOC_E_NOT_SUPPORTED,
+                 "reduced-precision storage needs block_offset in {1,2,4,8,16}, 64-wide groups");
+    const int64_t groups = ceildiv(num_blocks, int64_t(1) << scheme.group_power);
+    with_precision(prec, [&](auto pc) {
+        with_block_offset(scheme.block_offset, [&](auto bc) {
+            jacobi_convert_storage_kernel<decltype(pc)::value, decltype(bc)::value>
+                <<<dim3(unsigned(groups)), dim3(64), 0, as_stream(s)>>>(groups, scheme.group_offset, blocks);
+        });
+    });
+    GKOC_LAUNCH_OK();
+    return GKOC_OK;
+}
+
+// =========================================================================================
+// 4. Apply
+// =========================================================================================
+// ------------------------------------------------------------ 4a. the tuned kernels
 // one wave per storage group; lane l < stride: block = l / block_offset,
 // row = l % block_offset
 template <typename T, typename I, bool ADV, bool STORED = false>
@@ -373,8 +913,8 @@ __global__ __launch_bounds__(256) void jacobi_apply_kernel(
             T m;
             if constexpr (STORED) {
                 // block stored in the precision of its group (any layout; T = double)
-                m = load_stored_any(int(precisions[blk]), blocks + scheme.group_offset * group,
-                                    lane + c * stride);
+                m = load_stored(int(precisions[blk]), blocks + scheme.group_offset * group,
+                                lane + c * stride);
             } else {
                 m = gp[c * stride];
             }
@@ -482,247 +1022,6 @@ __global__ __launch_bounds__(256) void jacobi_apply_mfma_kernel(
 // value are requested before the first use; b[start + c] then comes from lane
 // (block, c) through ds_bpermute instead of BO more gathers.  Accumulation
 // order and rounding are those of the generic kernel (reference apply_block).
-// ---- reduced-precision block storage (adaptive block-Jacobi with a fixed
-// storage_optimization; include/ginkgo/core/preconditioner/jacobi.hpp, the types of
-// core/preconditioner/jacobi_utils.hpp:15-37 for ValueType = double).  The stored
-// blocks are widened to double on load and the product runs in double, exactly like
-// reference apply_block with its default_converter.  PREC = the precision_reduction
-// byte (preserving << 4 | nonpreserving):
-//   0x01 float (round to nearest)            0x02 half (via float, round to nearest
-//   0x10 upper 32 bits of the double              even; values below the smallest
-//   0x11 upper 16 bits of the float               normal half become signed zero,
-//   0x20 upper 16 bits of the double              like gko::half, half.hpp:405-433)
-// A group keeps its place (group_offset is in doubles); its reduced entries sit at
-// the same element index of the narrower type, i.e. in the first part of the group.
-template <int PREC>
-struct stored;
-template <>
-struct stored<0x01> {
-    using type = float;
-    __device__ static double load(type v) { return double(v); }
-    __device__ static type store(double v) { return float(v); }
-};
-template <>
-struct stored<0x10> {
-    using type = uint32_t;
-    __device__ static double load(type v) { return __longlong_as_double((long long)(uint64_t(v) << 32)); }
-    __device__ static type store(double v) { return uint32_t(uint64_t(__double_as_longlong(v)) >> 32); }
-};
-template <>
-struct stored<0x20> {
-    using type = uint16_t;
-    __device__ static double load(type v) { return __longlong_as_double((long long)(uint64_t(v) << 48)); }
-    __device__ static type store(double v) { return uint16_t(uint64_t(__double_as_longlong(v)) >> 48); }
-};
-template <>
-struct stored<0x11> {
-    using type = uint16_t;
-    __device__ static double load(type v) { return double(__uint_as_float(uint32_t(v) << 16)); }
-    __device__ static type store(double v) { return uint16_t(__float_as_uint(float(v)) >> 16); }
-};
-template <>
-struct stored<0x02> {
-    using type = uint16_t;
-    __device__ static double load(type h)
-    {
-        // the hardware conversion, except that subnormal halves read as signed zero
-        // (gko::half does not decode them, half.hpp:444-446)
-        _Float16 hv;
-        __builtin_memcpy(&hv, &h, 2);
-        const float f = (h & 0x7c00u) == 0 ? __uint_as_float(uint32_t(h & 0x8000u) << 16) : float(hv);
-        return double(f);
-    }
-    __device__ static type store(double v)
-    {
-        const uint32_t f = __float_as_uint(float(v));
-        const uint16_t sign = uint16_t((f >> 16) & 0x8000u);
-        const uint32_t e = (f >> 23) & 0xffu, m = f & 0x007fffffu;
-        if (e == 0xffu) return uint16_t(sign | 0x7c00u | (m ? 0x03ffu : 0u));
-        if (e <= 112u) return sign;                      // below the normal half range
-        if (e - 112u >= 31u) return uint16_t(sign | 0x7c00u);
-        const uint16_t res = uint16_t(sign | ((e - 112u) << 10) | (m >> 13));
-        const uint32_t tail = m & 0x1fffu;
-        return uint16_t(res + ((tail > 0x1000u || (tail == 0x1000u && (res & 1u))) ? 1u : 0u));
-    }
-};
-
-// runtime-selected storage type (one precision per storage group)
-__device__ __forceinline__ double load_stored(int prec, const double* group, int64_t idx)
-{
-    switch (prec) {
-    case 0x01: return stored<0x01>::load(reinterpret_cast<const float*>(group)[idx]);
-    case 0x02: return stored<0x02>::load(reinterpret_cast<const uint16_t*>(group)[idx]);
-    case 0x10: return stored<0x10>::load(reinterpret_cast<const uint32_t*>(group)[idx]);
-    case 0x11: return stored<0x11>::load(reinterpret_cast<const uint16_t*>(group)[idx]);
-    case 0x20: return stored<0x20>::load(reinterpret_cast<const uint16_t*>(group)[idx]);
-    default: return group[idx];
-    }
-}
-
-__device__ double load_stored_any(int prec, const double* group, int64_t idx)
-{
-    return load_stored(prec, group, idx);
-}
-
-__device__ __forceinline__ void store_stored(int prec, double* group, int64_t idx, double v)
-{
-    switch (prec) {
-    case 0x01: reinterpret_cast<float*>(group)[idx] = stored<0x01>::store(v); break;
-    case 0x02: reinterpret_cast<uint16_t*>(group)[idx] = stored<0x02>::store(v); break;
-    case 0x10: reinterpret_cast<uint32_t*>(group)[idx] = stored<0x10>::store(v); break;
-    case 0x11: reinterpret_cast<uint16_t*>(group)[idx] = stored<0x11>::store(v); break;
-    case 0x20: reinterpret_cast<uint16_t*>(group)[idx] = stored<0x20>::store(v); break;
-    default: group[idx] = v; break;
-    }
-}
-
-// reference compute_inf_norm (reference/components/matrix_operations.hpp:22-37) applied to
-// the ROW-major block as the reference applies it (element i + j * bs = row j, column i):
-// lane r sums |B(j, r)| over j in order, the maximum over the lanes is order-free
-__device__ __forceinline__ double block_norm_lds(const double* Bm, int ld, int bs, int r, int sub)
-{
-    double t = 0.0;
-    if (r < bs) {
-        for (int j = 0; j < bs; ++j) t += fabs(Bm[j * ld + r]);
-    }
-    for (int off = 1; off < sub; off <<= 1) {
-        const double o = __shfl_xor(t, off, 64);
-        t = o > t ? o : t;
-    }
-    return t;
-}
-
-// validate_precision_reduction_feasibility<ReducedType> (reference :280-307): round the
-// inverse to the reduced type, invert that in double, condition number must be >= 1 and
-// * eps(double) < 1e-3.  PREC 0x01 = float, 0x02 = half.  Tm: scratch block in LDS.
-template <int PREC>
-__device__ __forceinline__ bool feasible_lds(const double* Bm, double* Tm, int ld, int bs, int r,
-                                             int g, int sub, int max_bs)
-{
-    if (r < bs) {
-        for (int j = 0; j < bs; ++j) {
-            Tm[r * ld + j] = stored<PREC>::load(stored<PREC>::store(Bm[r * ld + j]));
-        }
-    }
-    wave_lds_sync();
-    double cond = block_norm_lds(Tm, ld, bs, r, sub);
-    int perm = r;
-    const bool ok = gauss_jordan_lds<double>(Tm, ld, bs, r, g, sub, max_bs, perm);
-    cond *= block_norm_lds(Tm, ld, bs, r, sub);
-    wave_lds_sync();
-    return ok && cond >= 1.0 && cond * (1.0 / 9007199254740992.0) < 1e-3;
-}
-
-// adaptive generate (reference/preconditioner/jacobi_kernels.cpp:313-411), value type
-// double, one wave per storage group (64-wide groups: 64/SUB blocks).
-// precisions[blk] in: requested precision_reduction byte (0xff = autodetect); out: the
-// precision of the group = get_optimal_storage_reduction of the AND of the blocks'
-// descriptors (core/preconditioner/jacobi_utils.hpp:104-176).  conditioning[blk] =
-// norm(block) * norm(inverse).  dynamic LDS: 2 * (64/SUB) * SUB * (SUB+1) doubles.
-template <typename I>
-__global__ __launch_bounds__(64) void jacobi_generate_adaptive_kernel(
-    const I* __restrict__ row_ptrs, const I* __restrict__ cols, const double* __restrict__ vals,
-    int64_t num_blocks, int sub, gkoc_jacobi_scheme scheme, const I* __restrict__ block_ptrs,
-    double accuracy, uint8_t* __restrict__ precisions, double* __restrict__ conditioning,
-    double* __restrict__ blocks)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    double* lds = reinterpret_cast<double*>(lds_raw);
-    const int lane = threadIdx.x;
-    const int per_wave = 64 / sub;
-    const int g = lane / sub;
-    const int r = lane % sub;
-    const int ld = sub + 1;
-    double* Bm = lds + int64_t(g) * sub * ld;
-    double* Tm = lds + int64_t(per_wave) * sub * ld + int64_t(g) * sub * ld;
-    const int64_t blk = int64_t(blockIdx.x) * per_wave + g;
-    int64_t start = 0;
-    int bs = 0;
-    if (blk < num_blocks) {
-        start = block_ptrs[blk];
-        bs = int(block_ptrs[blk + 1] - start);
-    }
-    if (r < bs) {
-        for (int j = 0; j < bs; ++j) Bm[r * ld + j] = 0.0;
-        const int64_t a = row_ptrs[start + r], e = row_ptrs[start + r + 1];
-        for (int64_t k = a; k < e; ++k) {
-            const int64_t c = int64_t(cols[k]) - start;
-            if (c >= 0 && c < bs) Bm[r * ld + c] = vals[k];
-        }
-    }
-    const int max_bs = wave_max(bs);
-    wave_lds_sync();
-    double cond = block_norm_lds(Bm, ld, bs, r, sub);
-    int perm = r;
-    gauss_jordan_lds<double>(Bm, ld, bs, r, g, sub, max_bs, perm);
-    cond *= block_norm_lds(Bm, ld, bs, r, sub);
-    const int request = blk < num_blocks ? int(precisions[blk]) : -1;
-    uint32_t desc = 0xffffffffu;           // blocks past the end do not restrict the group
-    const bool any_auto = __ballot(request == 0xff) != 0;
-    bool v1 = false, v2 = false;
-    if (any_auto) {                        // wave-uniform: the inversions run in lock step
-        v1 = feasible_lds<0x01>(Bm, Tm, ld, bs, r, g, sub, max_bs);
-        v2 = feasible_lds<0x02>(Bm, Tm, ld, bs, r, g, sub, max_bs);
-    }
-    if (request == 0xff) {
-        // get_supported_storage_reductions: eps of truncated<double,4>, truncated<float,2>,
-        // half, truncated<double,2>, float; verificators are pure, so evaluating them
-        // eagerly and replaying the short-circuit logic gives the same set
-        int verified1 = 2;
-        desc = 0;
-        if (cond * (1.0 / 16) < accuracy) desc |= 0x04;
-        if (cond * (1.0 / 128) < accuracy) {
-            verified1 = v1 ? 1 : 0;
-            if (v1) desc |= 0x02;
-        }
-        if (cond * (1.0 / 2048) < accuracy && verified1 != 0 && v2) desc |= 0x01;
-        if (cond * (1.0 / 1048576) < accuracy) desc |= 0x10;
-        if (cond * (1.0 / 16777216) < accuracy) {
-            if (verified1 == 2) verified1 = v1 ? 1 : 0;
-            if (verified1 == 1) desc |= 0x08;
-        }
-    } else if (request >= 0) {
-        desc = request == 0x01 ? 0x08u : request == 0x02 ? 0x01u : request == 0x10 ? 0x10u
-             : request == 0x11 ? 0x02u : request == 0x20 ? 0x04u : 0u;
-    }
-    for (int off = 1; off < 64; off <<= 1) desc &= __shfl_xor(desc, off, 64);
-    const int p = (desc & 0x01) ? 0x02 : (desc & 0x02) ? 0x11 : (desc & 0x04) ? 0x20
-                : (desc & 0x08) ? 0x01 : (desc & 0x10) ? 0x10 : 0x00;
-    if (blk < num_blocks && r == 0) {
-        precisions[blk] = uint8_t(p);
-        if (conditioning) conditioning[blk] = cond;
-    }
-    const int64_t gsize = int64_t(1) << scheme.group_power;
-    const int64_t stride = scheme.block_offset << scheme.group_power;
-    double* group = blocks + scheme.group_offset * (blk >> scheme.group_power);
-    const int64_t boff = scheme.block_offset * (blk & (gsize - 1));
-    for (int j = 0; j < max_bs; ++j) {
-        const int pj = __shfl(perm, g * sub + j, 64);
-        if (r < bs && j < bs) store_stored(p, group, boff + r + int64_t(pj) * stride, Bm[r * ld + j]);
-    }
-}
-
-// in place: the group's double entries become PREC entries at the same element index
-template <int PREC, int BO>
-__global__ __launch_bounds__(64) void jacobi_convert_storage_kernel(int64_t num_groups,
-                                                                    int64_t group_offset,
-                                                                    double* blocks)
-{
-    using S = typename stored<PREC>::type;
-    const int64_t group = blockIdx.x;
-    if (group >= num_groups) return;
-    double* gp = blocks + group_offset * group;
-    double v[BO];
-#pragma unroll
-    for (int c = 0; c < BO; ++c) v[c] = gp[c * 64 + threadIdx.x];
-    // every lane has its loads back before any narrow entry is written
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    S* sp = reinterpret_cast<S*>(gp);
-#pragma unroll
-    for (int c = 0; c < BO; ++c) sp[c * 64 + threadIdx.x] = stored<PREC>::store(v[c]);
-}
-
 template <typename T, typename I, bool ADV, int BO, int GPW, bool DOT = false, int PREC = 0>
 __global__ __launch_bounds__(256) void jacobi_apply_fixed_kernel(
     int64_t num_blocks, int64_t num_groups, int64_t group_offset,
@@ -1184,33 +1483,24 @@ int launch_pipe_steps(gkoc_stream_t s, int64_t num_blocks, int64_t n_rows, uint3
     GKOC_REQUIRE(beta_in && beta_out && beta_in != beta_out, GKOC_E_INVALID,
                  "beta_in and beta_out must be two different scalars");
     const int64_t bo = scheme.block_offset;
-    GKOC_REQUIRE(bo >= 1 && bo <= 16 && (bo << scheme.group_power) == 64 && (bo & (bo - 1)) == 0,
-                 GKOC_E_NOT_SUPPORTED, "needs block_offset in {1,2,4,8,16} and a 64-wide group");
+    GKOC_REQUIRE(wide_group_layout(scheme), GKOC_E_NOT_SUPPORTED,
+                 "needs block_offset in {1,2,4,8,16} and a 64-wide group");
     GKOC_REQUIRE(max_bs <= uint64_t(bo), GKOC_E_INVALID, "max_block_size exceeds block_offset");
     GKOC_REQUIRE(work_bytes >= fused_workspace_bytes(n_rows, sizeof(T)), GKOC_E_WORKSPACE,
                  "workspace too small (gkoc_x_workspace_bytes)");
     const int64_t groups = ceildiv(num_blocks, int64_t(1) << scheme.group_power);
-    const int gpw = (bo * int64_t(sizeof(T)) >= 128) ? 1 : 2;
-    const int64_t nb = ceildiv(groups, 4 * gpw);
+    const int64_t nb = ceildiv(groups, 4 * groups_per_wave<T>(bo));
     const int64_t total = int64_t(fused_workspace_bytes(n_rows, sizeof(T)) / sizeof(T));
     GKOC_REQUIRE(3 * nb <= total, GKOC_E_WORKSPACE, "too many blocks for the workspace");
     T* partial = static_cast<T*>(work);
     const int64_t go = scheme.group_offset;
-#define GKOC_JAC_PS(BO_)                                                                              \
-    jacobi_pipe_steps_kernel<T, I, BO_, ((BO_ * sizeof(T) >= 128) ? 1 : 2)>                            \
-        <<<dim3(unsigned(nb)), dim3(256), 0, as_stream(s)>>>(num_blocks, groups, go, block_ptrs, blocks, \
-                                                             x, r, z, w, p, q, f, g, m, nv, prev_rho,  \
-                                                             rho, delta, beta_in, beta_out,            \
-                                                             const_cast<uint8_t*>(stop), partial, nb,  \
-                                                             gate)
-    switch (int(bo)) {
-    case 1: GKOC_JAC_PS(1); break;
-    case 2: GKOC_JAC_PS(2); break;
-    case 4: GKOC_JAC_PS(4); break;
-    case 8: GKOC_JAC_PS(8); break;
-    default: GKOC_JAC_PS(16); break;
-    }
-#undef GKOC_JAC_PS
+    with_block_offset(bo, [&](auto bc) {
+        constexpr int BO = decltype(bc)::value;
+        jacobi_pipe_steps_kernel<T, I, BO, groups_per_wave<T>(BO)>
+            <<<dim3(unsigned(nb)), dim3(256), 0, as_stream(s)>>>(
+                num_blocks, groups, go, block_ptrs, blocks, x, r, z, w, p, q, f, g, m, nv, prev_rho, rho, delta,
+                beta_in, beta_out, const_cast<uint8_t*>(stop), partial, nb, gate);
+    });
     GKOC_LAUNCH_OK();
     fold_rows_kernel<T><<<dim3(3), dim3(1024), 0, as_stream(s)>>>(nb, nb, partial, out3);
     GKOC_LAUNCH_OK();
@@ -1222,12 +1512,9 @@ int launch_pipe_steps(gkoc_stream_t s, int64_t num_blocks, int64_t n_rows, uint3
 inline bool step2_apply_fits(int64_t num_blocks, int64_t n_rows, gkoc_jacobi_scheme scheme,
                              size_t value_size)
 {
-    const int64_t bo = scheme.block_offset;
-    if (!(bo >= 1 && bo <= 16 && (bo << scheme.group_power) == 64 && (bo & (bo - 1)) == 0)) return false;
-    if (num_blocks <= 0 || n_rows <= 0) return false;
+    if (!wide_group_layout(scheme) || num_blocks <= 0 || n_rows <= 0) return false;
     const int64_t groups = ceildiv(num_blocks, int64_t(1) << scheme.group_power);
-    const int gpw = (bo * int64_t(value_size) >= 128) ? 1 : 2;
-    const int64_t nb = ceildiv(groups, 4 * gpw);
+    const int64_t nb = ceildiv(groups, 4 * groups_per_wave(scheme.block_offset, value_size));
     const int64_t total = int64_t(fused_workspace_bytes(n_rows, value_size) / value_size);
     const int64_t pstride = (total - 2 * fold_chunks) / 2;
     return nb <= pstride;
@@ -1244,8 +1531,7 @@ int launch_step2_apply(gkoc_stream_t s, int64_t num_blocks, int64_t n_rows, uint
     GKOC_REQUIRE(block_ptrs && blocks && x && r && p && q && beta && rho && stop && z && work,
                  GKOC_E_INVALID, "null pointer");
     const int64_t bo = scheme.block_offset;
-    GKOC_REQUIRE(bo >= 1 && bo <= 16 && (bo << scheme.group_power) == 64 && (bo & (bo - 1)) == 0,
-                 GKOC_E_NOT_SUPPORTED,
+    GKOC_REQUIRE(wide_group_layout(scheme), GKOC_E_NOT_SUPPORTED,
                  "fused step_2 + apply needs block_offset in {1,2,4,8,16} and a 64-wide group");
     GKOC_REQUIRE(max_bs <= uint64_t(bo), GKOC_E_INVALID, "max_block_size exceeds block_offset");
     GKOC_REQUIRE(work_bytes >= fused_workspace_bytes(n_rows, sizeof(T)), GKOC_E_WORKSPACE,
@@ -1253,8 +1539,7 @@ int launch_step2_apply(gkoc_stream_t s, int64_t num_blocks, int64_t n_rows, uint
     const int64_t groups = ceildiv(num_blocks, int64_t(1) << scheme.group_power);
     // groups per wave as in the plain fused apply + dot: the partial sums then group the same
     // rows, and <r, z> comes out with the same bits
-    const int gpw = (bo * int64_t(sizeof(T)) >= 128) ? 1 : 2;
-    const int64_t nb = ceildiv(groups, 4 * gpw);
+    const int64_t nb = ceildiv(groups, 4 * groups_per_wave<T>(bo));
     // workspace of gkoc_x_workspace_bytes: [two rows of partials | 2 * fold_chunks of scratch]:
     // (n + 63) / 64 + 4096 + fold_chunks values; a row needs n / 64 at most (one partial per 8
     // groups of 8+ rows)
@@ -1265,19 +1550,12 @@ int launch_step2_apply(gkoc_stream_t s, int64_t num_blocks, int64_t n_rows, uint
     T* partial = static_cast<T*>(work);
     T* scratch = partial + 2 * pstride;
     const int64_t go = scheme.group_offset;
-#define GKOC_JAC_S2(BO_)                                                                          \
-    jacobi_step2_apply_kernel<T, I, BO_, ((BO_ * sizeof(T) >= 128) ? 1 : 2)>                        \
-        <<<dim3(unsigned(nb)), dim3(256), 0, as_stream(s)>>>(num_blocks, groups, go, block_ptrs,     \
-                                                             blocks, x, r, p, q, beta, rho, stop, z, \
-                                                             partial, pstride)
-    switch (int(bo)) {
-    case 1: GKOC_JAC_S2(1); break;
-    case 2: GKOC_JAC_S2(2); break;
-    case 4: GKOC_JAC_S2(4); break;
-    case 8: GKOC_JAC_S2(8); break;
-    default: GKOC_JAC_S2(16); break;
-    }
-#undef GKOC_JAC_S2
+    with_block_offset(bo, [&](auto bc) {
+        constexpr int BO = decltype(bc)::value;
+        jacobi_step2_apply_kernel<T, I, BO, groups_per_wave<T>(BO)>
+            <<<dim3(unsigned(nb)), dim3(256), 0, as_stream(s)>>>(
+                num_blocks, groups, go, block_ptrs, blocks, x, r, p, q, beta, rho, stop, z, partial, pstride);
+    });
     GKOC_LAUNCH_OK();
     // <r, z> through the tree of gkoc_x_jacobi_simple_apply_dot: the same bits as the unfused pair
     return fold_partials2<T>(s, nb, pstride, partial, scratch, rho_out, norm_out, take_sqrt ? 1 : -1);
@@ -1294,7 +1572,7 @@ void launch_apply_fixed(gkoc_stream_t s, int64_t num_blocks, int64_t groups,
                         const T* blocks, const T* alpha, const T* b,
                         const T* beta, T* x)
 {
-    constexpr int GPW = (BO * sizeof(T) >= 128) ? 1 : 2;
+    constexpr int GPW = groups_per_wave<T>(BO);
     jacobi_apply_fixed_kernel<T, I, ADV, BO, GPW>
         <<<dim3(unsigned(ceildiv(groups, 4 * GPW))), dim3(256), 0,
            as_stream(s)>>>(num_blocks, groups, group_offset, block_ptrs, blocks,
@@ -1309,7 +1587,7 @@ void launch_apply_dot_fixed(gkoc_stream_t s, int64_t num_blocks, int64_t groups,
                             const T* blocks, const T* b, T* x, T* partial,
                             int64_t* n_partials)
 {
-    constexpr int GPW = (BO * sizeof(T) >= 128) ? 1 : 2;
+    constexpr int GPW = groups_per_wave<T>(BO);
     const int64_t nb = ceildiv(groups, 4 * GPW);
     *n_partials = nb;
     jacobi_apply_fixed_kernel<T, I, false, BO, GPW, true>
@@ -1331,9 +1609,7 @@ int launch_apply_dot(gkoc_stream_t s, int64_t num_blocks, int64_t n_rows,
     }
     GKOC_REQUIRE(block_ptrs && blocks && b && x && work, GKOC_E_INVALID, "null pointer");
     const int64_t bo = scheme.block_offset;
-    GKOC_REQUIRE(bo >= 1 && bo <= 16 && (bo << scheme.group_power) == 64 &&
-                     (bo & (bo - 1)) == 0,
-                 GKOC_E_NOT_SUPPORTED,
+    GKOC_REQUIRE(wide_group_layout(scheme), GKOC_E_NOT_SUPPORTED,
                  "fused apply+dot needs block_offset in {1,2,4,8,16} and a 64-wide group");
     GKOC_REQUIRE(max_bs <= uint64_t(bo), GKOC_E_INVALID,
                  "max_block_size exceeds block_offset");
@@ -1347,13 +1623,10 @@ int launch_apply_dot(gkoc_stream_t s, int64_t num_blocks, int64_t n_rows,
     T* scratch = partial + (fused_workspace_bytes(n_rows, sizeof(T)) / sizeof(T) - fold_chunks);
     int64_t np = 0;
     const int64_t go = scheme.group_offset;
-    switch (int(bo)) {
-    case 1: launch_apply_dot_fixed<T, I, 1>(s, num_blocks, groups, go, block_ptrs, blocks, b, x, partial, &np); break;
-    case 2: launch_apply_dot_fixed<T, I, 2>(s, num_blocks, groups, go, block_ptrs, blocks, b, x, partial, &np); break;
-    case 4: launch_apply_dot_fixed<T, I, 4>(s, num_blocks, groups, go, block_ptrs, blocks, b, x, partial, &np); break;
-    case 8: launch_apply_dot_fixed<T, I, 8>(s, num_blocks, groups, go, block_ptrs, blocks, b, x, partial, &np); break;
-    default: launch_apply_dot_fixed<T, I, 16>(s, num_blocks, groups, go, block_ptrs, blocks, b, x, partial, &np); break;
-    }
+    with_block_offset(bo, [&](auto bc) {
+        launch_apply_dot_fixed<T, I, decltype(bc)::value>(s, num_blocks, groups, go, block_ptrs, blocks, b, x,
+                                                          partial, &np);
+    });
     GKOC_LAUNCH_OK();
     return fold_partials<T>(s, np, partial, scratch, dot_out, false);
 }
@@ -1374,20 +1647,13 @@ int launch_apply(gkoc_stream_t s, int64_t num_blocks, uint32_t max_bs,
     const int64_t gsize = int64_t(1) << scheme.group_power;
     const int64_t groups = ceildiv(num_blocks, gsize);
     const int64_t bo = scheme.block_offset;
-    if (nrhs == 1 && ldb == 1 && ldx == 1 && (bo << scheme.group_power) == 64 &&
-        bo <= 16) {
+    const bool wide = wide_group_layout(scheme);
+    if (nrhs == 1 && ldb == 1 && ldx == 1 && wide) {
         const int64_t go = scheme.group_offset;
-#define GKOC_JAC_FIXED(BO)                                                     \
-    launch_apply_fixed<T, I, ADV, BO>(s, num_blocks, groups, go, block_ptrs,   \
-                                      blocks, alpha, b, beta, x)
-        switch (int(bo)) {
-        case 1: GKOC_JAC_FIXED(1); break;
-        case 2: GKOC_JAC_FIXED(2); break;
-        case 4: GKOC_JAC_FIXED(4); break;
-        case 8: GKOC_JAC_FIXED(8); break;
-        default: GKOC_JAC_FIXED(16); break;
-        }
-#undef GKOC_JAC_FIXED
+        with_block_offset(bo, [&](auto bc) {
+            launch_apply_fixed<T, I, ADV, decltype(bc)::value>(s, num_blocks, groups, go, block_ptrs, blocks, alpha,
+                                                               b, beta, x);
+        });
         GKOC_LAUNCH_OK();
         return GKOC_OK;
     }
@@ -1396,7 +1662,7 @@ int launch_apply(gkoc_stream_t s, int64_t num_blocks, uint32_t max_bs,
     const int64_t mfma_from = mfma_mode == 1 ? 2 : mfma_mode == 3 ? 4 : 9;
     const bool mfma = sizeof(T) == 8 && mfma_mode != 0 && nrhs >= mfma_from && bo == 8 &&
                       scheme.group_power == 3 && b != x;
-    if (nrhs >= 2 && (bo << scheme.group_power) == 64 && bo <= 16 && !mfma) {
+    if (nrhs >= 2 && wide && !mfma) {
         // several right-hand sides, fast-path layout: the blocks stay in registers for all columns
         // (L256, block size 8, profiles/r03_jacobi_multi_256.txt: 2 / 4 / 8 columns 279 / 375 / 630 us =
         // 72 / 72 / 64 % of 8 TB/s; round 2: 530 / 654 / 778 with the general and the matrix-core
@@ -1404,26 +1670,19 @@ int launch_apply(gkoc_stream_t s, int64_t num_blocks, uint32_t max_bs,
         const int pairs_ok = reinterpret_cast<uintptr_t>(b) % (2 * sizeof(T)) == 0 && ldb % 2 == 0 &&
                              reinterpret_cast<uintptr_t>(x) % (2 * sizeof(T)) == 0 && ldx % 2 == 0;
         const dim3 gm(unsigned(ceildiv(groups, 4)));
-#define GKOC_JAC_MULTI(BO)                                                                        \
-    do {                                                                                          \
-        if (nrhs <= 4) {                                                                          \
-            jacobi_apply_fixed_multi_kernel<T, I, ADV, BO, 4><<<gm, dim3(256), 0, as_stream(s)>>>( \
-                num_blocks, groups, scheme.group_offset, block_ptrs, blocks, alpha, b, ldb, beta, \
-                x, ldx, int(nrhs), pairs_ok);                                                     \
-        } else {                                                                                  \
-            jacobi_apply_fixed_multi_kernel<T, I, ADV, BO, 8><<<gm, dim3(256), 0, as_stream(s)>>>( \
-                num_blocks, groups, scheme.group_offset, block_ptrs, blocks, alpha, b, ldb, beta, \
-                x, ldx, int(nrhs), pairs_ok);                                                     \
-        }                                                                                         \
-    } while (0)
-        switch (int(bo)) {
-        case 1: GKOC_JAC_MULTI(1); break;
-        case 2: GKOC_JAC_MULTI(2); break;
-        case 4: GKOC_JAC_MULTI(4); break;
-        case 8: GKOC_JAC_MULTI(8); break;
-        default: GKOC_JAC_MULTI(16); break;
-        }
-#undef GKOC_JAC_MULTI
+        // four columns per pass up to four right-hand sides, eight beyond
+        with_block_offset(bo, [&](auto bc) {
+            constexpr int BO = decltype(bc)::value;
+            if (nrhs <= 4) {
+                jacobi_apply_fixed_multi_kernel<T, I, ADV, BO, 4><<<gm, dim3(256), 0, as_stream(s)>>>(
+                    num_blocks, groups, scheme.group_offset, block_ptrs, blocks, alpha, b, ldb, beta, x, ldx,
+                    int(nrhs), pairs_ok);
+            } else {
+                jacobi_apply_fixed_multi_kernel<T, I, ADV, BO, 8><<<gm, dim3(256), 0, as_stream(s)>>>(
+                    num_blocks, groups, scheme.group_offset, block_ptrs, blocks, alpha, b, ldb, beta, x, ldx,
+                    int(nrhs), pairs_ok);
+            }
+        });
         GKOC_LAUNCH_OK();
         return GKOC_OK;
     }
@@ -1461,20 +1720,6 @@ void launch_apply_stored_fixed(gkoc_stream_t s, int64_t num_blocks, int64_t grou
             nullptr, jacobi_xcd_map(ceildiv(groups, 4 * GPW)));
 }
 
-inline bool known_precision(int prec)
-{
-    return prec == 0x01 || prec == 0x02 || prec == 0x10 || prec == 0x11 || prec == 0x20;
-}
-
-#define GKOC_FOR_PREC(M, ...)                 \
-    switch (prec) {                           \
-    case 0x01: M(0x01, __VA_ARGS__); break;   \
-    case 0x02: M(0x02, __VA_ARGS__); break;   \
-    case 0x10: M(0x10, __VA_ARGS__); break;   \
-    case 0x11: M(0x11, __VA_ARGS__); break;   \
-    default: M(0x20, __VA_ARGS__); break;     \
-    }
-
 template <typename I, bool ADV>
 int launch_apply_stored(gkoc_stream_t s, int64_t num_blocks, uint32_t max_bs,
                         gkoc_jacobi_scheme scheme, const I* block_ptrs, const double* blocks,
@@ -1489,8 +1734,7 @@ int launch_apply_stored(gkoc_stream_t s, int64_t num_blocks, uint32_t max_bs,
     GKOC_REQUIRE(known_precision(prec), GKOC_E_NOT_SUPPORTED, "unknown storage precision");
     GKOC_REQUIRE(block_ptrs && blocks && b && x, GKOC_E_INVALID, "null pointer");
     const int64_t bo = scheme.block_offset;
-    GKOC_REQUIRE(bo >= 1 && bo <= 16 && (bo & (bo - 1)) == 0 && (bo << scheme.group_power) == 64,
-                 GKOC_E_NOT_SUPPORTED,
+    GKOC_REQUIRE(wide_group_layout(scheme), GKOC_E_NOT_SUPPORTED,
                  "reduced-precision storage needs block_offset in {1,2,4,8,16}, 64-wide groups");
     GKOC_REQUIRE(max_bs <= uint64_t(bo), GKOC_E_INVALID, "max_block_size exceeds block_offset");
     const int64_t groups = ceildiv(num_blocks, int64_t(1) << scheme.group_power);
@@ -1499,484 +1743,14 @@ int launch_apply_stored(gkoc_stream_t s, int64_t num_blocks, uint32_t max_bs,
     for (int64_t j = 0; j < nrhs; ++j) {
         GKOC_REQUIRE(ldb == 1 && ldx == 1, GKOC_E_NOT_SUPPORTED,
                      "reduced-precision storage: one right-hand side with unit strides");
-#define GKOC_JAC_ST(PREC_, BO_)                                                                 \
-    launch_apply_stored_fixed<I, ADV, BO_, PREC_>(s, num_blocks, groups, go, block_ptrs, blocks, \
-                                                  alpha, b + j, beta, x + j)
-#define GKOC_JAC_ST_BO(PREC_, dummy)            \
-    switch (int(bo)) {                          \
-    case 1: GKOC_JAC_ST(PREC_, 1); break;       \
-    case 2: GKOC_JAC_ST(PREC_, 2); break;       \
-    case 4: GKOC_JAC_ST(PREC_, 4); break;       \
-    case 8: GKOC_JAC_ST(PREC_, 8); break;       \
-    default: GKOC_JAC_ST(PREC_, 16); break;     \
-    }
-        GKOC_FOR_PREC(GKOC_JAC_ST_BO, 0)
-#undef GKOC_JAC_ST_BO
-#undef GKOC_JAC_ST
+        with_precision(prec, [&](auto pc) {
+            with_block_offset(bo, [&](auto bc) {
+                launch_apply_stored_fixed<I, ADV, decltype(bc)::value, decltype(pc)::value>(
+                    s, num_blocks, groups, go, block_ptrs, blocks, alpha, b + j, beta, x + j);
+            });
+        });
         GKOC_LAUNCH_OK();
     }
-    return GKOC_OK;
-}
-
-int launch_convert_storage(gkoc_stream_t s, int64_t num_blocks, gkoc_jacobi_scheme scheme,
-                           double* blocks, int prec)
-{
-    if (prec == 0 || num_blocks <= 0) return GKOC_OK;
-    GKOC_REQUIRE(known_precision(prec), GKOC_E_NOT_SUPPORTED, "unknown storage precision");
-    GKOC_REQUIRE(blocks, GKOC_E_INVALID, "null pointer");
-    const int64_t bo = scheme.block_offset;
-    GKOC_REQUIRE(bo >= 1 && bo <= 16 && (bo & (bo - 1)) == 0 && (bo << scheme.group_power) == 64,
-                 GKOC_E_NOT_SUPPORTED,
-                 "reduced-precision storage needs block_offset in {1,2,4,8,16}, 64-wide groups");
-    const int64_t groups = ceildiv(num_blocks, int64_t(1) << scheme.group_power);
-#define GKOC_JAC_CV(PREC_, BO_)                                                        \
-    jacobi_convert_storage_kernel<PREC_, BO_>                                          \
-        <<<dim3(unsigned(groups)), dim3(64), 0, as_stream(s)>>>(groups, scheme.group_offset, blocks)
-#define GKOC_JAC_CV_BO(PREC_, dummy)            \
-    switch (int(bo)) {                          \
-    case 1: GKOC_JAC_CV(PREC_, 1); break;       \
-    case 2: GKOC_JAC_CV(PREC_, 2); break;       \
-    case 4: GKOC_JAC_CV(PREC_, 4); break;       \
-    case 8: GKOC_JAC_CV(PREC_, 8); break;       \
-    default: GKOC_JAC_CV(PREC_, 16); break;     \
-    }
-    GKOC_FOR_PREC(GKOC_JAC_CV_BO, 0)
-#undef GKOC_JAC_CV_BO
-#undef GKOC_JAC_CV
-    GKOC_LAUNCH_OK();
-    return GKOC_OK;
-}
-
-template <typename T, typename I>
-int launch_generate(gkoc_stream_t s, const I* row_ptrs, const I* cols,
-                    const T* vals, int64_t num_blocks, uint32_t max_bs,
-                    gkoc_jacobi_scheme scheme, const I* block_ptrs, T* blocks)
-{
-    if (num_blocks <= 0) return GKOC_OK;
-    GKOC_REQUIRE(max_bs >= 1 && max_bs <= 64, GKOC_E_NOT_SUPPORTED,
-                 "max_block_size must be in [1, 64]");
-    int sub = 1;
-    while (sub < int(max_bs)) sub *= 2;
-    const int per_wave = 64 / sub;
-    const size_t lds = size_t(per_wave) * sub * (sub + 1) * sizeof(T);
-    jacobi_generate_kernel<T, I>
-        <<<dim3(unsigned(ceildiv(num_blocks, per_wave))), dim3(64), lds,
-           as_stream(s)>>>(row_ptrs, cols, vals, num_blocks, sub, scheme,
-                           block_ptrs, blocks);
-    GKOC_LAUNCH_OK();
-    return GKOC_OK;
-}
-
-// Block-Jacobi application for the value types without a tuned kernel (complex): one lane per
-// (row, right-hand side) walks its row of the inverse block in the interleaved scheme - element
-// (r, c) of block b at group_offset * (b >> gp) + block_offset * (b & mask) + r + c * stride
-// (include/ginkgo/core/preconditioner/jacobi.hpp:37-140) - and adds the products in column order
-// (reference apply_block, reference/preconditioner/jacobi_kernels.cpp:419-531).  row_block[row] = the
-// block of a row (filled by jacobi_row_block_kernel).
-// (defined with the adaptive kernels at the end of this file)
-template <typename T, typename I, bool ADV>
-bool launch_apply_lanes_any(hipStream_t st, int64_t num_blocks, gkoc_jacobi_scheme scheme, const I* block_ptrs,
-                            const T* blocks, const uint8_t* precisions, const T* alpha, const T* b, int64_t ldb,
-                            const T* beta, T* x, int64_t ldx, int64_t nrhs);
-
-template <typename I>
-__global__ __launch_bounds__(256) void jacobi_row_block_kernel(int64_t num_blocks,
-                                                              const I* __restrict__ block_ptrs,
-                                                              I* __restrict__ row_block)
-{
-    const int64_t b = int64_t(blockIdx.x) * 256 + threadIdx.x;
-    if (b >= num_blocks) return;
-    for (I r = block_ptrs[b]; r < block_ptrs[b + 1]; ++r) row_block[r] = I(b);
-}
-
-template <typename T, typename I, bool ADV>
-__global__ __launch_bounds__(256) void jacobi_apply_simple_kernel(
-    int64_t n_rows, int64_t nrhs, gkoc_jacobi_scheme scheme, const I* __restrict__ block_ptrs,
-    const I* __restrict__ row_block, const T* __restrict__ blocks, const T* __restrict__ alpha_p,
-    const T* __restrict__ b, int64_t ldb, const T* __restrict__ beta_p, T* __restrict__ x, int64_t ldx)
-{
-    const int64_t total = n_rows * nrhs, step = int64_t(gridDim.x) * 256;
-    const int64_t stride = scheme.block_offset << scheme.group_power;
-    const int64_t mask = (int64_t(1) << scheme.group_power) - 1;
-    for (int64_t idx = int64_t(blockIdx.x) * 256 + threadIdx.x; idx < total; idx += step) {
-        const int64_t j = idx / n_rows, row = idx - j * n_rows;
-        const int64_t blk = row_block[row];
-        const int64_t start = block_ptrs[blk], bs = int64_t(block_ptrs[blk + 1]) - start;
-        const T* __restrict__ m = blocks + scheme.group_offset * (blk >> scheme.group_power) +
-                                  scheme.block_offset * (blk & mask) + (row - start);
-        T sum = T(0);
-        for (int64_t c = 0; c < bs; ++c) sum += m[c * stride] * b[(start + c) * ldb + j];
-        if (ADV) {
-            const T beta = beta_p[0];
-            const T ax = alpha_p[0] * sum;
-            x[row * ldx + j] = beta == T(0) ? ax : ax + beta * x[row * ldx + j];
-        } else {
-            x[row * ldx + j] = sum;
-        }
-    }
-}
-
-template <typename T, typename I, bool ADV>
-int launch_apply_simple(gkoc_stream_t s, int64_t num_blocks, gkoc_jacobi_scheme scheme, const I* block_ptrs,
-                        const T* blocks, const T* alpha, const T* b, int64_t ldb, const T* beta, T* x,
-                        int64_t ldx, int64_t nrhs)
-{
-    if (num_blocks <= 0 || nrhs <= 0) return GKOC_OK;
-    GKOC_REQUIRE(block_ptrs && blocks && b && x, GKOC_E_INVALID, "null pointer");
-    hipStream_t st = as_stream(s);
-    // complex values (the only users of this launcher): lane = (block, row), jacobi_apply_lanes_any_kernel
-    if (tune_value(GKOC_TUNE_JACOBI_LANES) != 1 &&
-        launch_apply_lanes_any<T, I, ADV>(st, num_blocks, scheme, block_ptrs, blocks, nullptr, alpha, b, ldb, beta,
-                                          x, ldx, nrhs)) {
-        GKOC_LAUNCH_OK();
-        return GKOC_OK;
-    }
-    I last = 0;
-    GKOC_HIP(hipMemcpyAsync(&last, block_ptrs + num_blocks, sizeof(I), hipMemcpyDeviceToHost, st));
-    GKOC_HIP(hipStreamSynchronize(st));
-    const int64_t n_rows = int64_t(last);
-    if (n_rows <= 0) return GKOC_OK;
-    I* row_block = nullptr;
-    GKOC_TRY(scratch_malloc(st, reinterpret_cast<void**>(&row_block), size_t(n_rows) * sizeof(I)));
-    jacobi_row_block_kernel<I><<<dim3(unsigned(ceildiv(num_blocks, 256))), dim3(256), 0, st>>>(
-        num_blocks, block_ptrs, row_block);
-    int64_t nb = ceildiv(n_rows * nrhs, 256);
-    if (nb > 8 * max_stream_blocks) nb = 8 * max_stream_blocks;
-    jacobi_apply_simple_kernel<T, I, ADV><<<dim3(unsigned(nb)), dim3(256), 0, st>>>(
-        n_rows, nrhs, scheme, block_ptrs, row_block, blocks, alpha, b, ldb, beta, x, ldx);
-    const hipError_t e = hipGetLastError();
-    (void)scratch_free(st, row_block);
-    GKOC_HIP(e);
-    return GKOC_OK;
-}
-
-}  // namespace
-}  // namespace gkoc
-
-using namespace gkoc;
-
-// complex block-Jacobi: find_blocks (indices only), generate (the Gauss-Jordan kernel above on
-// gkoc_cplx: pivot by magnitude), simple_apply / apply (jacobi_apply_simple_kernel).  Uniform storage
-// precision (block-wise / adaptive: the end of this file); agrees with the reference to rounding.
-#define GKOC_DEF_CJACOBI(T, TN, I, IN)                                                                  \
-    extern "C" int gkoc_jacobi_find_blocks_##TN##_##IN(gkoc_stream_t s, int64_t n_rows, const I* row_ptrs, \
-                                                       const I* col_idxs, uint32_t max_block_size,      \
-                                                       int64_t* num_blocks_host, I* block_ptrs)         \
-    {                                                                                                   \
-        return find_blocks_impl<I>(s, n_rows, row_ptrs, col_idxs, max_block_size, num_blocks_host,      \
-                                   block_ptrs);                                                         \
-    }                                                                                                   \
-    extern "C" int gkoc_jacobi_generate_##TN##_##IN(                                                    \
-        gkoc_stream_t s, int64_t n_rows, const I* row_ptrs, const I* col_idxs, const T* vals,           \
-        int64_t num_blocks, uint32_t max_block_size, gkoc_jacobi_scheme scheme, const I* block_ptrs,    \
-        T* blocks, T* conditioning)                                                                     \
-    {                                                                                                   \
-        (void)n_rows;                                                                                   \
-        GKOC_REQUIRE(conditioning == nullptr, GKOC_E_NOT_SUPPORTED,                                     \
-                     "condition numbers: gkoc_jacobi_generate_adaptive_* computes them");               \
-        GKOC_REQUIRE(max_block_size <= 32, GKOC_E_NOT_SUPPORTED, "complex blocks: max_block_size <= 32"); \
-        return launch_generate<T, I>(s, row_ptrs, col_idxs, vals, num_blocks, max_block_size, scheme,   \
-                                     block_ptrs, blocks);                                               \
-    }                                                                                                   \
-    extern "C" int gkoc_jacobi_simple_apply_##TN##_##IN(                                                \
-        gkoc_stream_t s, int64_t num_blocks, uint32_t max_block_size, gkoc_jacobi_scheme scheme,        \
-        const I* block_ptrs, const T* blocks, const T* b, int64_t ldb, T* x, int64_t ldx, int64_t nrhs) \
-    {                                                                                                   \
-        (void)max_block_size;                                                                           \
-        return launch_apply_simple<T, I, false>(s, num_blocks, scheme, block_ptrs, blocks, nullptr, b,  \
-                                                ldb, nullptr, x, ldx, nrhs);                            \
-    }                                                                                                   \
-    extern "C" int gkoc_jacobi_apply_##TN##_##IN(                                                       \
-        gkoc_stream_t s, int64_t num_blocks, uint32_t max_block_size, gkoc_jacobi_scheme scheme,        \
-        const I* block_ptrs, const T* blocks, const T* alpha, const T* b, int64_t ldb, const T* beta,   \
-        T* x, int64_t ldx, int64_t nrhs)                                                                \
-    {                                                                                                   \
-        (void)max_block_size;                                                                           \
-        GKOC_REQUIRE(alpha && beta, GKOC_E_INVALID, "null alpha / beta");                               \
-        return launch_apply_simple<T, I, true>(s, num_blocks, scheme, block_ptrs, blocks, alpha, b,     \
-                                               ldb, beta, x, ldx, nrhs);                                \
-    }
-GKOC_DEF_CJACOBI(gkoc_c128, c128, int32_t, i32)
-GKOC_DEF_CJACOBI(gkoc_c128, c128, int64_t, i64)
-GKOC_DEF_CJACOBI(gkoc_c64, c64, int32_t, i32)
-GKOC_DEF_CJACOBI(gkoc_c64, c64, int64_t, i64)
-
-#define GKOC_DEF_JACOBI(T, TN, I, IN)                                          \
-    extern "C" int gkoc_jacobi_find_blocks_##TN##_##IN(                        \
-        gkoc_stream_t s, int64_t n_rows, const I* row_ptrs,                    \
-        const I* col_idxs, uint32_t max_block_size,                            \
-        int64_t* num_blocks_host, I* block_ptrs)                               \
-    {                                                                          \
-        return find_blocks_impl<I>(s, n_rows, row_ptrs, col_idxs,              \
-                                   max_block_size, num_blocks_host,            \
-                                   block_ptrs);                                \
-    }                                                                          \
-    extern "C" int gkoc_jacobi_generate_##TN##_##IN(                           \
-        gkoc_stream_t s, int64_t n_rows, const I* row_ptrs,                    \
-        const I* col_idxs, const T* vals, int64_t num_blocks,                  \
-        uint32_t max_block_size, gkoc_jacobi_scheme scheme,                    \
-        const I* block_ptrs, T* blocks, T* conditioning)                       \
-    {                                                                          \
-        (void)n_rows;                                                          \
-        GKOC_REQUIRE(conditioning == nullptr, GKOC_E_NOT_SUPPORTED,            \
-                     "adaptive-precision block-Jacobi is not supported");      \
-        return launch_generate<T, I>(s, row_ptrs, col_idxs, vals, num_blocks,  \
-                                     max_block_size, scheme, block_ptrs,       \
-                                     blocks);                                  \
-    }                                                                          \
-    extern "C" int gkoc_jacobi_simple_apply_##TN##_##IN(                       \
-        gkoc_stream_t s, int64_t num_blocks, uint32_t max_block_size,          \
-        gkoc_jacobi_scheme scheme, const I* block_ptrs, const T* blocks,       \
-        const T* b, int64_t ldb, T* x, int64_t ldx, int64_t nrhs)              \
-    {                                                                          \
-        return launch_apply<T, I, false>(s, num_blocks, max_block_size,        \
-                                         scheme, block_ptrs, blocks, nullptr,  \
-                                         b, ldb, nullptr, x, ldx, nrhs);       \
-    }                                                                          \
-    extern "C" int gkoc_x_jacobi_simple_apply_dot_##TN##_##IN(                 \
-        gkoc_stream_t s, int64_t num_blocks, int64_t n_rows,                   \
-        uint32_t max_block_size, gkoc_jacobi_scheme scheme,                    \
-        const I* block_ptrs, const T* blocks, const T* b, T* x, T* dot_out,    \
-        void* work, size_t work_bytes)                                         \
-    {                                                                          \
-        return launch_apply_dot<T, I>(s, num_blocks, n_rows, max_block_size,   \
-                                      scheme, block_ptrs, blocks, b, x,        \
-                                      dot_out, work, work_bytes);              \
-    }                                                                          \
-    extern "C" int gkoc_x_cg_step_2_jacobi_apply_##TN##_##IN(                  \
-        gkoc_stream_t s, int64_t num_blocks, int64_t n_rows,                   \
-        uint32_t max_block_size, gkoc_jacobi_scheme scheme,                    \
-        const I* block_ptrs, const T* blocks, T* x, T* r, const T* p,          \
-        const T* q, const T* beta, const T* rho, const uint8_t* stop_status,   \
-        T* z, T* rho_out, T* norm_out, int take_sqrt, void* work,              \
-        size_t work_bytes)                                                     \
-    {                                                                          \
-        return launch_step2_apply<T, I>(s, num_blocks, n_rows, max_block_size, \
-                                        scheme, block_ptrs, blocks, x, r, p,   \
-                                        q, beta, rho, stop_status, z, rho_out, \
-                                        norm_out, take_sqrt, work, work_bytes); \
-    }                                                                          \
-    extern "C" int gkoc_x_pipe_cg_steps_jacobi_##TN##_##IN(                    \
-        gkoc_stream_t s, int64_t num_blocks, int64_t n_rows,                   \
-        uint32_t max_block_size, gkoc_jacobi_scheme scheme,                    \
-        const I* block_ptrs, const T* blocks, T* x, T* r, T* z, T* w, T* p,    \
-        T* q, T* f, T* g, T* m, const T* n, const T* prev_rho, const T* rho,   \
-        const T* delta, const T* beta_in, T* beta_out,                         \
-        const uint8_t* stop_status, T* out3, void* work, size_t work_bytes,    \
-        const gkoc_step_gate* gate)                                            \
-    {                                                                          \
-        return launch_pipe_steps<T, I>(s, num_blocks, n_rows, max_block_size,  \
-                                       scheme, block_ptrs, blocks, x, r, z, w, \
-                                       p, q, f, g, m, n, prev_rho, rho, delta, \
-                                       beta_in, beta_out, stop_status, out3,   \
-                                       work, work_bytes, gate);                \
-    }                                                                          \
-    extern "C" int gkoc_jacobi_apply_##TN##_##IN(                              \
-        gkoc_stream_t s, int64_t num_blocks, uint32_t max_block_size,          \
-        gkoc_jacobi_scheme scheme, const I* block_ptrs, const T* blocks,       \
-        const T* alpha, const T* b, int64_t ldb, const T* beta, T* x,          \
-        int64_t ldx, int64_t nrhs)                                             \
-    {                                                                          \
-        GKOC_REQUIRE(alpha && beta, GKOC_E_INVALID, "null alpha/beta");        \
-        return launch_apply<T, I, true>(s, num_blocks, max_block_size, scheme, \
-                                        block_ptrs, blocks, alpha, b, ldb,     \
-                                        beta, x, ldx, nrhs);                   \
-    }
-
-extern "C" int gkoc_x_cg_step_2_jacobi_apply_fits(int64_t num_blocks, int64_t n_rows,
-                                                  gkoc_jacobi_scheme scheme, size_t value_size)
-{
-    return gkoc::step2_apply_fits(num_blocks, n_rows, scheme, value_size) ? 1 : 0;
-}
-
-namespace gkoc {
-namespace {
-__global__ void tile_bytes_kernel(int64_t n, const uint8_t* __restrict__ src, int64_t src_n,
-                                  uint8_t* __restrict__ dst)
-{
-    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
-    for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
-        dst[i] = src[i % src_n];
-    }
-}
-}  // namespace
-}  // namespace gkoc
-
-namespace gkoc {
-namespace {
-// jacobi::transpose_jacobi / conj_transpose_jacobi for real types
-// (reference/preconditioner/jacobi_kernels.cpp:597-627): every stored block is
-// transposed in place of its group, in its own storage type (the entries are moved as
-// raw words of the type's width, so no rounding takes place).
-template <typename T, typename I>
-__global__ __launch_bounds__(256) void jacobi_transpose_kernel(
-    int64_t num_blocks, gkoc_jacobi_scheme scheme, const I* __restrict__ block_ptrs,
-    const T* __restrict__ blocks, const uint8_t* __restrict__ precs, T* __restrict__ out)
-{
-    const int64_t bo = scheme.block_offset;
-    const int64_t stride = bo << scheme.group_power;
-    const int64_t gmask = (int64_t(1) << scheme.group_power) - 1;
-    const int64_t total = num_blocks * bo;
-    const int64_t step = int64_t(gridDim.x) * 256;
-    for (int64_t t = int64_t(blockIdx.x) * 256 + threadIdx.x; t < total; t += step) {
-        const int64_t blk = t / bo;
-        const int r = int(t - blk * bo);
-        const int bs = int(block_ptrs[blk + 1] - block_ptrs[blk]);
-        if (r >= bs) continue;
-        const int64_t goff = scheme.group_offset * (blk >> scheme.group_power);
-        const int64_t boff = bo * (blk & gmask);
-        const int prec = precs ? int(precs[blk]) : 0;
-        const int width = prec == 0 ? int(sizeof(T)) : (prec == 0x01 || prec == 0x10) ? 4 : 2;
-        const unsigned char* src = reinterpret_cast<const unsigned char*>(blocks + goff);
-        unsigned char* dst = reinterpret_cast<unsigned char*>(out + goff);
-        for (int c = 0; c < bs; ++c) {
-            // out(r, c) = in(c, r)
-            const int64_t from = (boff + c + int64_t(r) * stride) * width;
-            const int64_t to = (boff + r + int64_t(c) * stride) * width;
-            for (int k = 0; k < width; ++k) dst[to + k] = src[from + k];
-        }
-    }
-}
-}  // namespace
-}  // namespace gkoc
-
-#define GKOC_DEF_JACOBI_TRANSPOSE(T, TN, I, IN)                                             \
-    extern "C" int gkoc_jacobi_transpose_##TN##_##IN(                                       \
-        gkoc_stream_t s, int64_t num_blocks, uint32_t max_block_size,                       \
-        gkoc_jacobi_scheme scheme, const I* block_ptrs, const T* blocks,                    \
-        const uint8_t* precisions, T* out_blocks)                                           \
-    {                                                                                       \
-        (void)max_block_size;                                                               \
-        if (num_blocks <= 0) return GKOC_OK;                                                \
-        GKOC_REQUIRE(block_ptrs && blocks && out_blocks, GKOC_E_INVALID, "null pointer");   \
-        GKOC_REQUIRE(scheme.block_offset >= 1, GKOC_E_INVALID, "bad storage scheme");       \
-        GKOC_REQUIRE(precisions == nullptr || sizeof(T) == 8, GKOC_E_NOT_SUPPORTED,         \
-                     "reduced float blocks: gkoc_jacobi_transpose_adaptive_f32_*");         \
-        int64_t nb = ceildiv(num_blocks * scheme.block_offset, 256);                        \
-        if (nb > 4 * max_stream_blocks) nb = 4 * max_stream_blocks;                         \
-        jacobi_transpose_kernel<T, I><<<dim3(unsigned(nb)), dim3(256), 0, as_stream(s)>>>(  \
-            num_blocks, scheme, block_ptrs, blocks, precisions, out_blocks);                \
-        GKOC_LAUNCH_OK();                                                                   \
-        return GKOC_OK;                                                                     \
-    }
-GKOC_DEF_JACOBI_TRANSPOSE(double, f64, int32_t, i32)
-GKOC_DEF_JACOBI_TRANSPOSE(double, f64, int64_t, i64)
-GKOC_DEF_JACOBI_TRANSPOSE(float, f32, int32_t, i32)
-GKOC_DEF_JACOBI_TRANSPOSE(float, f32, int64_t, i64)
-
-// ... and for complex values (uniform storage): conj != 0 conjugates the moved entries
-// (conj_transpose_jacobi, reference/preconditioner/jacobi_kernels.cpp:613-627)
-namespace gkoc {
-namespace {
-template <typename T, typename I>
-__global__ __launch_bounds__(256) void cjacobi_transpose_kernel(int64_t num_blocks, gkoc_jacobi_scheme scheme,
-                                                                const I* __restrict__ block_ptrs,
-                                                                const T* __restrict__ blocks, int conj,
-                                                                T* __restrict__ out)
-{
-    const int64_t bo = scheme.block_offset;
-    const int64_t stride = bo << scheme.group_power;
-    const int64_t gmask = (int64_t(1) << scheme.group_power) - 1;
-    const int64_t total = num_blocks * bo;
-    const int64_t step = int64_t(gridDim.x) * 256;
-    for (int64_t t = int64_t(blockIdx.x) * 256 + threadIdx.x; t < total; t += step) {
-        const int64_t blk = t / bo;
-        const int r = int(t - blk * bo);
-        const int bs = int(block_ptrs[blk + 1] - block_ptrs[blk]);
-        if (r >= bs) continue;
-        const int64_t base = scheme.group_offset * (blk >> scheme.group_power) + bo * (blk & gmask);
-        for (int c = 0; c < bs; ++c) {
-            T v = blocks[base + c + int64_t(r) * stride];      // in(c, r)
-            if (conj) v = conj_v(v);
-            out[base + r + int64_t(c) * stride] = v;           // out(r, c)
-        }
-    }
-}
-}  // namespace
-}  // namespace gkoc
-
-#define GKOC_DEF_CJACOBI_TRANSPOSE(T, TN, I, IN)                                                        \
-    extern "C" int gkoc_cjacobi_transpose_##TN##_##IN(gkoc_stream_t s, int64_t num_blocks,              \
-                                                      gkoc_jacobi_scheme scheme, const I* block_ptrs,   \
-                                                      const T* blocks, int conj, T* out_blocks)         \
-    {                                                                                                   \
-        if (num_blocks <= 0) return GKOC_OK;                                                            \
-        GKOC_REQUIRE(block_ptrs && blocks && out_blocks, GKOC_E_INVALID, "null pointer");               \
-        GKOC_REQUIRE(scheme.block_offset >= 1, GKOC_E_INVALID, "bad storage scheme");                   \
-        int64_t nb = ceildiv(num_blocks * scheme.block_offset, 256);                                    \
-        if (nb > 4 * max_stream_blocks) nb = 4 * max_stream_blocks;                                     \
-        cjacobi_transpose_kernel<T, I><<<dim3(unsigned(nb)), dim3(256), 0, as_stream(s)>>>(             \
-            num_blocks, scheme, block_ptrs, blocks, conj, out_blocks);                                  \
-        GKOC_LAUNCH_OK();                                                                               \
-        return GKOC_OK;                                                                                 \
-    }
-GKOC_DEF_CJACOBI_TRANSPOSE(gkoc_c128, c128, int32_t, i32)
-GKOC_DEF_CJACOBI_TRANSPOSE(gkoc_c128, c128, int64_t, i64)
-GKOC_DEF_CJACOBI_TRANSPOSE(gkoc_c64, c64, int32_t, i32)
-GKOC_DEF_CJACOBI_TRANSPOSE(gkoc_c64, c64, int64_t, i64)
-
-// jacobi::initialize_precisions (reference/preconditioner/jacobi_kernels.cpp:454-462)
-extern "C" int gkoc_jacobi_initialize_precisions(gkoc_stream_t s, const uint8_t* source,
-                                                 int64_t source_size, uint8_t* precisions,
-                                                 int64_t n)
-{
-    GKOC_REQUIRE(n >= 0 && source_size >= 0, GKOC_E_INVALID, "negative size");
-    if (n == 0) return GKOC_OK;
-    GKOC_REQUIRE(source && precisions && source_size > 0, GKOC_E_INVALID, "bad argument");
-    int64_t nb = ceildiv(n, 256);
-    if (nb > max_stream_blocks) nb = max_stream_blocks;
-    tile_bytes_kernel<<<dim3(unsigned(nb)), dim3(256), 0, as_stream(s)>>>(n, source, source_size,
-                                                                         precisions);
-    GKOC_LAUNCH_OK();
-    return GKOC_OK;
-}
-
-namespace gkoc {
-namespace {
-
-inline bool wide_group_layout(const gkoc_jacobi_scheme& sc)
-{
-    const int64_t bo = sc.block_offset;
-    return bo >= 1 && bo <= 16 && (bo & (bo - 1)) == 0 && (bo << sc.group_power) == 64;
-}
-
-// lanes per block = the power of two at or above block_offset
-// (Jacobi::compute_storage_scheme, include/ginkgo/core/preconditioner/jacobi.hpp: a group holds
-// max_block_stride / that power blocks; max_block_stride = 64 on this device)
-inline int subwarp_of(const gkoc_jacobi_scheme& sc)
-{
-    int sub = 1;
-    while (sub < sc.block_offset) sub <<= 1;
-    return sub;
-}
-
-inline bool wave_group_layout(const gkoc_jacobi_scheme& sc)
-{
-    return sc.block_offset >= 1 && sc.block_offset <= 32 &&
-           (int64_t(subwarp_of(sc)) << sc.group_power) == 64;
-}
-
-template <typename I>
-int launch_generate_adaptive(gkoc_stream_t s, const I* row_ptrs, const I* cols, const double* vals,
-                             int64_t num_blocks, uint32_t max_bs, gkoc_jacobi_scheme scheme,
-                             const I* block_ptrs, double accuracy, uint8_t* precisions,
-                             double* conditioning, double* blocks)
-{
-    if (num_blocks <= 0) return GKOC_OK;
-    GKOC_REQUIRE(row_ptrs && cols && vals && block_ptrs && precisions && blocks, GKOC_E_INVALID,
-                 "null pointer");
-    GKOC_REQUIRE(wave_group_layout(scheme) && max_bs >= 1 && max_bs <= uint64_t(scheme.block_offset),
-                 GKOC_E_NOT_SUPPORTED,
-                 "adaptive block-Jacobi needs max_block_size <= 32 and groups that fill a wavefront "
-                 "(max_block_stride 64)");
-    const int sub = subwarp_of(scheme);
-    const int per_wave = 64 / sub;
-    const size_t lds = 2 * size_t(per_wave) * sub * (sub + 1) * sizeof(double);
-    jacobi_generate_adaptive_kernel<I>
-        <<<dim3(unsigned(ceildiv(num_blocks, per_wave))), dim3(64), lds, as_stream(s)>>>(
-            row_ptrs, cols, vals, num_blocks, sub, scheme, block_ptrs, accuracy, precisions,
-            conditioning, blocks);
-    GKOC_LAUNCH_OK();
     return GKOC_OK;
 }
 
@@ -2016,370 +1790,29 @@ int launch_apply_adaptive(gkoc_stream_t s, int64_t num_blocks, uint32_t max_bs,
         return GKOC_OK;
     }
     const int64_t go = scheme.group_offset;
-#define GKOC_JAC_AD(BO_)                                                                    \
-    launch_apply_adaptive_fixed<I, ADV, BO_>(s, num_blocks, groups, go, block_ptrs, blocks, \
-                                             precisions, alpha, b, beta, x)
-    switch (int(scheme.block_offset)) {
-    case 1: GKOC_JAC_AD(1); break;
-    case 2: GKOC_JAC_AD(2); break;
-    case 4: GKOC_JAC_AD(4); break;
-    case 8: GKOC_JAC_AD(8); break;
-    default: GKOC_JAC_AD(16); break;
-    }
-#undef GKOC_JAC_AD
+    with_block_offset(scheme.block_offset, [&](auto bc) {
+        launch_apply_adaptive_fixed<I, ADV, decltype(bc)::value>(s, num_blocks, groups, go, block_ptrs, blocks,
+                                                                 precisions, alpha, b, beta, x);
+    });
     GKOC_LAUNCH_OK();
     return GKOC_OK;
 }
 
-}  // namespace
-}  // namespace gkoc
-
-#define GKOC_DEF_JACOBI_ADAPTIVE(I, IN)                                                      \
-    extern "C" int gkoc_jacobi_generate_adaptive_f64_##IN(                                   \
-        gkoc_stream_t s, int64_t n_rows, const I* row_ptrs, const I* col_idxs,               \
-        const double* vals, int64_t num_blocks, uint32_t max_block_size,                     \
-        gkoc_jacobi_scheme scheme, const I* block_ptrs, double accuracy,                     \
-        uint8_t* precisions, double* conditioning, double* blocks)                           \
-    {                                                                                        \
-        (void)n_rows;                                                                        \
-        return launch_generate_adaptive<I>(s, row_ptrs, col_idxs, vals, num_blocks,          \
-                                           max_block_size, scheme, block_ptrs, accuracy,     \
-                                           precisions, conditioning, blocks);                \
-    }                                                                                        \
-    extern "C" int gkoc_jacobi_apply_adaptive_f64_##IN(                                      \
-        gkoc_stream_t s, int64_t num_blocks, uint32_t max_block_size,                        \
-        gkoc_jacobi_scheme scheme, const I* block_ptrs, const double* blocks,                \
-        const uint8_t* precisions, const double* alpha, const double* b, int64_t ldb,        \
-        const double* beta, double* x, int64_t ldx, int64_t nrhs)                            \
-    {                                                                                        \
-        GKOC_REQUIRE((alpha == nullptr) == (beta == nullptr), GKOC_E_INVALID,                \
-                     "pass alpha and beta, or neither");                                     \
-        if (alpha) {                                                                         \
-            return launch_apply_adaptive<I, true>(s, num_blocks, max_block_size, scheme,     \
-                                                  block_ptrs, blocks, precisions, alpha, b,  \
-                                                  ldb, beta, x, ldx, nrhs);                  \
-        }                                                                                    \
-        return launch_apply_adaptive<I, false>(s, num_blocks, max_block_size, scheme,        \
-                                               block_ptrs, blocks, precisions, nullptr, b,   \
-                                               ldb, nullptr, x, ldx, nrhs);                  \
-    }
-GKOC_DEF_JACOBI_ADAPTIVE(int32_t, i32)
-GKOC_DEF_JACOBI_ADAPTIVE(int64_t, i64)
-
-// reduced-precision storage: value type double only
-extern "C" int gkoc_jacobi_convert_storage_f64(gkoc_stream_t s, int64_t num_blocks,
-                                               gkoc_jacobi_scheme scheme, double* blocks,
-                                               uint8_t precision)
-{
-    return launch_convert_storage(s, num_blocks, scheme, blocks, int(precision));
-}
-
-#define GKOC_DEF_JACOBI_STORED(I, IN)                                                        \
-    extern "C" int gkoc_jacobi_apply_stored_f64_##IN(                                        \
-        gkoc_stream_t s, int64_t num_blocks, uint32_t max_block_size,                        \
-        gkoc_jacobi_scheme scheme, const I* block_ptrs, const double* blocks,                \
-        uint8_t precision, const double* alpha, const double* b, int64_t ldb,                \
-        const double* beta, double* x, int64_t ldx, int64_t nrhs)                            \
-    {                                                                                        \
-        GKOC_REQUIRE((alpha == nullptr) == (beta == nullptr), GKOC_E_INVALID,                \
-                     "pass alpha and beta, or neither");                                     \
-        if (alpha) {                                                                         \
-            return launch_apply_stored<I, true>(s, num_blocks, max_block_size, scheme,       \
-                                                block_ptrs, blocks, int(precision), alpha,   \
-                                                b, ldb, beta, x, ldx, nrhs);                 \
-        }                                                                                    \
-        return launch_apply_stored<I, false>(s, num_blocks, max_block_size, scheme,          \
-                                             block_ptrs, blocks, int(precision), nullptr, b, \
-                                             ldb, nullptr, x, ldx, nrhs);                    \
-    }
-GKOC_DEF_JACOBI_STORED(int32_t, i32)
-GKOC_DEF_JACOBI_STORED(int64_t, i64)
-
-GKOC_DEF_JACOBI(double, f64, int32_t, i32)
-GKOC_DEF_JACOBI(double, f64, int64_t, i64)
-GKOC_DEF_JACOBI(float, f32, int32_t, i32)
-GKOC_DEF_JACOBI(float, f32, int64_t, i64)
-
-// =========================================================================================
-// Adaptive / block-wise storage precision for the value types float, complex<float> and
-// complex<double> (VT instantiations of jacobi::generate / apply / transpose the reference
-// compiles for every value type, core/preconditioner/jacobi_kernels.hpp:30-103).  A path of its
-// own: the double kernels above stay as tuned.  The rules are the reference's, per component type
-// R = remove_complex<T> (core/preconditioner/jacobi_utils.hpp:104-176, include/ginkgo/core/base/
-// math.hpp:365-383, :546-582):
-//   R = double: the five reduced types of the double path (float, half, the upper 32 / 16 bits of
-//               the double, the upper 16 bits of the float);
-//   R = float:  reduce_precision<float> = half and nothing below it, truncate_type<float> = the
-//               upper 16 bits and nothing below them, so the five precision_reduction values fall
-//               on two 16-bit types: (0,1) (0,2) (1,1) -> half, (1,0) (2,0) -> upper 16 bits.
-// A complex value is stored as its two parts in the reduced type.  One wave per storage group;
-// any group size of a 64-wide scheme (max_block_size <= 32).
-namespace gkoc {
-namespace {
-
-template <typename T>
-struct is_cplx {
-    static constexpr bool value = false;
-};
-template <typename R>
-struct is_cplx<gkoc_cplx<R>> {
-    static constexpr bool value = true;
-};
-
-// precision_reduction byte -> storage kind in the codes of stored<> (0 = the value type itself)
-template <typename R>
-__host__ __device__ __forceinline__ int storage_kind(int p);
-template <>
-__host__ __device__ __forceinline__ int storage_kind<double>(int p)
-{
-    return (p == 0x01 || p == 0x02 || p == 0x10 || p == 0x11 || p == 0x20) ? p : 0;
-}
-template <>
-__host__ __device__ __forceinline__ int storage_kind<float>(int p)
-{
-    return (p == 0x01 || p == 0x02 || p == 0x11) ? 0x02 : (p == 0x10 || p == 0x20) ? 0x11 : 0;
-}
-
-template <typename R>
-__device__ __forceinline__ R load_part(int kind, const void* group, int64_t i)
-{
-    if (kind == 0) return reinterpret_cast<const R*>(group)[i];
-    return R(load_stored(kind, reinterpret_cast<const double*>(group), i));
-}
-template <typename R>
-__device__ __forceinline__ void store_part(int kind, void* group, int64_t i, R v)
-{
-    if (kind == 0) {
-        reinterpret_cast<R*>(group)[i] = v;
-    } else {
-        store_stored(kind, reinterpret_cast<double*>(group), i, double(v));
-    }
-}
-template <typename R>
-__device__ __forceinline__ R round_part(int kind, R v)
-{
-    switch (kind) {
-    case 0x01: return R(stored<0x01>::load(stored<0x01>::store(double(v))));
-    case 0x02: return R(stored<0x02>::load(stored<0x02>::store(double(v))));
-    case 0x10: return R(stored<0x10>::load(stored<0x10>::store(double(v))));
-    case 0x11: return R(stored<0x11>::load(stored<0x11>::store(double(v))));
-    case 0x20: return R(stored<0x20>::load(stored<0x20>::store(double(v))));
-    default: return v;
-    }
-}
-
-template <typename R>
-__device__ __forceinline__ R load_value(int kind, const R* group, int64_t idx)
-{
-    return load_part<R>(kind, group, idx);
-}
-template <typename R>
-__device__ __forceinline__ gkoc_cplx<R> load_value(int kind, const gkoc_cplx<R>* group, int64_t idx)
-{
-    return {load_part<R>(kind, group, 2 * idx), load_part<R>(kind, group, 2 * idx + 1)};
-}
-template <typename R>
-__device__ __forceinline__ void store_value(int kind, R* group, int64_t idx, R v)
-{
-    store_part<R>(kind, group, idx, v);
-}
-template <typename R>
-__device__ __forceinline__ void store_value(int kind, gkoc_cplx<R>* group, int64_t idx, gkoc_cplx<R> v)
-{
-    store_part<R>(kind, group, 2 * idx, v.re);
-    store_part<R>(kind, group, 2 * idx + 1, v.im);
-}
-template <typename R>
-__device__ __forceinline__ R round_value(int kind, R v)
-{
-    return round_part<R>(kind, v);
-}
-template <typename R>
-__device__ __forceinline__ gkoc_cplx<R> round_value(int kind, gkoc_cplx<R> v)
-{
-    return {round_part<R>(kind, v.re), round_part<R>(kind, v.im)};
-}
-
-// the unit round-offs get_supported_storage_reductions compares with (jacobi_utils.hpp:118-146;
-// float_traits<>::eps, core/base/extended_float.hpp): p2n0, p1n1, p0n2, p1n0, p0n1, the value
-// type's own, and the storage kinds the two verificators round to
-template <typename R>
-struct reduction_rules;
-template <>
-struct reduction_rules<double> {
-    static constexpr double p2n0 = 1.0 / 16, p1n1 = 1.0 / 128, p0n2 = 1.0 / 2048, p1n0 = 1.0 / 1048576,
-                            p0n1 = 1.0 / 16777216, own = 1.0 / 9007199254740992.0;
-    static constexpr int verify1 = 0x01, verify2 = 0x02;
-};
-template <>
-struct reduction_rules<float> {
-    static constexpr float p2n0 = 1.0f / 128, p1n1 = 1.0f / 2048, p0n2 = 1.0f / 2048, p1n0 = 1.0f / 128,
-                           p0n1 = 1.0f / 2048, own = 1.0f / 16777216;
-    static constexpr int verify1 = 0x02, verify2 = 0x02;
-};
-
-// compute_inf_norm as block_norm_lds above, any value type (|z| of a complex entry)
-template <typename T>
-__device__ __forceinline__ real_t<T> block_norm_any(const T* Bm, int ld, int bs, int r, int sub)
-{
-    using R = real_t<T>;
-    R t = R(0);
-    if (r < bs) {
-        for (int j = 0; j < bs; ++j) t += abs_v(Bm[j * ld + r]);
-    }
-    for (int off = 1; off < sub; off <<= 1) {
-        const R o = __shfl_xor(t, off, 64);
-        t = o > t ? o : t;
-    }
-    return t;
-}
-
-// validate_precision_reduction_feasibility (reference :280-307) for a storage kind
-template <typename T>
-__device__ __forceinline__ bool feasible_any(int kind, const T* Bm, T* Tm, int ld, int bs, int r, int g,
-                                             int sub, int max_bs)
-{
-    using R = real_t<T>;
-    if (r < bs) {
-        for (int j = 0; j < bs; ++j) Tm[r * ld + j] = round_value(kind, Bm[r * ld + j]);
-    }
-    wave_lds_sync();
-    R cond = block_norm_any<T>(Tm, ld, bs, r, sub);
-    int perm = r;
-    const bool ok = gauss_jordan_lds<T>(Tm, ld, bs, r, g, sub, max_bs, perm);
-    cond *= block_norm_any<T>(Tm, ld, bs, r, sub);
-    wave_lds_sync();
-    return ok && cond >= R(1) && cond * reduction_rules<R>::own < R(1e-3);
-}
-
-// dynamic LDS: 2 * (64/SUB) * SUB * ld values
-template <typename T, typename I>
-__global__ __launch_bounds__(64) void jacobi_generate_adaptive_any_kernel(
-    const I* __restrict__ row_ptrs, const I* __restrict__ cols, const T* __restrict__ vals,
-    int64_t num_blocks, int sub, int ld, gkoc_jacobi_scheme scheme, const I* __restrict__ block_ptrs,
-    real_t<T> accuracy, uint8_t* __restrict__ precisions, real_t<T>* __restrict__ conditioning,
-    T* __restrict__ blocks)
-{
-    using R = real_t<T>;
-    using rules = reduction_rules<R>;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    T* lds = reinterpret_cast<T*>(lds_raw);
-    const int lane = threadIdx.x;
-    const int per_wave = 64 / sub;
-    const int g = lane / sub;
-    const int r = lane % sub;
-    T* Bm = lds + int64_t(g) * sub * ld;
-    T* Tm = lds + int64_t(per_wave) * sub * ld + int64_t(g) * sub * ld;
-    const int64_t blk = int64_t(blockIdx.x) * per_wave + g;
-    int64_t start = 0;
-    int bs = 0;
-    if (blk < num_blocks) {
-        start = block_ptrs[blk];
-        bs = int(block_ptrs[blk + 1] - start);
-    }
-    if (r < bs) {
-        for (int j = 0; j < bs; ++j) Bm[r * ld + j] = T(0);
-        const int64_t a = row_ptrs[start + r], e = row_ptrs[start + r + 1];
-        for (int64_t k = a; k < e; ++k) {
-            const int64_t c = int64_t(cols[k]) - start;
-            if (c >= 0 && c < bs) Bm[r * ld + c] = vals[k];
-        }
-    }
-    const int max_bs = wave_max(bs);
-    wave_lds_sync();
-    R cond = block_norm_any<T>(Bm, ld, bs, r, sub);
-    int perm = r;
-    gauss_jordan_lds<T>(Bm, ld, bs, r, g, sub, max_bs, perm);
-    cond *= block_norm_any<T>(Bm, ld, bs, r, sub);
-    // autodetect needs the condition numbers (reference :347: "... && cond"): without the array the
-    // request reads as "keep the value type"
-    int request = blk < num_blocks ? int(precisions[blk]) : -1;
-    if (request == 0xff && conditioning == nullptr) request = 0;
-    uint32_t desc = 0xffffffffu;
-    const bool any_auto = __ballot(request == 0xff) != 0;
-    bool v1 = false, v2 = false;
-    if (any_auto) {
-        v1 = feasible_any<T>(rules::verify1, Bm, Tm, ld, bs, r, g, sub, max_bs);
-        v2 = rules::verify2 == rules::verify1
-                 ? v1
-                 : feasible_any<T>(rules::verify2, Bm, Tm, ld, bs, r, g, sub, max_bs);
-    }
-    if (request == 0xff) {
-        int verified1 = 2;
-        desc = 0;
-        if (cond * rules::p2n0 < accuracy) desc |= 0x04;
-        if (cond * rules::p1n1 < accuracy) {
-            verified1 = v1 ? 1 : 0;
-            if (v1) desc |= 0x02;
-        }
-        if (cond * rules::p0n2 < accuracy && verified1 != 0 && v2) desc |= 0x01;
-        if (cond * rules::p1n0 < accuracy) desc |= 0x10;
-        if (cond * rules::p0n1 < accuracy) {
-            if (verified1 == 2) verified1 = v1 ? 1 : 0;
-            if (verified1 == 1) desc |= 0x08;
-        }
-    } else if (request >= 0) {
-        desc = request == 0x01 ? 0x08u : request == 0x02 ? 0x01u : request == 0x10 ? 0x10u
-             : request == 0x11 ? 0x02u : request == 0x20 ? 0x04u : 0u;
-    }
-    for (int off = 1; off < 64; off <<= 1) desc &= __shfl_xor(desc, off, 64);
-    const int p = (desc & 0x01) ? 0x02 : (desc & 0x02) ? 0x11 : (desc & 0x04) ? 0x20
-                : (desc & 0x08) ? 0x01 : (desc & 0x10) ? 0x10 : 0x00;
-    if (blk < num_blocks && r == 0) {
-        precisions[blk] = uint8_t(p);
-        if (conditioning) conditioning[blk] = cond;
-    }
-    const int kind = storage_kind<R>(p);
-    const int64_t gsize = int64_t(1) << scheme.group_power;
-    const int64_t stride = scheme.block_offset << scheme.group_power;
-    T* group = blocks + scheme.group_offset * (blk >> scheme.group_power);
-    const int64_t boff = scheme.block_offset * (blk & (gsize - 1));
-    for (int j = 0; j < max_bs; ++j) {
-        const int pj = __shfl(perm, g * sub + j, 64);
-        if (r < bs && j < bs) store_value(kind, group, boff + r + int64_t(pj) * stride, Bm[r * ld + j]);
-    }
-}
-
-template <typename T, typename I>
-int launch_generate_adaptive_any(gkoc_stream_t s, const I* row_ptrs, const I* cols, const T* vals,
-                                 int64_t num_blocks, uint32_t max_bs, gkoc_jacobi_scheme scheme,
-                                 const I* block_ptrs, real_t<T> accuracy, uint8_t* precisions,
-                                 real_t<T>* conditioning, T* blocks)
-{
-    if (num_blocks <= 0) return GKOC_OK;
-    GKOC_REQUIRE(row_ptrs && cols && vals && block_ptrs && precisions && blocks, GKOC_E_INVALID,
-                 "null pointer");
-    GKOC_REQUIRE(wave_group_layout(scheme) && max_bs >= 1 && max_bs <= uint64_t(scheme.block_offset),
-                 GKOC_E_NOT_SUPPORTED,
-                 "adaptive block-Jacobi needs max_block_size <= 32 and groups that fill a wavefront "
-                 "(max_block_stride 64)");
-    const int sub = subwarp_of(scheme);
-    const int per_wave = 64 / sub;
-    // rows padded by one entry against bank conflicts where two blocks per lane group fit in 64 KB
-    int ld = sub + 1;
-    if (2 * size_t(per_wave) * sub * ld * sizeof(T) > 65536) ld = sub;
-    const size_t lds = 2 * size_t(per_wave) * sub * ld * sizeof(T);
-    jacobi_generate_adaptive_any_kernel<T, I>
-        <<<dim3(unsigned(ceildiv(num_blocks, per_wave))), dim3(64), lds, as_stream(s)>>>(
-            row_ptrs, cols, vals, num_blocks, sub, ld, scheme, block_ptrs, accuracy, precisions,
-            conditioning, blocks);
-    GKOC_LAUNCH_OK();
-    return GKOC_OK;
-}
-
-// ---- round 6: lane = (block, row) for every value type and storage precision -------------------------
-// The thread-per-row kernels above (jacobi_apply_simple_kernel, jacobi_apply_adaptive_any_kernel) need a
-// row -> block table (a pass of its own plus a device-to-host copy of the row count) and read the block with
-// one strided load per entry and lane: L256, block size 8: float adaptive 373 us = 13.5 % of 8 TB/s,
-// complex<double> adaptive 582 us = 23 %, complex<double> full storage 586 us = 57 %
-// (profiles/r06/r06_round5_additions.txt).  This is the scheme of jacobi_apply_fixed_kernel for them:
+// ------------------------------------------------------------ 4b. lane = (block, row), any value type
+// The value types without a tuned kernel (float with adaptive storage, complex<float>, complex<double>) in
+// full or adaptive storage.  This is the scheme of jacobi_apply_fixed_kernel for them:
 // one wave per storage group (GPW groups per wave), lane = (block, row) = the group's interleaved storage
 // order, so column c of all blocks of the group is ONE contiguous run (lane + c * stride) in whatever type
 // the group is stored in; the block's b values come from the block's other lanes by shuffle instead of
 // `bs` gathers per lane; all loads of a group are requested before the first use.  SUB = the lanes of a
 // block (the power of two at or above block_offset), so every 64-wide scheme is covered, block_offset 13
-// included.  Per (row, column) the operations and their order are those of the thread-per-row kernels:
+// included.  precisions == nullptr: full storage.  Per (row, column) the operations and their order are
+// those of the thread-per-row kernel below (jacobi_apply_rows_any_kernel):
 // sum = 0, sum += B(row, c) * b(c) for c = 0 .. bs-1, then alpha * sum (+ beta * x) - the same bits.
+// That kernel needs a row -> block table (a pass of its own plus a device-to-host copy of the row count) and
+// reads the block with one strided load per entry and lane: L256, block size 8: float adaptive 373 us =
+// 13.5 % of 8 TB/s against 105 us here, complex<double> adaptive 582 -> 234 us, complex<double> full storage
+// 586 -> 485 us (profiles/r06/r06_round5_additions.txt, r06_jacobi_lanes_kernel.txt).
 template <typename T, int KIND>
 struct entry_loader {
     using R = real_t<T>;
@@ -2544,10 +1977,26 @@ bool launch_apply_lanes_any(hipStream_t st, int64_t num_blocks, gkoc_jacobi_sche
     return true;
 }
 
-// x = M b / x = alpha M b + beta x, one thread per (row, right-hand side), blocks widened on load
-// (reference apply_block with the resolved precision, :425-470)
+// ------------------------------------------------------------ 4c. thread per row, any value type
+// What the lane kernel does not take (a scheme whose groups do not fill a wavefront, b == x) and
+// GKOC_TUNE_JACOBI_LANES = 1: one thread per (row, right-hand side) walks its row of the inverse block in
+// the interleaved scheme - element (r, c) of block b at group_offset * (b >> gp) + block_offset * (b & mask)
+// + r + c * stride (include/ginkgo/core/preconditioner/jacobi.hpp:37-140) - widens the entries on load
+// (precisions == nullptr: full storage) and adds the products in column order (reference apply_block with
+// the resolved precision, reference/preconditioner/jacobi_kernels.cpp:419-531).  row_block[row] = the block
+// of a row (filled by jacobi_row_block_kernel).
+template <typename I>
+__global__ __launch_bounds__(256) void jacobi_row_block_kernel(int64_t num_blocks,
+                                                              const I* __restrict__ block_ptrs,
+                                                              I* __restrict__ row_block)
+{
+    const int64_t b = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (b >= num_blocks) return;
+    for (I r = block_ptrs[b]; r < block_ptrs[b + 1]; ++r) row_block[r] = I(b);
+}
+
 template <typename T, typename I, bool ADV>
-__global__ __launch_bounds__(256) void jacobi_apply_adaptive_any_kernel(
+__global__ __launch_bounds__(256) void jacobi_apply_rows_any_kernel(
     int64_t n_rows, int64_t nrhs, gkoc_jacobi_scheme scheme, const I* __restrict__ block_ptrs,
     const I* __restrict__ row_block, const T* __restrict__ blocks,
     const uint8_t* __restrict__ precisions, const T* __restrict__ alpha_p, const T* __restrict__ b,
@@ -2579,10 +2028,9 @@ __global__ __launch_bounds__(256) void jacobi_apply_adaptive_any_kernel(
 }
 
 template <typename T, typename I, bool ADV>
-int launch_apply_adaptive_any(gkoc_stream_t s, int64_t num_blocks, gkoc_jacobi_scheme scheme,
-                              const I* block_ptrs, const T* blocks, const uint8_t* precisions,
-                              const T* alpha, const T* b, int64_t ldb, const T* beta, T* x, int64_t ldx,
-                              int64_t nrhs)
+int launch_apply_any(gkoc_stream_t s, int64_t num_blocks, gkoc_jacobi_scheme scheme, const I* block_ptrs,
+                     const T* blocks, const uint8_t* precisions, const T* alpha, const T* b, int64_t ldb,
+                     const T* beta, T* x, int64_t ldx, int64_t nrhs)
 {
     if (num_blocks <= 0 || nrhs <= 0) return GKOC_OK;
     GKOC_REQUIRE(block_ptrs && blocks && b && x, GKOC_E_INVALID, "null pointer");
@@ -2604,7 +2052,7 @@ int launch_apply_adaptive_any(gkoc_stream_t s, int64_t num_blocks, gkoc_jacobi_s
         num_blocks, block_ptrs, row_block);
     int64_t nb = ceildiv(n_rows * nrhs, 256);
     if (nb > 8 * max_stream_blocks) nb = 8 * max_stream_blocks;
-    jacobi_apply_adaptive_any_kernel<T, I, ADV><<<dim3(unsigned(nb)), dim3(256), 0, st>>>(
+    jacobi_apply_rows_any_kernel<T, I, ADV><<<dim3(unsigned(nb)), dim3(256), 0, st>>>(
         n_rows, nrhs, scheme, block_ptrs, row_block, blocks, precisions, alpha, b, ldb, beta, x, ldx);
     const hipError_t e = hipGetLastError();
     (void)scratch_free(st, row_block);
@@ -2612,7 +2060,46 @@ int launch_apply_adaptive_any(gkoc_stream_t s, int64_t num_blocks, gkoc_jacobi_s
     return GKOC_OK;
 }
 
-// out block = (conjugate) transpose of the block, in the storage type of its group
+// =========================================================================================
+// 5. Transposes
+// =========================================================================================
+// jacobi::transpose_jacobi / conj_transpose_jacobi for real types
+// (reference/preconditioner/jacobi_kernels.cpp:597-627): every stored block is
+// transposed in place of its group, in its own storage type (the entries are moved as
+// raw words of the type's width, so no rounding takes place).
+template <typename T, typename I>
+__global__ __launch_bounds__(256) void jacobi_transpose_kernel(
+    int64_t num_blocks, gkoc_jacobi_scheme scheme, const I* __restrict__ block_ptrs,
+    const T* __restrict__ blocks, const uint8_t* __restrict__ precs, T* __restrict__ out)
+{
+    const int64_t bo = scheme.block_offset;
+    const int64_t stride = bo << scheme.group_power;
+    const int64_t gmask = (int64_t(1) << scheme.group_power) - 1;
+    const int64_t total = num_blocks * bo;
+    const int64_t step = int64_t(gridDim.x) * 256;
+    for (int64_t t = int64_t(blockIdx.x) * 256 + threadIdx.x; t < total; t += step) {
+        const int64_t blk = t / bo;
+        const int r = int(t - blk * bo);
+        const int bs = int(block_ptrs[blk + 1] - block_ptrs[blk]);
+        if (r >= bs) continue;
+        const int64_t goff = scheme.group_offset * (blk >> scheme.group_power);
+        const int64_t boff = bo * (blk & gmask);
+        const int prec = precs ? int(precs[blk]) : 0;
+        const int width = prec == 0 ? int(sizeof(T)) : (prec == 0x01 || prec == 0x10) ? 4 : 2;
+        const unsigned char* src = reinterpret_cast<const unsigned char*>(blocks + goff);
+        unsigned char* dst = reinterpret_cast<unsigned char*>(out + goff);
+        for (int c = 0; c < bs; ++c) {
+            // out(r, c) = in(c, r)
+            const int64_t from = (boff + c + int64_t(r) * stride) * width;
+            const int64_t to = (boff + r + int64_t(c) * stride) * width;
+            for (int k = 0; k < width; ++k) dst[to + k] = src[from + k];
+        }
+    }
+}
+
+// float with adaptive storage and the complex types (full storage: precisions == nullptr):
+// out block = (conjugate) transpose of the block, in the storage type of its group; conj != 0
+// conjugates the moved entries
 // (reference transpose_jacobi / conj_transpose_jacobi, :528-600: the reduced values move as they are)
 template <typename T, typename I>
 __global__ __launch_bounds__(256) void jacobi_transpose_adaptive_any_kernel(
@@ -2648,9 +2135,9 @@ int launch_transpose_adaptive_any(gkoc_stream_t s, int64_t num_blocks, gkoc_jaco
 {
     if (num_blocks <= 0) return GKOC_OK;
     GKOC_REQUIRE(block_ptrs && blocks && out, GKOC_E_INVALID, "null pointer");
-    GKOC_REQUIRE(scheme.block_offset >= 1, GKOC_E_INVALID, "storage scheme");
+    GKOC_REQUIRE(scheme.block_offset >= 1, GKOC_E_INVALID, "bad storage scheme");
     int64_t nb = ceildiv(num_blocks * scheme.block_offset, 256);
-    if (nb > 8 * max_stream_blocks) nb = 8 * max_stream_blocks;
+    if (nb > 4 * max_stream_blocks) nb = 4 * max_stream_blocks;      // (a grid-stride loop)
     jacobi_transpose_adaptive_any_kernel<T, I><<<dim3(unsigned(nb)), dim3(256), 0, as_stream(s)>>>(
         num_blocks, scheme, block_ptrs, blocks, precisions, conj, out);
     GKOC_LAUNCH_OK();
@@ -2660,6 +2147,217 @@ int launch_transpose_adaptive_any(gkoc_stream_t s, int64_t num_blocks, gkoc_jaco
 }  // namespace
 }  // namespace gkoc
 
+using namespace gkoc;
+
+// =========================================================================================
+// 6. C ABI
+// =========================================================================================
+// find_blocks works on the indices only: one body for the four value types
+#define GKOC_DEF_JACOBI_FIND_BLOCKS(TN, I, IN)                                                          \
+    extern "C" int gkoc_jacobi_find_blocks_##TN##_##IN(gkoc_stream_t s, int64_t n_rows, const I* row_ptrs, \
+                                                       const I* col_idxs, uint32_t max_block_size,      \
+                                                       int64_t* num_blocks_host, I* block_ptrs)         \
+    {                                                                                                   \
+        return find_blocks_impl<I>(s, n_rows, row_ptrs, col_idxs, max_block_size, num_blocks_host,      \
+                                   block_ptrs);                                                         \
+    }
+#define GKOC_DEF_JACOBI_FIND_BLOCKS_BOTH(TN)         \
+    GKOC_DEF_JACOBI_FIND_BLOCKS(TN, int32_t, i32)    \
+    GKOC_DEF_JACOBI_FIND_BLOCKS(TN, int64_t, i64)
+GKOC_DEF_JACOBI_FIND_BLOCKS_BOTH(f64)
+GKOC_DEF_JACOBI_FIND_BLOCKS_BOTH(f32)
+GKOC_DEF_JACOBI_FIND_BLOCKS_BOTH(c128)
+GKOC_DEF_JACOBI_FIND_BLOCKS_BOTH(c64)
+
+// double and float, full storage: the tuned kernels
+#define GKOC_DEF_JACOBI(T, TN, I, IN)                                          \
+    extern "C" int gkoc_jacobi_generate_##TN##_##IN(                           \
+        gkoc_stream_t s, int64_t n_rows, const I* row_ptrs,                    \
+        const I* col_idxs, const T* vals, int64_t num_blocks,                  \
+        uint32_t max_block_size, gkoc_jacobi_scheme scheme,                    \
+        const I* block_ptrs, T* blocks, T* conditioning)                       \
+    {                                                                          \
+        (void)n_rows;                                                          \
+        GKOC_REQUIRE(conditioning == nullptr, GKOC_E_NOT_SUPPORTED,            \
+                     "adaptive-precision block-Jacobi is not supported");      \
+        return launch_generate<T, I>(s, row_ptrs, col_idxs, vals, num_blocks,  \
+                                     max_block_size, scheme, block_ptrs,       \
+                                     blocks);                                  \
+    }                                                                          \
+    extern "C" int gkoc_jacobi_simple_apply_##TN##_##IN(                       \
+        gkoc_stream_t s, int64_t num_blocks, uint32_t max_block_size,          \
+        gkoc_jacobi_scheme scheme, const I* block_ptrs, const T* blocks,       \
+        const T* b, int64_t ldb, T* x, int64_t ldx, int64_t nrhs)              \
+    {                                                                          \
+        return launch_apply<T, I, false>(s, num_blocks, max_block_size,        \
+                                         scheme, block_ptrs, blocks, nullptr,  \
+                                         b, ldb, nullptr, x, ldx, nrhs);       \
+    }                                                                          \
+    extern "C" int gkoc_x_jacobi_simple_apply_dot_##TN##_##IN(                 \
+        gkoc_stream_t s, int64_t num_blocks, int64_t n_rows,                   \
+        uint32_t max_block_size, gkoc_jacobi_scheme scheme,                    \
+        const I* block_ptrs, const T* blocks, const T* b, T* x, T* dot_out,    \
+        void* work, size_t work_bytes)                                         \
+    {                                                                          \
+        return launch_apply_dot<T, I>(s, num_blocks, n_rows, max_block_size,   \
+                                      scheme, block_ptrs, blocks, b, x,        \
+                                      dot_out, work, work_bytes);              \
+    }                                                                          \
+    extern "C" int gkoc_x_cg_step_2_jacobi_apply_##TN##_##IN(                  \
+        gkoc_stream_t s, int64_t num_blocks, int64_t n_rows,                   \
+        uint32_t max_block_size, gkoc_jacobi_scheme scheme,                    \
+        const I* block_ptrs, const T* blocks, T* x, T* r, const T* p,          \
+        const T* q, const T* beta, const T* rho, const uint8_t* stop_status,   \
+        T* z, T* rho_out, T* norm_out, int take_sqrt, void* work,              \
+        size_t work_bytes)                                                     \
+    {                                                                          \
+        return launch_step2_apply<T, I>(s, num_blocks, n_rows, max_block_size, \
+                                        scheme, block_ptrs, blocks, x, r, p,   \
+                                        q, beta, rho, stop_status, z, rho_out, \
+                                        norm_out, take_sqrt, work, work_bytes); \
+    }                                                                          \
+    extern "C" int gkoc_x_pipe_cg_steps_jacobi_##TN##_##IN(                    \
+        gkoc_stream_t s, int64_t num_blocks, int64_t n_rows,                   \
+        uint32_t max_block_size, gkoc_jacobi_scheme scheme,                    \
+        const I* block_ptrs, const T* blocks, T* x, T* r, T* z, T* w, T* p,    \
+        T* q, T* f, T* g, T* m, const T* n, const T* prev_rho, const T* rho,   \
+        const T* delta, const T* beta_in, T* beta_out,                         \
+        const uint8_t* stop_status, T* out3, void* work, size_t work_bytes,    \
+        const gkoc_step_gate* gate)                                            \
+    {                                                                          \
+        return launch_pipe_steps<T, I>(s, num_blocks, n_rows, max_block_size,  \
+                                       scheme, block_ptrs, blocks, x, r, z, w, \
+                                       p, q, f, g, m, n, prev_rho, rho, delta, \
+                                       beta_in, beta_out, stop_status, out3,   \
+                                       work, work_bytes, gate);                \
+    }                                                                          \
+    extern "C" int gkoc_jacobi_apply_##TN##_##IN(                              \
+        gkoc_stream_t s, int64_t num_blocks, uint32_t max_block_size,          \
+        gkoc_jacobi_scheme scheme, const I* block_ptrs, const T* blocks,       \
+        const T* alpha, const T* b, int64_t ldb, const T* beta, T* x,          \
+        int64_t ldx, int64_t nrhs)                                             \
+    {                                                                          \
+        GKOC_REQUIRE(alpha && beta, GKOC_E_INVALID, "null alpha/beta");        \
+        return launch_apply<T, I, true>(s, num_blocks, max_block_size, scheme, \
+                                        block_ptrs, blocks, alpha, b, ldb,     \
+                                        beta, x, ldx, nrhs);                   \
+    }
+GKOC_DEF_JACOBI(double, f64, int32_t, i32)
+GKOC_DEF_JACOBI(double, f64, int64_t, i64)
+GKOC_DEF_JACOBI(float, f32, int32_t, i32)
+GKOC_DEF_JACOBI(float, f32, int64_t, i64)
+
+extern "C" int gkoc_x_cg_step_2_jacobi_apply_fits(int64_t num_blocks, int64_t n_rows,
+                                                  gkoc_jacobi_scheme scheme, size_t value_size)
+{
+    return gkoc::step2_apply_fits(num_blocks, n_rows, scheme, value_size) ? 1 : 0;
+}
+
+// complex block-Jacobi, full storage: generate (the Gauss-Jordan kernel on gkoc_cplx: pivot by magnitude),
+// simple_apply / apply (the lane kernel, else thread per row).  Agrees with the reference to rounding.
+#define GKOC_DEF_CJACOBI(T, TN, I, IN)                                                                  \
+    extern "C" int gkoc_jacobi_generate_##TN##_##IN(                                                    \
+        gkoc_stream_t s, int64_t n_rows, const I* row_ptrs, const I* col_idxs, const T* vals,           \
+        int64_t num_blocks, uint32_t max_block_size, gkoc_jacobi_scheme scheme, const I* block_ptrs,    \
+        T* blocks, T* conditioning)                                                                     \
+    {                                                                                                   \
+        (void)n_rows;                                                                                   \
+        GKOC_REQUIRE(conditioning == nullptr, GKOC_E_NOT_SUPPORTED,                                     \
+                     "condition numbers: gkoc_jacobi_generate_adaptive_* computes them");               \
+        GKOC_REQUIRE(max_block_size <= 32, GKOC_E_NOT_SUPPORTED, "complex blocks: max_block_size <= 32"); \
+        return launch_generate<T, I>(s, row_ptrs, col_idxs, vals, num_blocks, max_block_size, scheme,   \
+                                     block_ptrs, blocks);                                               \
+    }                                                                                                   \
+    extern "C" int gkoc_jacobi_simple_apply_##TN##_##IN(                                                \
+        gkoc_stream_t s, int64_t num_blocks, uint32_t max_block_size, gkoc_jacobi_scheme scheme,        \
+        const I* block_ptrs, const T* blocks, const T* b, int64_t ldb, T* x, int64_t ldx, int64_t nrhs) \
+    {                                                                                                   \
+        (void)max_block_size;                                                                           \
+        return launch_apply_any<T, I, false>(s, num_blocks, scheme, block_ptrs, blocks,                 \
+                                             /* precisions: full storage */ nullptr, nullptr, b, ldb,   \
+                                             nullptr, x, ldx, nrhs);                                    \
+    }                                                                                                   \
+    extern "C" int gkoc_jacobi_apply_##TN##_##IN(                                                       \
+        gkoc_stream_t s, int64_t num_blocks, uint32_t max_block_size, gkoc_jacobi_scheme scheme,        \
+        const I* block_ptrs, const T* blocks, const T* alpha, const T* b, int64_t ldb, const T* beta,   \
+        T* x, int64_t ldx, int64_t nrhs)                                                                \
+    {                                                                                                   \
+        (void)max_block_size;                                                                           \
+        GKOC_REQUIRE(alpha && beta, GKOC_E_INVALID, "null alpha / beta");                               \
+        return launch_apply_any<T, I, true>(s, num_blocks, scheme, block_ptrs, blocks,                  \
+                                            /* precisions: full storage */ nullptr, alpha, b, ldb,      \
+                                            beta, x, ldx, nrhs);                                        \
+    }
+GKOC_DEF_CJACOBI(gkoc_c128, c128, int32_t, i32)
+GKOC_DEF_CJACOBI(gkoc_c128, c128, int64_t, i64)
+GKOC_DEF_CJACOBI(gkoc_c64, c64, int32_t, i32)
+GKOC_DEF_CJACOBI(gkoc_c64, c64, int64_t, i64)
+
+// adaptive storage, double: generate by the kernel of all value types (an autodetect request does not
+// need the conditioning array: AUTO_NEEDS_COND = false), apply by the tuned kernel
+#define GKOC_DEF_JACOBI_ADAPTIVE(I, IN)                                                      \
+    extern "C" int gkoc_jacobi_generate_adaptive_f64_##IN(                                   \
+        gkoc_stream_t s, int64_t n_rows, const I* row_ptrs, const I* col_idxs,               \
+        const double* vals, int64_t num_blocks, uint32_t max_block_size,                     \
+        gkoc_jacobi_scheme scheme, const I* block_ptrs, double accuracy,                     \
+        uint8_t* precisions, double* conditioning, double* blocks)                           \
+    {                                                                                        \
+        (void)n_rows;                                                                        \
+        return launch_generate_adaptive_any<double, I, false>(                               \
+            s, row_ptrs, col_idxs, vals, num_blocks, max_block_size, scheme, block_ptrs,     \
+            accuracy, precisions, conditioning, blocks);                                     \
+    }                                                                                        \
+    extern "C" int gkoc_jacobi_apply_adaptive_f64_##IN(                                      \
+        gkoc_stream_t s, int64_t num_blocks, uint32_t max_block_size,                        \
+        gkoc_jacobi_scheme scheme, const I* block_ptrs, const double* blocks,                \
+        const uint8_t* precisions, const double* alpha, const double* b, int64_t ldb,        \
+        const double* beta, double* x, int64_t ldx, int64_t nrhs)                            \
+    {                                                                                        \
+        GKOC_REQUIRE((alpha == nullptr) == (beta == nullptr), GKOC_E_INVALID,                \
+                     "pass alpha and beta, or neither");                                     \
+        if (alpha) {                                                                         \
+            return launch_apply_adaptive<I, true>(s, num_blocks, max_block_size, scheme,     \
+                                                  block_ptrs, blocks, precisions, alpha, b,  \
+                                                  ldb, beta, x, ldx, nrhs);                  \
+        }                                                                                    \
+        return launch_apply_adaptive<I, false>(s, num_blocks, max_block_size, scheme,        \
+                                               block_ptrs, blocks, precisions, nullptr, b,   \
+                                               ldb, nullptr, x, ldx, nrhs);                  \
+    }
+GKOC_DEF_JACOBI_ADAPTIVE(int32_t, i32)
+GKOC_DEF_JACOBI_ADAPTIVE(int64_t, i64)
+
+// reduced-precision storage: value type double only
+extern "C" int gkoc_jacobi_convert_storage_f64(gkoc_stream_t s, int64_t num_blocks,
+                                               gkoc_jacobi_scheme scheme, double* blocks,
+                                               uint8_t precision)
+{
+    return launch_convert_storage(s, num_blocks, scheme, blocks, int(precision));
+}
+
+#define GKOC_DEF_JACOBI_STORED(I, IN)                                                        \
+    extern "C" int gkoc_jacobi_apply_stored_f64_##IN(                                        \
+        gkoc_stream_t s, int64_t num_blocks, uint32_t max_block_size,                        \
+        gkoc_jacobi_scheme scheme, const I* block_ptrs, const double* blocks,                \
+        uint8_t precision, const double* alpha, const double* b, int64_t ldb,                \
+        const double* beta, double* x, int64_t ldx, int64_t nrhs)                            \
+    {                                                                                        \
+        GKOC_REQUIRE((alpha == nullptr) == (beta == nullptr), GKOC_E_INVALID,                \
+                     "pass alpha and beta, or neither");                                     \
+        if (alpha) {                                                                         \
+            return launch_apply_stored<I, true>(s, num_blocks, max_block_size, scheme,       \
+                                                block_ptrs, blocks, int(precision), alpha,   \
+                                                b, ldb, beta, x, ldx, nrhs);                 \
+        }                                                                                    \
+        return launch_apply_stored<I, false>(s, num_blocks, max_block_size, scheme,          \
+                                             block_ptrs, blocks, int(precision), nullptr, b, \
+                                             ldb, nullptr, x, ldx, nrhs);                    \
+    }
+GKOC_DEF_JACOBI_STORED(int32_t, i32)
+GKOC_DEF_JACOBI_STORED(int64_t, i64)
+
+// adaptive storage, float and the complex types (an autodetect request without the conditioning array
+// keeps the value type: AUTO_NEEDS_COND = true)
 #define GKOC_DEF_JACOBI_ADAPTIVE_ANY(T, R, TN, I, IN)                                               \
     extern "C" int gkoc_jacobi_generate_adaptive_##TN##_##IN(                                       \
         gkoc_stream_t s, int64_t n_rows, const I* row_ptrs, const I* col_idxs, const T* vals,       \
@@ -2667,9 +2365,9 @@ int launch_transpose_adaptive_any(gkoc_stream_t s, int64_t num_blocks, gkoc_jaco
         R accuracy, uint8_t* precisions, R* conditioning, T* blocks)                                \
     {                                                                                               \
         (void)n_rows;                                                                               \
-        return launch_generate_adaptive_any<T, I>(s, row_ptrs, col_idxs, vals, num_blocks,          \
-                                                  max_block_size, scheme, block_ptrs, accuracy,     \
-                                                  precisions, conditioning, blocks);                \
+        return launch_generate_adaptive_any<T, I, true>(s, row_ptrs, col_idxs, vals, num_blocks,    \
+                                                        max_block_size, scheme, block_ptrs,         \
+                                                        accuracy, precisions, conditioning, blocks); \
     }                                                                                               \
     extern "C" int gkoc_jacobi_apply_adaptive_##TN##_##IN(                                          \
         gkoc_stream_t s, int64_t num_blocks, uint32_t max_block_size, gkoc_jacobi_scheme scheme,    \
@@ -2680,13 +2378,11 @@ int launch_transpose_adaptive_any(gkoc_stream_t s, int64_t num_blocks, gkoc_jaco
         GKOC_REQUIRE((alpha == nullptr) == (beta == nullptr), GKOC_E_INVALID,                       \
                      "pass alpha and beta, or neither");                                            \
         if (alpha) {                                                                                \
-            return launch_apply_adaptive_any<T, I, true>(s, num_blocks, scheme, block_ptrs, blocks, \
-                                                         precisions, alpha, b, ldb, beta, x, ldx,   \
-                                                         nrhs);                                     \
+            return launch_apply_any<T, I, true>(s, num_blocks, scheme, block_ptrs, blocks, precisions, \
+                                                alpha, b, ldb, beta, x, ldx, nrhs);                 \
         }                                                                                           \
-        return launch_apply_adaptive_any<T, I, false>(s, num_blocks, scheme, block_ptrs, blocks,    \
-                                                      precisions, nullptr, b, ldb, nullptr, x, ldx, \
-                                                      nrhs);                                        \
+        return launch_apply_any<T, I, false>(s, num_blocks, scheme, block_ptrs, blocks, precisions, \
+                                             nullptr, b, ldb, nullptr, x, ldx, nrhs);               \
     }                                                                                               \
     extern "C" int gkoc_jacobi_transpose_adaptive_##TN##_##IN(                                      \
         gkoc_stream_t s, int64_t num_blocks, gkoc_jacobi_scheme scheme, const I* block_ptrs,        \
@@ -2701,3 +2397,59 @@ GKOC_DEF_JACOBI_ADAPTIVE_ANY(gkoc_c128, double, c128, int32_t, i32)
 GKOC_DEF_JACOBI_ADAPTIVE_ANY(gkoc_c128, double, c128, int64_t, i64)
 GKOC_DEF_JACOBI_ADAPTIVE_ANY(gkoc_c64, float, c64, int32_t, i32)
 GKOC_DEF_JACOBI_ADAPTIVE_ANY(gkoc_c64, float, c64, int64_t, i64)
+
+// jacobi::transpose_jacobi / conj_transpose_jacobi
+#define GKOC_DEF_JACOBI_TRANSPOSE(T, TN, I, IN)                                             \
+    extern "C" int gkoc_jacobi_transpose_##TN##_##IN(                                       \
+        gkoc_stream_t s, int64_t num_blocks, uint32_t max_block_size,                       \
+        gkoc_jacobi_scheme scheme, const I* block_ptrs, const T* blocks,                    \
+        const uint8_t* precisions, T* out_blocks)                                           \
+    {                                                                                       \
+        (void)max_block_size;                                                               \
+        if (num_blocks <= 0) return GKOC_OK;                                                \
+        GKOC_REQUIRE(block_ptrs && blocks && out_blocks, GKOC_E_INVALID, "null pointer");   \
+        GKOC_REQUIRE(scheme.block_offset >= 1, GKOC_E_INVALID, "bad storage scheme");       \
+        GKOC_REQUIRE(precisions == nullptr || sizeof(T) == 8, GKOC_E_NOT_SUPPORTED,         \
+                     "reduced float blocks: gkoc_jacobi_transpose_adaptive_f32_*");         \
+        int64_t nb = ceildiv(num_blocks * scheme.block_offset, 256);                        \
+        if (nb > 4 * max_stream_blocks) nb = 4 * max_stream_blocks;                         \
+        jacobi_transpose_kernel<T, I><<<dim3(unsigned(nb)), dim3(256), 0, as_stream(s)>>>(  \
+            num_blocks, scheme, block_ptrs, blocks, precisions, out_blocks);                \
+        GKOC_LAUNCH_OK();                                                                   \
+        return GKOC_OK;                                                                     \
+    }
+GKOC_DEF_JACOBI_TRANSPOSE(double, f64, int32_t, i32)
+GKOC_DEF_JACOBI_TRANSPOSE(double, f64, int64_t, i64)
+GKOC_DEF_JACOBI_TRANSPOSE(float, f32, int32_t, i32)
+GKOC_DEF_JACOBI_TRANSPOSE(float, f32, int64_t, i64)
+
+// ... and for complex values in full storage
+#define GKOC_DEF_CJACOBI_TRANSPOSE(T, TN, I, IN)                                                        \
+    extern "C" int gkoc_cjacobi_transpose_##TN##_##IN(gkoc_stream_t s, int64_t num_blocks,              \
+                                                      gkoc_jacobi_scheme scheme, const I* block_ptrs,   \
+                                                      const T* blocks, int conj, T* out_blocks)         \
+    {                                                                                                   \
+        return launch_transpose_adaptive_any<T, I>(s, num_blocks, scheme, block_ptrs, blocks,           \
+                                                   /* precisions: full storage */ nullptr, conj,        \
+                                                   out_blocks);                                         \
+    }
+GKOC_DEF_CJACOBI_TRANSPOSE(gkoc_c128, c128, int32_t, i32)
+GKOC_DEF_CJACOBI_TRANSPOSE(gkoc_c128, c128, int64_t, i64)
+GKOC_DEF_CJACOBI_TRANSPOSE(gkoc_c64, c64, int32_t, i32)
+GKOC_DEF_CJACOBI_TRANSPOSE(gkoc_c64, c64, int64_t, i64)
+
+// jacobi::initialize_precisions (reference/preconditioner/jacobi_kernels.cpp:454-462)
+extern "C" int gkoc_jacobi_initialize_precisions(gkoc_stream_t s, const uint8_t* source,
+                                                 int64_t source_size, uint8_t* precisions,
+                                                 int64_t n)
+{
+    GKOC_REQUIRE(n >= 0 && source_size >= 0, GKOC_E_INVALID, "negative size");
+    if (n == 0) return GKOC_OK;
+    GKOC_REQUIRE(source && precisions && source_size > 0, GKOC_E_INVALID, "bad argument");
+    int64_t nb = ceildiv(n, 256);
+    if (nb > max_stream_blocks) nb = max_stream_blocks;
+    tile_bytes_kernel<<<dim3(unsigned(nb)), dim3(256), 0, as_stream(s)>>>(n, source, source_size,
+                                                                         precisions);
+    GKOC_LAUNCH_OK();
+    return GKOC_OK;
+}

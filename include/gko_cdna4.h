@@ -225,7 +225,7 @@ int gkoc_arena_probe(const void* x, size_t x_bytes, void* y, int read_kb_per_wav
                                       r06_waves_per_workgroup.txt) */
 #define GKOC_TUNE_JACOBI_LANES 15    /* block-Jacobi apply for float / complex values and adaptive storage of those:
                                       0 (default) lane = (block, row) of a storage group, 1: the thread-per-row
-                                      kernels of round 5 (A/B runs) */
+                                      kernel of round 5 (A/B runs) */
 #define GKOC_TUNE_CCSR_THREAD_PER_ROW 16 /* csr::spmv on complex values: 0 (default) the row-segment kernel of the real
                                       types, 1: one thread per row (round 5; A/B runs) */
 #define GKOC_TUNE_JACOBI_REHOME 17   /* binding for the unmodified Ginkgo core: 1 (default) jacobi::generate re-allocates
@@ -1000,7 +1000,8 @@ int gkoc_jacobi_apply_stored_f64_i64(
  * storage type < accuracy, and - for float / half - the rounded inverse must still be
  * invertible with a sane condition number, :280-307); out: the precision of its storage
  * group (all blocks of a group share one: the best one every block supports,
- * core/preconditioner/jacobi_utils.hpp:104-176).  conditioning[b] (may be NULL) =
+ * core/preconditioner/jacobi_utils.hpp:104-176).  conditioning[b] (may be NULL: only
+ * an output here, autodetect works without it) =
  * norm(block) * norm(inverse) as the reference computes it.  The blocks are stored in
  * the chosen types; apply_adaptive widens on load (alpha = beta = NULL: x = M b).
  * Decisions, condition numbers, stored blocks and apply results are bit-identical to
@@ -1025,7 +1026,9 @@ GKOC_DECL_JACOBI_ADAPTIVE(int64_t, i64)
 /* ... for the value types float, complex<float>, complex<double> (the other instantiations of
  * jacobi::generate / simple_apply / apply / transpose_jacobi / conj_transpose_jacobi with a
  * precision array, core/preconditioner/jacobi_kernels.hpp:30-103).  Same meaning of the arguments;
- * accuracy and conditioning are of the component type.  The storage types follow the component
+ * accuracy and conditioning are of the component type; without a conditioning array (NULL) an
+ * autodetect request keeps the value type (precision 0x00) - unlike the double entry point above, which
+ * autodetects all the same.  The storage types follow the component
  * type (core/preconditioner/jacobi_utils.hpp:15-38 with include/ginkgo/core/base/math.hpp:365-383,
  * :546-582): for double components the five of the double path; for float components (0,1), (0,2),
  * (1,1) = half and (1,0), (2,0) = the upper 16 bits of the float; a complex entry is its two parts

@@ -28,3 +28,21 @@ def graded_block_matrix(n_groups, bs, seed, coupling=1e-3):
     a.sort_indices()
     # block detection needs the full block pattern: make sure no block entry is exactly zero
     return a.indptr.astype(np.int32), a.indices.astype(np.int32), a.data.astype(np.float64)
+
+
+def block_byte_mask(scheme, ptrs, width):
+    """bytes of the group-major storage (first go*width bytes of every group) that belong to
+    an entry of a block"""
+    bo, go, gp = scheme
+    stride = bo << gp
+    nb = len(ptrs) - 1
+    groups = (nb + (1 << gp) - 1) >> gp
+    mask = np.zeros((groups, go * width), dtype=bool)
+    for blk in range(nb):
+        bsz = int(ptrs[blk + 1] - ptrs[blk])
+        g_, off = blk >> gp, bo * (blk & ((1 << gp) - 1))
+        for c in range(bsz):
+            for r in range(bsz):
+                e = off + r + c * stride
+                mask[g_, e * width:(e + 1) * width] = True
+    return mask

@@ -272,3 +272,73 @@ def test_lane_layout_equals_the_thread_per_row_kernels_bit_for_bit(gexec, vt, ma
 
 def rdt_np(rdt):
     return np.float32 if rdt == torch.float32 else np.float64
+
+
+@pytest.mark.parametrize("bs", [4, 13])
+def test_autodetect_without_the_condition_number_array(gexec, oracle, bs):
+    """gkoc_jacobi_generate_adaptive_* with conditioning == NULL and every block on autodetect (0xff).
+    The two families differ here, and both behaviours are pinned as they are:
+    f64 autodetects all the same ("conditioning ... may be NULL", include/gko_cdna4.h) - the same precision
+    bytes and the same stored bytes as with the array, and more than one storage type among them;
+    f32 (and the complex types, which share its kernel) reads the request as "keep the value type": every
+    precision byte 0x00, the blocks those of gkoc_jacobi_generate_f32 - the same product bit for bit -
+    whereas with the array something is reduced."""
+    from adaptive_cases import block_byte_mask, graded_block_matrix
+    from ginkgo_amd._lib import call
+    from ginkgo_amd.preconditioner import compute_storage_scheme
+    ex = gexec
+    rp, ci, v = graded_block_matrix(24, bs, bs)
+    n = len(rp) - 1
+    nb, ptrs = oracle.jacobi_find_blocks(rp, ci, bs)
+    ptrs = ptrs[:nb + 1]
+    scheme = compute_storage_scheme(bs, 64)
+    oscheme = oracle.jacobi_storage_scheme(bs)
+    assert (scheme.block_offset, scheme.group_offset, scheme.group_power) == tuple(oscheme)
+    go, gp = oscheme[1], oscheme[2]
+    storage = ((nb + (1 << gp) - 1) >> gp) * go
+    d_rp, d_ci, d_bp = (ex.to_device(a) for a in (rp, ci, ptrs))
+    acc = 1e-1
+
+    def generate(vt, d_v, dt, rdt, with_cond):
+        blocks = ex.zeros((storage,), dt)
+        prec = ex.to_device(np.full(nb, 0xff, np.uint8))
+        cond = ex.zeros((nb,), rdt) if with_cond else None
+        call(f"gkoc_jacobi_generate_adaptive_{vt}_i32", ex.stream, n, d_rp, d_ci, d_v, nb, C.c_uint32(bs), scheme,
+             d_bp, C.c_float(acc) if rdt == torch.float32 else C.c_double(acc), prec, cond, blocks)
+        ex.synchronize()
+        return blocks, prec
+
+    # (a) f64: NULL changes nothing
+    d_v = ex.to_device(v)
+    blocks_c, prec_c = generate("f64", d_v, torch.float64, torch.float64, True)
+    blocks_n, prec_n = generate("f64", d_v, torch.float64, torch.float64, False)
+    prec = prec_c.cpu().numpy()
+    assert np.array_equal(prec_n.cpu().numpy(), prec)
+    assert len(set(prec.tolist())) >= 2, prec
+    with_c = blocks_c.cpu().numpy().view(np.uint8).reshape(-1, go * 8)
+    without = blocks_n.cpu().numpy().view(np.uint8).reshape(-1, go * 8)
+    for grp in range(with_c.shape[0]):
+        width = {0x00: 8, 0x01: 4, 0x02: 2, 0x10: 4, 0x11: 2, 0x20: 2}[int(prec[grp << gp])]
+        mask = block_byte_mask(oscheme, ptrs[grp << gp:min((grp + 1) << gp, nb) + 1], width)[0]
+        assert np.array_equal(without[grp, :go * width][mask], with_c[grp, :go * width][mask]), grp
+
+    # (b) f32: NULL keeps the value type
+    d_v = ex.to_device(v.astype(np.float32))
+    blocks_n, prec_n = generate("f32", d_v, torch.float32, torch.float32, False)
+    assert not prec_n.cpu().numpy().any(), prec_n.cpu().numpy()
+    full = ex.zeros((storage,), torch.float32)
+    call("gkoc_jacobi_generate_f32_i32", ex.stream, n, d_rp, d_ci, d_v, nb, C.c_uint32(bs), scheme, d_bp, full, None)
+    d_b = ex.to_device(np.random.default_rng(bs).uniform(-1, 1, n).astype(np.float32))
+
+    def product(blk):
+        x = ex.zeros((n,), torch.float32)
+        call("gkoc_jacobi_apply_adaptive_f32_i32", ex.stream, nb, C.c_uint32(bs), scheme, d_bp, blk, prec_n, None,
+             d_b, 1, None, x, 1, 1)
+        ex.synchronize()
+        return x.cpu().numpy()
+
+    want = product(full)
+    assert want.any()
+    assert product(blocks_n).tobytes() == want.tobytes()
+    _, prec_c = generate("f32", d_v, torch.float32, torch.float32, True)
+    assert prec_c.cpu().numpy().any()

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+from adaptive_cases import block_byte_mask
 from util import random_csr, rel_frobenius
 
 pytestmark = pytest.mark.gpu
@@ -687,7 +688,7 @@ def test_jacobi_reduced_storage_bit_exact(gexec, oracle, bs):
         go = scheme[1]
         dev = m.blocks.cpu().numpy().view(np.uint8).reshape(-1, go * 8)[:, :go * width]
         ref = st.view(np.uint8).reshape(-1, go * 8)[:, :go * width]
-        mask = _block_byte_mask(scheme, ptrs[:nb + 1], width)
+        mask = block_byte_mask(scheme, ptrs[:nb + 1], width)
         assert np.array_equal(dev[mask], ref[mask]), (bs, hex(prec))
         x = g.Dense.create(gexec, (n, 1))
         m.apply(g.Dense.from_numpy(gexec, b), x)
@@ -696,24 +697,6 @@ def test_jacobi_reduced_storage_bit_exact(gexec, oracle, bs):
         m.apply(g.scalar(gexec, 0.7), g.Dense.from_numpy(gexec, b), g.scalar(gexec, -1.1), x)
         assert np.array_equal(x.to_numpy()[:, 0],
                               oracle.jacobi_apply_stored(nb, scheme, ptrs, st, prec, b, 0.7, -1.1, x0))
-
-
-def _block_byte_mask(scheme, ptrs, width):
-    """bytes of the group-major storage (first go*width bytes of every group) that belong to
-    an entry of a block"""
-    bo, go, gp = scheme
-    stride = bo << gp
-    nb = len(ptrs) - 1
-    groups = (nb + (1 << gp) - 1) >> gp
-    mask = np.zeros((groups, go * width), dtype=bool)
-    for blk in range(nb):
-        bsz = int(ptrs[blk + 1] - ptrs[blk])
-        g_, off = blk >> gp, bo * (blk & ((1 << gp) - 1))
-        for c in range(bsz):
-            for r in range(bsz):
-                e = off + r + c * stride
-                mask[g_, e * width:(e + 1) * width] = True
-    return mask
 
 
 def test_jacobi_reduced_storage_golden_and_cg(gexec, oracle):
@@ -794,7 +777,7 @@ def test_jacobi_adaptive_precision_bit_exact(gexec, oracle, bs):
         for grp in range(dev.shape[0]):
             width = {0x00: 8, 0x01: 4, 0x02: 2, 0x10: 4, 0x11: 2, 0x20: 2}[int(prec_o[grp << gp])]
             sub_ptrs = ptrs[grp << gp:min(((grp + 1) << gp), nb) + 1]
-            mask = _block_byte_mask(scheme, sub_ptrs, width)[0]
+            mask = block_byte_mask(scheme, sub_ptrs, width)[0]
             assert np.array_equal(dev[grp, :go * width][mask], ref[grp, :go * width][mask]), (bs, acc, grp)
         x = g.Dense.create(gexec, (n, 1))
         m.apply(g.Dense.from_numpy(gexec, b), x)
