@@ -970,6 +970,23 @@ bool arena_owns(const void* ptr)
     return false;
 }
 
+size_t arena_allocation_bytes(const void* ptr)
+{
+    if (ptr == nullptr) return 0;
+    std::lock_guard<std::mutex> g(g_mtx);
+    auto starts = [ptr](const span& c) -> size_t {
+        const auto u = c.used.find(size_t(static_cast<const char*>(ptr) - c.base));
+        return u == c.used.end() ? 0 : u->second;
+    };
+    for (int dev = 0; dev < 64; ++dev) {
+        const device_arena& A = g_arena[dev];
+        for (const span* c : A.small) if (c->owns(ptr)) return starts(*c);
+        for (const span* c : A.plain) if (c->owns(ptr)) return starts(*c);
+        for (int k = 0; k < A.n_cls; ++k) if (A.reg[k].owns(ptr)) return starts(A.reg[k]);
+    }
+    return 0;
+}
+
 // ---- stream-ordered scratch ---------------------------------------------------
 namespace {
 struct pending_free {

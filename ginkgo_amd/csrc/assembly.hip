@@ -220,6 +220,7 @@ extern "C" size_t gkoc_compact_workspace_bytes(int64_t nnz)
                                                    I* row_idxs, I* col_idxs, T* vals,       \
                                                    void* work, size_t work_bytes)           \
     {                                                                                       \
+        gkoc::csr_structure_written(row_idxs); gkoc::csr_structure_written(col_idxs);       \
         GKOC_REQUIRE(nnz >= 0, GKOC_E_INVALID, "negative size");                            \
         if (nnz <= 1) return GKOC_OK;                                                       \
         const size_t need = sort_work_bytes<T, I>(nnz);                                     \
@@ -263,6 +264,7 @@ extern "C" size_t gkoc_compact_workspace_bytes(int64_t nnz)
         gkoc_stream_t s, int64_t nnz, const I* row_idxs, const I* col_idxs, const T* vals,  \
         const void* work, I* out_rows, I* out_cols, T* out_vals)                            \
     {                                                                                       \
+        gkoc::csr_structure_written(out_rows); gkoc::csr_structure_written(out_cols);       \
         if (nnz <= 0) return GKOC_OK;                                                       \
         GKOC_REQUIRE(work, GKOC_E_WORKSPACE, "null workspace");                             \
         compact_kernel<T, I><<<dim3(grid_for(nnz)), dim3(256), 0, as_stream(s)>>>(          \
@@ -275,6 +277,7 @@ extern "C" size_t gkoc_compact_workspace_bytes(int64_t nnz)
         gkoc_stream_t s, int64_t nnz, const I* row_idxs, const I* col_idxs, const T* vals,  \
         const void* work, I* out_rows, I* out_cols, T* out_vals)                            \
     {                                                                                       \
+        gkoc::csr_structure_written(out_rows); gkoc::csr_structure_written(out_cols);       \
         if (nnz <= 0) return GKOC_OK;                                                       \
         GKOC_REQUIRE(work, GKOC_E_WORKSPACE, "null workspace");                             \
         sum_runs_kernel<T, I><<<dim3(grid_for(nnz)), dim3(256), 0, as_stream(s)>>>(         \

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdint>
 #include <cstdio>
 
@@ -54,6 +55,9 @@ const device_props& current_device_props();
 int arena_malloc(void** ptr, size_t bytes, int role);
 int arena_free(void* ptr);
 bool arena_owns(const void* ptr);
+// bytes of the live allocation of the arena that STARTS at ptr (gkoc_free sees such an address before it is
+// reused); 0: ptr is no such start
+size_t arena_allocation_bytes(const void* ptr);
 // Stream-ordered scratch for the library's own temporaries (flags, scan partials,
 // find_blocks work arrays): taken from the arena, handed back once `st` has passed the
 // point of scratch_free.  NOT hipMallocAsync / hipFreeAsync: their pool unmaps and
@@ -76,6 +80,17 @@ int stream_ticket(hipStream_t st, unsigned** word);
 // csr::spmv's memory of which segments of a matrix hold very long rows (csr_spmv.hip): forgotten when the
 // row-pointer array is freed
 void csr_long_rows_forget(const void* ptr);
+// csr::spmv's cached column-offset plans (csr_offsets.hpp, csr_spmv.hip), keyed by a matrix' two index arrays:
+// every entry of the library that frees or WRITES an index array of a CSR matrix says so.  An atomic load
+// while no plan exists.
+extern std::atomic<int> g_csr_offsets_cached;
+void csr_offsets_forget(const void* first, size_t bytes);
+inline void csr_structure_written(const void* index_array, size_t bytes = 1)
+{
+    if (index_array != nullptr && g_csr_offsets_cached.load(std::memory_order_relaxed) != 0) {
+        csr_offsets_forget(index_array, bytes);
+    }
+}
 // csr::spmv / advanced_spmv on complex values through the row-segment kernel of the real types
 // (csr_spmv.hip; complex_blas.hip's gkoc_ccsr_spmv_* calls it).  GKOC_E_NOT_SUPPORTED: the arrays are not
 // aligned for its loads - the caller keeps its thread-per-row kernel for that.
@@ -91,7 +106,7 @@ int csr_spmv_complex(gkoc_stream_t s, int64_t n_rows, int64_t nrhs, const I* row
 int gate_fence_policy();
 void gate_fence_policy_set(int policy);
 // tuning switches (runtime.hip; keys = GKOC_TUNE_* of gko_cdna4.h)
-constexpr int tune_num_keys = 18;
+constexpr int tune_num_keys = 19;
 int64_t tune_value(int key);
 
 #ifdef __HIPCC__

@@ -754,6 +754,7 @@ GKOC_DEF_CDENSE_CSR(gkoc_c64, c64, float)
     extern "C" int gkoc_cdense_to_csr_##TN##_##IN(gkoc_stream_t s, int64_t rows, int64_t cols, const P* in, \
                                                   int64_t ld, const I* row_ptrs, I* out_cols, P* out_vals)  \
     {                                                                                                       \
+        gkoc::csr_structure_written(out_cols);                                                              \
         if (rows <= 0) return GKOC_OK;                                                                      \
         cx_dense_to_csr_kernel<R, I><<<dim3(grid_of(rows)), dim3(256), 0, as_stream(s)>>>(                  \
             rows, cols, reinterpret_cast<const cx<R>*>(in), ld, row_ptrs, out_cols,                         \

@@ -996,6 +996,7 @@ GKOC_DEF_CV_DENSE(gkoc_c64, c64)
                                                  const T* in, int64_t ld, const I* row_ptrs,            \
                                                  I* out_cols, T* out_vals)                              \
     {                                                                                                   \
+        gkoc::csr_structure_written(out_cols);                                                          \
         GKOC_REQUIRE(rows >= 0 && cols >= 0 && (rows == 0 || row_ptrs), GKOC_E_INVALID, "bad argument"); \
         CV_LAUNCH((dense_to_rows_kernel<T, I, I>), rows, rows, cols, in, ld, row_ptrs,                  \
                   static_cast<I*>(nullptr), out_cols, out_vals);                                        \
@@ -1099,6 +1100,7 @@ GKOC_DEF_CV_DENSE(gkoc_c64, c64)
                                                int64_t stride, const I* cols, const T* vals,            \
                                                const I* row_ptrs, I* out_cols, T* out_vals)             \
     {                                                                                                   \
+        gkoc::csr_structure_written(out_cols);                                                          \
         CV_LAUNCH((ell_to_csr_kernel<T, I>), n_rows, n_rows, ell_k, stride, cols, vals, row_ptrs,       \
                   out_cols, out_vals);                                                                  \
         return GKOC_OK;                                                                                 \
@@ -1108,6 +1110,7 @@ GKOC_DEF_CV_DENSE(gkoc_c64, c64)
                                                  const T* vals, const I* row_ptrs, I* out_cols,         \
                                                  T* out_vals)                                           \
     {                                                                                                   \
+        gkoc::csr_structure_written(out_cols);                                                          \
         GKOC_REQUIRE(slice_size > 0, GKOC_E_INVALID, "bad slice size");                                 \
         CV_LAUNCH((sellp_to_csr_kernel<T, I>), n_rows, n_rows, slice_size, slice_sets, cols, vals,      \
                   row_ptrs, out_cols, out_vals);                                                        \
@@ -1118,6 +1121,7 @@ GKOC_DEF_CV_DENSE(gkoc_c64, c64)
         const T* ell_vals, const I* coo_cols, const T* coo_vals, const I* ell_row_ptrs,                 \
         const I* coo_row_ptrs, I* out_row_ptrs, I* out_cols, T* out_vals)                               \
     {                                                                                                   \
+        gkoc::csr_structure_written(out_row_ptrs); gkoc::csr_structure_written(out_cols);               \
         GKOC_REQUIRE(n_rows >= 0 && ell_row_ptrs && coo_row_ptrs && out_row_ptrs, GKOC_E_INVALID,       \
                      "bad argument");                                                                   \
         CV_LAUNCH((hybrid_to_csr_kernel<T, I>), n_rows + 1, n_rows, ell_k, stride, ell_cols, ell_vals,  \
@@ -1201,6 +1205,7 @@ GKOC_DEF_CV_INDEX(int64_t, i64)
         const I* row_perm, int row_inverse, const I* col_perm, const T* row_scale, const T* col_scale,  \
         int scale_mode, I* out_rp, I* out_ci, T* out_v)                                                 \
     {                                                                                                   \
+        gkoc::csr_structure_written(out_rp); gkoc::csr_structure_written(out_ci);                       \
         GKOC_REQUIRE(n_rows >= 0 && in_rp && out_rp, GKOC_E_INVALID, "bad argument");                   \
         GKOC_REQUIRE(scale_mode >= 0 && scale_mode <= 2 && (scale_mode != 1 || row_scale) &&            \
                          (scale_mode != 2 || row_scale || col_scale),                                   \
@@ -1246,6 +1251,7 @@ GKOC_DEF_CV_INDEX(int64_t, i64)
                                                   const I* in_ci, const T* in_v, const I* out_rp,       \
                                                   I* out_ci, T* out_v)                                  \
     {                                                                                                   \
+        gkoc::csr_structure_written(out_ci);                                                            \
         CV_LAUNCH((csr_span_kernel<T, I, true>), n, n, row0, col0, col1, in_rp, in_ci, in_v,            \
                   static_cast<I*>(nullptr), out_rp, out_ci, out_v);                                     \
         return GKOC_OK;                                                                                 \
@@ -1274,6 +1280,7 @@ GKOC_DEF_CV_INDEX(int64_t, i64)
         const I* col_superset, int64_t col_set_size, const I* in_rp, const I* in_ci, const T* in_v,     \
         const I* out_rp, I* out_ci, T* out_v)                                                           \
     {                                                                                                   \
+        gkoc::csr_structure_written(out_ci);                                                            \
         GKOC_REQUIRE(n_result_rows >= 0 && n_row_subsets >= 0 && n_col_subsets >= 0, GKOC_E_INVALID,    \
                      "negative size");                                                                  \
         GKOC_REQUIRE(n_result_rows == 0 || (n_row_subsets > 0 && n_col_subsets > 0 && row_begin &&      \
@@ -1377,6 +1384,7 @@ GKOC_DEF_SPGEMM(gkoc_c64, c64, int64_t, i64)
                                                           const I* shift, I* new_rp, I* new_ci,         \
                                                           T* new_v)                                     \
     {                                                                                                   \
+        gkoc::csr_structure_written(new_rp); gkoc::csr_structure_written(new_ci);                       \
         GKOC_REQUIRE(n_rows >= 0 && rp && shift && new_rp, GKOC_E_INVALID, "bad argument");             \
         CV_LAUNCH((add_diagonal_fill_kernel<T, I>), n_rows + 1, n_rows, rp, ci, v, shift, new_rp,       \
                   new_ci, new_v);                                                                       \

@@ -505,6 +505,7 @@ extern "C" int gkoc_hybrid_compute_coo_row_ptrs(gkoc_stream_t s, int64_t n_rows,
     extern "C" int gkoc_convert_ptrs_to_idxs_##IN(gkoc_stream_t s, const I* ptrs,           \
                                                   int64_t n_rows, I* idxs)                  \
     {                                                                                       \
+        gkoc::csr_structure_written(idxs);                                                  \
         GKOC_REQUIRE(n_rows >= 0, GKOC_E_INVALID, "negative size");                         \
         if (n_rows == 0) return GKOC_OK;                                                    \
         ptrs_to_idxs_kernel<I><<<dim3(unsigned(ceildiv(n_rows, 64))), dim3(64), 0,          \

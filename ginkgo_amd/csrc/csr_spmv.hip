@@ -30,6 +30,7 @@
 
 #include "common.hpp"
 #include "csr_long_rows.hpp"
+#include "csr_offsets.hpp"
 #include "csr_spmv_multi.hpp"
 #include "csr_spmv_pipe.hpp"
 #include "fused.hpp"
@@ -203,6 +204,8 @@ void csr_long_rows_forget(const void* ptr)
     }
 }
 
+std::atomic<int> g_csr_offsets_cached{0};
+
 namespace {
 
 // ---- the launch plan of the row-segment kernels (csr_spmv_pipe3_kernel, csr_spmv_multi_kernel) -------------
@@ -360,6 +363,173 @@ int launch_csr_pair(gkoc_stream_t s, int64_t n_rows, const T* alpha, const I* ro
     return GKOC_OK;
 }
 
+// ---- cached per-segment column offsets (csr_offsets.hpp) ---------------------------------------------------
+// A derived, read-only description of (row_ptrs, col_idxs), keyed by (device, row_ptrs, col_idxs, n_rows), in
+// the style of the long-row cache above.  Only for index arrays that are live allocations of the library's own
+// allocator: their addresses cannot be reused without gkoc_free seeing them.  Built by the SECOND product on the
+// same arrays (a one-shot product never pays; GKOC_TUNE_CSR_OFFSETS = 1: by the first, 2: never), never inside a
+// stream capture (the product takes the row-segment kernel and the next one tries again).  Dropped by
+// csr_offsets_forget: gkoc_free, every C-ABI entry that writes an index array of a CSR matrix, gkoc_memcpy_h2d /
+// _d2d into one, gkoc_csr_structure_changed.  Lookup and launch happen under the mutex, so a plan cannot be
+// released between the two; its buffers are released after a device synchronisation.
+std::mutex g_off_mtx;
+struct offsets_plan {
+    int state = 0;                  // 0: seen once, 1: in use, 2: rejected (fewer than half of the segments eligible)
+    int64_t n_seg = 0, eligible = 0;
+    int32_t* seg_tab = nullptr;     // device: OFFS_TAB int32 per segment
+    uint32_t* row_mask = nullptr;   // device: one word per row
+    uint32_t* skip = nullptr;       // device: bit per segment the row-segment kernel leaves out (eligible | long-flagged)
+    bool with_long = false;         // skip holds the long-row flags too
+    int64_t bytes = 0, products = 0;
+    uint64_t seq = 0;
+    size_t rp_bytes = 0, ci_bytes = 0;      // the two allocations the plan describes (csr_offsets_forget)
+};
+using offsets_key = std::tuple<int, const void*, const void*, int64_t>;
+std::map<offsets_key, offsets_plan> g_off_cache;
+constexpr size_t offsets_cache_cap = 128;
+// at least this share of the segments must be eligible, in per cent (docs/KERNELS.md: measured on a stencil
+// whose every other segment is not)
+constexpr int64_t offsets_min_share = 50;
+
+// buffers of dropped plans that could not be released at once (inside a stream capture the device cannot be
+// synchronised): released with the next plan that goes.  Guarded by g_off_mtx.
+std::vector<void*> g_off_graveyard;
+
+// Only plans that HAVE buffers pay the synchronisation (a product in flight on any stream may still read them):
+// matrices that were multiplied through a plan, as with the long-row cache above.
+void offsets_release(std::vector<offsets_plan>& gone)
+{
+    std::vector<void*> bufs;
+    for (auto& pl : gone) {
+        for (void* b : {static_cast<void*>(pl.seg_tab), static_cast<void*>(pl.row_mask), static_cast<void*>(pl.skip)}) {
+            if (b) bufs.push_back(b);
+        }
+    }
+    if (bufs.empty()) return;
+    std::lock_guard<std::mutex> g(g_off_mtx);
+    g_off_graveyard.insert(g_off_graveyard.end(), bufs.begin(), bufs.end());
+    if (hipDeviceSynchronize() != hipSuccess) {
+        (void)hipGetLastError();      // (a capture is under way: they wait in the graveyard)
+        return;
+    }
+    for (void* b : g_off_graveyard) (void)arena_free(b);
+    g_off_graveyard.clear();
+}
+
+// the analysis: one pass over the column indices, the eligible count comes back with one stream synchronisation
+int offsets_build(hipStream_t st, int64_t n_rows, const int32_t* row_ptrs, const int32_t* col_idxs,
+                  const csr_long_info& lng, offsets_plan& pl)
+{
+    const int64_t n_seg = ceildiv(n_rows, int64_t(64));
+    const size_t tab_bytes = size_t(n_seg) * OFFS_TAB * 4, mask_bytes = size_t(n_rows) * 4;
+    const size_t skip_bytes = size_t(ceildiv(n_seg, int64_t(32))) * 4;
+    void *tab = nullptr, *mask = nullptr, *skip = nullptr, *count_dev = nullptr;
+    bool ok = arena_malloc(&tab, tab_bytes, GKOC_MEM_INDICES) == GKOC_OK &&
+              arena_malloc(&mask, mask_bytes, GKOC_MEM_INDICES) == GKOC_OK &&
+              arena_malloc(&skip, skip_bytes, GKOC_MEM_INDICES) == GKOC_OK &&
+              arena_malloc(&count_dev, 8, GKOC_MEM_VECTOR) == GKOC_OK;
+    unsigned long long count = 0;
+    if (ok) {
+        csr_offsets_build_kernel<int32_t><<<dim3(unsigned(ceildiv(n_seg, int64_t(4)))), dim3(256), 0, st>>>(
+            n_rows, row_ptrs, col_idxs, static_cast<int32_t*>(tab), static_cast<uint32_t*>(mask));
+        csr_offsets_finish_kernel<<<dim3(1), dim3(1024), 0, st>>>(
+            n_seg, static_cast<const int32_t*>(tab), lng.count > 0 ? lng.bits : nullptr,
+            static_cast<uint32_t*>(skip), static_cast<unsigned long long*>(count_dev));
+        ok = hipGetLastError() == hipSuccess &&
+             hipMemcpyAsync(&count, count_dev, 8, hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipStreamSynchronize(st) == hipSuccess;
+    }
+    (void)hipGetLastError();
+    if (count_dev) (void)arena_free(count_dev);
+    pl.n_seg = n_seg;
+    pl.eligible = ok ? int64_t(count) : 0;
+    if (!ok || pl.eligible == 0 || pl.eligible * 100 < n_seg * offsets_min_share) {
+        if (tab) (void)arena_free(tab);
+        if (mask) (void)arena_free(mask);
+        if (skip) (void)arena_free(skip);
+        // too few eligible segments: rejected for good; an analysis that FAILED (no memory, a stream error) is
+        // tried again by the next product
+        if (ok) pl.state = 2;
+        return GKOC_OK;
+    }
+    pl.state = 1;
+    pl.seg_tab = static_cast<int32_t*>(tab);
+    pl.row_mask = static_cast<uint32_t*>(mask);
+    pl.bytes = int64_t(tab_bytes + mask_bytes);
+    if (pl.eligible == n_seg) {
+        (void)arena_free(skip);        // every segment is this kernel's: the row-segment kernel is not launched
+    } else {
+        pl.skip = static_cast<uint32_t*>(skip);
+        pl.with_long = lng.count > 0;
+        pl.bytes += int64_t(skip_bytes);
+    }
+    return GKOC_OK;
+}
+
+// plans that made room in the cache while the mutex was held: released when the holder is destroyed, which the
+// callers arrange to happen AFTER their lock is gone (declared in front of it)
+struct evicted_plans {
+    std::vector<offsets_plan> v;
+    ~evicted_plans() { offsets_release(v); }
+};
+
+// The plan this product may use, or nullptr.  The caller holds g_off_mtx.
+offsets_plan* offsets_plan_for(hipStream_t st, int64_t n_rows, int64_t n_cols, const int32_t* row_ptrs,
+                               const int32_t* col_idxs, const csr_long_info& lng, std::vector<offsets_plan>* evicted)
+{
+    const int64_t mode = tune_value(GKOC_TUNE_CSR_OFFSETS);
+    if (mode == 2 || row_ptrs == nullptr || col_idxs == nullptr || n_cols < 1 ||
+        n_rows >= (int64_t(1) << 31) - 64 || n_cols >= (int64_t(1) << 31)) {
+        return nullptr;
+    }
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+    const offsets_key key{dev, row_ptrs, col_idxs, n_rows};
+    auto it = g_off_cache.find(key);
+    if (it == g_off_cache.end()) {
+        const size_t rp_bytes = arena_allocation_bytes(row_ptrs), ci_bytes = arena_allocation_bytes(col_idxs);
+        if (rp_bytes == 0 || ci_bytes == 0) return nullptr;
+        if (g_off_cache.size() >= offsets_cache_cap) {
+            auto oldest = g_off_cache.begin();
+            for (auto jt = g_off_cache.begin(); jt != g_off_cache.end(); ++jt) {
+                if (jt->second.seq < oldest->second.seq) oldest = jt;
+            }
+            evicted->push_back(oldest->second);      // (released by the caller once the mutex is free)
+            g_off_cache.erase(oldest);
+        }
+        static uint64_t arrivals = 0;
+        offsets_plan fresh;
+        fresh.seq = ++arrivals;
+        fresh.rp_bytes = rp_bytes;
+        fresh.ci_bytes = ci_bytes;
+        it = g_off_cache.emplace(key, fresh).first;
+        g_csr_offsets_cached.store(int(g_off_cache.size()));
+        if (mode != 1) return nullptr;      // the first product of these arrays
+    }
+    offsets_plan& pl = it->second;
+    if (pl.state == 0) {
+        if (stream_is_capturing(st)) return nullptr;
+        (void)offsets_build(st, n_rows, row_ptrs, col_idxs, lng, pl);
+    }
+    if (pl.state != 1) return nullptr;
+    // the row-segment kernel beside this one must leave out what the plan's skip bits say, and somebody must
+    // do the long-flagged segments: only with the flags the plan was built with
+    if (pl.skip != nullptr && pl.with_long != (lng.count > 0)) return nullptr;
+    return &pl;
+}
+
+// the product of the plan's segments
+template <typename T, bool ADV, bool DOT>
+void launch_offsets_kernel(hipStream_t st, const offsets_plan& pl, const segment_plan& p, int64_t n_rows,
+                           int64_t n_cols, const T* alpha, const int32_t* row_ptrs, const T* vals, const T* b,
+                           const T* beta, T* c, T* dot_partial)
+{
+    const dim3 grid(static_cast<unsigned>(p.n_waves)), block(64);
+    csr_spmv_pipe3_kernel_offsets<T, ADV, DOT><<<grid, block, 0, st>>>(
+        int32_t(n_rows), int32_t(n_cols), p.n_seg, p.spw, row_ptrs, vals, b, c, alpha, beta, pl.seg_tab,
+        pl.row_mask, dot_partial);
+}
+
 // The hub rows' kernels run BEHIND the row-segment kernel on the caller's stream.  (Round 6 also ran them
 // BESIDE it - a side stream per calling stream, forked in front of the product and joined behind it by two
 // events; the two kernels write disjoint rows of c.  The heavy-tailed stand-in took 245.7 us that way
@@ -381,7 +551,7 @@ int launch_hub_rows(hipStream_t st, const csr_long_info& lng, int64_t n_rows, co
 // One right-hand side - and whatever the launchers above do not take: the kernel walks nrhs columns one
 // after the other.
 template <typename T, typename I, bool ADV>
-int launch_csr_single(gkoc_stream_t s, int64_t n_rows, const T* alpha, const I* row_ptrs, const I* col_idxs,
+int launch_csr_single(gkoc_stream_t s, int64_t n_rows, int64_t n_cols, const T* alpha, const I* row_ptrs, const I* col_idxs,
                       const T* vals, const T* b, int64_t ldb, const T* beta, T* c, int64_t ldc, int64_t nrhs)
 {
     using lay = pipe_layout<T>;
@@ -392,6 +562,21 @@ int launch_csr_single(gkoc_stream_t s, int64_t n_rows, const T* alpha, const I* 
         GKOC_TRY((long_info_of<T, I>(s, n_rows, row_ptrs, &lng)));
     }
     const uint32_t* seg_skip = lng.count > 0 ? lng.bits : nullptr;
+    // stencil-like structure seen before: the column-offset plan (csr_offsets.hpp) takes its eligible
+    // segments, the row-segment kernel below the others.  Held to the end: a plan is not released while its
+    // product is being enqueued.
+    constexpr bool offsets_type = std::is_same<I, int32_t>::value && (sizeof(T) == 8 || sizeof(T) == 4);
+    evicted_plans evicted;
+    std::unique_lock<std::mutex> plan_lock(g_off_mtx, std::defer_lock);
+    offsets_plan* plan = nullptr;
+    if constexpr (offsets_type) {
+        if (nrhs == 1 && ldb == 1 && ldc == 1 && vals != nullptr && b != nullptr &&
+            reinterpret_cast<uintptr_t>(vals) % 16 == 0 && tune_value(GKOC_TUNE_CSR_OFFSETS) != 2) {
+            plan_lock.lock();
+            plan = offsets_plan_for(as_stream(s), n_rows, n_cols, row_ptrs, col_idxs, lng, &evicted.v);
+            if (plan == nullptr) plan_lock.unlock();
+        }
+    }
     // GKOC_TUNE_CSR_SEGS_PER_WAVE forces 1 or 2 segments per wave (round 6 tried "up to eight for matrices
     // with short rows" - the heavy-tailed stand-in 256 us with one, 261 with two, 276 with four, 320 with eight
     // segments; 5-pt 4096^2 325 / 289 / 325 / 315; profiles/r06/r06_segments_per_wave.txt: the size rule
@@ -400,6 +585,16 @@ int launch_csr_single(gkoc_stream_t s, int64_t n_rows, const T* alpha, const I* 
     segment_plan p;
     GKOC_TRY(plan_segments(n_rows, &p, tune_value(GKOC_TUNE_CSR_SEGS_PER_WAVE)));
     const dim3 grid(static_cast<unsigned>(p.n_waves)), block(64);
+    if constexpr (offsets_type) {
+        if (plan != nullptr) {
+            launch_offsets_kernel<T, ADV, false>(as_stream(s), *plan, p, n_rows, n_cols, alpha, row_ptrs, vals, b,
+                                                 beta, c, static_cast<T*>(nullptr));
+            GKOC_LAUNCH_OK();
+            ++plan->products;
+            if (plan->skip == nullptr) return GKOC_OK;      // every segment was eligible
+            seg_skip = plan->skip;
+        }
+    }
     // XCD-contiguous wave order needs enough waves per XCD to keep the in-order
     // window argument valid; below that the plain order is used
     // ... and is the default for a matrix WITH HUB ROWS (flagged segments): its gathers go all over b, and with
@@ -481,7 +676,7 @@ int launch_csr(gkoc_stream_t s, int64_t n_rows, int64_t n_cols, const T* alpha,
         return launch_csr_pair<T, I, ADV>(s, n_rows, alpha, row_ptrs, col_idxs, vals, b, ldb, beta, c, ldc);
     }
     // (two columns whose matrix streams are not aligned for vector loads: one pass per column)
-    return launch_csr_single<T, I, ADV>(s, n_rows, alpha, row_ptrs, col_idxs, vals, b, ldb, beta, c, ldc, nrhs);
+    return launch_csr_single<T, I, ADV>(s, n_rows, n_cols, alpha, row_ptrs, col_idxs, vals, b, ldb, beta, c, ldc, nrhs);
 }
 
 // The distributed product in ONE kernel (csr_spmv_pipe.hpp, GATE): the interior rows of the rank's
@@ -687,6 +882,21 @@ int launch_csr_dot(gkoc_stream_t s, int64_t n, const I* row_ptrs,
     const dim3 grid(static_cast<unsigned>(p.n_waves)), block(64);
     const bool vec_ok = streams_aligned(vals, col_idxs, 4);      // (for four entries whatever the type)
     const int xcd_map = (tune_value(GKOC_TUNE_CSR_XCD_MAP) == 1 && p.n_waves >= 8 * 1024) ? 1 : 0;
+    // the column-offset plan, where EVERY segment is eligible (a wave's part of <b, c> comes from one kernel)
+    if constexpr (std::is_same<I, int32_t>::value) {
+        if (vals != nullptr && reinterpret_cast<uintptr_t>(vals) % 16 == 0 && tune_value(GKOC_TUNE_CSR_OFFSETS) != 2) {
+            evicted_plans evicted;
+            std::lock_guard<std::mutex> plan_lock(g_off_mtx);
+            offsets_plan* plan = offsets_plan_for(as_stream(s), n, n, row_ptrs, col_idxs, csr_long_info{}, &evicted.v);
+            if (plan != nullptr && plan->skip == nullptr) {
+                launch_offsets_kernel<T, false, true>(as_stream(s), *plan, p, n, n, static_cast<const T*>(nullptr),
+                                                      row_ptrs, vals, b, static_cast<const T*>(nullptr), c, partial);
+                GKOC_LAUNCH_OK();
+                ++plan->products;
+                return fold_partials<T>(s, p.n_waves, partial, scratch, dot_out, false);
+            }
+        }
+    }
     // four waves per SIMD, like the plain product: the dot's registers (and, since round 6, the loop over runs
     // of unflagged segments) had taken the double / int32 kernel to 133 VGPRs = three waves - 985 -> 1107 us on
     // L256 (profiles/r06/r06_bench_kernel_stats_regression.csv); with the bound the compiler stays at 128
@@ -844,6 +1054,30 @@ __global__ __launch_bounds__(64) void sort_rows_kernel(
 
 }  // namespace
 
+// (common.hpp) the index array(s) in [first, first + bytes) are freed or written: what was derived from them goes
+void csr_offsets_forget(const void* first, size_t bytes)
+{
+    const char* lo = static_cast<const char*>(first);
+    const char* hi = lo + (bytes ? bytes : 1);
+    std::vector<offsets_plan> gone;
+    {
+        std::lock_guard<std::mutex> g(g_off_mtx);
+        for (auto it = g_off_cache.begin(); it != g_off_cache.end();) {
+            const char* rp = static_cast<const char*>(std::get<1>(it->first));
+            const char* ci = static_cast<const char*>(std::get<2>(it->first));
+            // [lo, hi) overlaps either allocation (a copy into the middle of an array counts)
+            if ((lo < rp + it->second.rp_bytes && rp < hi) || (lo < ci + it->second.ci_bytes && ci < hi)) {
+                gone.push_back(it->second);
+                it = g_off_cache.erase(it);
+            } else {
+                ++it;
+            }
+        }
+        g_csr_offsets_cached.store(int(g_off_cache.size()));
+    }
+    offsets_release(gone);
+}
+
 // Complex values (round 6).  The product of round 5 was one thread per row walking global memory: 15.0 ms on
 // the 27-pt 256^3 matrix with complex<double> values = 0.63 TB/s, 78 % of a CbGmres<complex<double>> iteration
 // (profiles/r06/r06_cb_gmres_complex_kernel_stats.csv).  The row-segment kernel is a template on the value
@@ -971,6 +1205,7 @@ using namespace gkoc;
         T* vals)                                                               \
     {                                                                          \
         if (n_rows <= 0) return GKOC_OK;                                       \
+        gkoc::csr_structure_written(col_idxs);                                 \
         sort_rows_kernel<T, I>                                                 \
             <<<dim3(unsigned(ceildiv(n_rows, 64))), dim3(64), 0,               \
                as_stream(s)>>>(n_rows, row_ptrs, col_idxs, vals);              \
@@ -990,6 +1225,7 @@ GKOC_DEF_CSR(float, f32, int64_t, i64)
         T* vals)                                                               \
     {                                                                          \
         if (n_rows <= 0) return GKOC_OK;                                       \
+        gkoc::csr_structure_written(col_idxs);                                 \
         sort_rows_kernel<T, I>                                                 \
             <<<dim3(unsigned(ceildiv(n_rows, 64))), dim3(64), 0,               \
                as_stream(s)>>>(n_rows, row_ptrs, col_idxs, vals);              \
@@ -1033,6 +1269,40 @@ GKOC_DEF_CSR_GATED_DOT(double, f64, int32_t, i32)
 GKOC_DEF_CSR_GATED_DOT(double, f64, int64_t, i64)
 GKOC_DEF_CSR_GATED_DOT(float, f32, int32_t, i32)
 GKOC_DEF_CSR_GATED_DOT(float, f32, int64_t, i64)
+
+extern "C" int gkoc_csr_structure_changed(const void* index_array)
+{
+    gkoc::csr_structure_written(index_array);
+    return GKOC_OK;
+}
+
+extern "C" int gkoc_csr_plan_info(const void* row_ptrs, const void* col_idxs, int* state, int64_t* eligible_segments,
+                                  int64_t* segments, int64_t* bytes, int64_t* products_by_plan)
+{
+    int st = -1;
+    int64_t el = 0, ns = 0, by = 0, pr = 0;
+    int dev = 0;
+    GKOC_HIP(hipGetDevice(&dev));
+    {
+        std::lock_guard<std::mutex> g(gkoc::g_off_mtx);
+        for (const auto& kv : gkoc::g_off_cache) {
+            if (std::get<0>(kv.first) == dev && std::get<1>(kv.first) == row_ptrs &&
+                std::get<2>(kv.first) == col_idxs) {
+                st = kv.second.state;
+                el = kv.second.eligible;
+                ns = kv.second.n_seg;
+                by = kv.second.bytes;
+                pr = kv.second.products;
+            }
+        }
+    }
+    if (state) *state = st;
+    if (eligible_segments) *eligible_segments = el;
+    if (segments) *segments = ns;
+    if (bytes) *bytes = by;
+    if (products_by_plan) *products_by_plan = pr;
+    return GKOC_OK;
+}
 
 extern "C" int gkoc_csr_spmv_gated_fits(int64_t n_rows, int64_t head_rows, int64_t tail_rows)
 {

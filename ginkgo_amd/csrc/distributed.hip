@@ -363,6 +363,7 @@ using namespace gkoc;
         int64_t* nnz_local_host, int64_t* nnz_nl_host,                         \
         int64_t* n_nl_rows_host)                                               \
     {                                                                          \
+        gkoc::csr_structure_written(local_row_ptrs); gkoc::csr_structure_written(nl_row_ptrs_full); \
         return split_count<I>(s, n_rows, row_ptrs, cols, col_lo, col_hi,       \
                               n_global_cols, col_map, local_row_ptrs,          \
                               nl_row_ptrs_full, n_halo_host, nnz_local_host,   \
@@ -376,6 +377,7 @@ GKOC_DEF_DIST_IDX(int64_t, i64)
         gkoc_stream_t s, int64_t n_list, const I* rows, const I* row_ptrs,     \
         I* out_ptrs, int64_t* nnz_host)                                        \
     {                                                                          \
+        gkoc::csr_structure_written(out_ptrs);                                 \
         GKOC_REQUIRE(out_ptrs && nnz_host && n_list >= 0, GKOC_E_INVALID,      \
                      "bad argument");                                          \
         hipStream_t st = as_stream(s);                                         \
@@ -402,6 +404,7 @@ GKOC_DEF_DIST_BND_IDX(int64_t, i64)
         I* local_cols, T* local_vals, I* nl_rows, I* nl_ptrs, I* nl_cols,      \
         T* nl_vals, I* recv_gidx)                                              \
     {                                                                          \
+        gkoc::csr_structure_written(local_cols); gkoc::csr_structure_written(nl_ptrs); gkoc::csr_structure_written(nl_cols); \
         return split_fill<T, I>(s, n_rows, row_ptrs, cols, vals, col_lo,       \
                                 col_hi, n_global_cols, col_map,                \
                                 local_row_ptrs, nl_row_ptrs_full, local_cols,  \
@@ -414,6 +417,7 @@ GKOC_DEF_DIST_BND_IDX(int64_t, i64)
         int64_t halo_base, const I* col_map, const I* out_ptrs, I* out_cols,   \
         T* out_vals)                                                           \
     {                                                                          \
+        gkoc::csr_structure_written(out_cols);                                 \
         if (n_list <= 0) return GKOC_OK;                                       \
         GKOC_REQUIRE(halo_base >= col_hi - col_lo, GKOC_E_INVALID,             \
                      "halo_base inside the local columns");                    \

@@ -433,6 +433,7 @@ using namespace gkoc;
         gkoc_stream_t s, int64_t n_block_rows, int64_t block_size, const I* row_ptrs,             \
         const I* col_idxs, const T* vals, I* csr_row_ptrs, I* csr_col_idxs, T* csr_vals)          \
     {                                                                                             \
+        gkoc::csr_structure_written(csr_row_ptrs); gkoc::csr_structure_written(csr_col_idxs);     \
         FB_CHECK_BS(block_size);                                                                  \
         GKOC_REQUIRE(n_block_rows >= 0, GKOC_E_INVALID, "Fbcsr: negative size");                  \
         FB_CHECK_PTR(csr_row_ptrs, true);                                                         \

@@ -814,6 +814,7 @@ GKOC_DEF_ELL_MIXED(int64_t, i64)
                                                I* row_idxs, I* col_idxs,       \
                                                T* vals)                        \
     {                                                                          \
+        gkoc::csr_structure_written(row_idxs); gkoc::csr_structure_written(col_idxs); \
         if (nnz <= 0) return GKOC_OK;                                          \
         int64_t nb = ceildiv(nnz, 256);                                        \
         if (nb > max_stream_blocks) nb = max_stream_blocks;                    \
@@ -843,6 +844,7 @@ GKOC_DEF_ELL_MIXED(int64_t, i64)
                                                I* row_idxs, I* col_idxs,       \
                                                T* vals)                        \
     {                                                                          \
+        gkoc::csr_structure_written(row_idxs); gkoc::csr_structure_written(col_idxs); \
         if (nnz <= 0) return GKOC_OK;                                          \
         int64_t nb = ceildiv(nnz, 256);                                        \
         if (nb > max_stream_blocks) nb = max_stream_blocks;                    \
@@ -934,6 +936,7 @@ GKOC_DEF_FMT_CONVERT(gkoc_c64, c64, int64_t, i64)
     extern "C" int gkoc_convert_idxs_to_ptrs_##IN(                             \
         gkoc_stream_t s, int64_t num_idxs, const I* idxs, int64_t n, I* ptrs)  \
     {                                                                          \
+        gkoc::csr_structure_written(ptrs);                                     \
         GKOC_REQUIRE(num_idxs >= 0 && n >= 0, GKOC_E_INVALID, "negative size"); \
         idxs_to_ptrs_kernel<I>                                                 \
             <<<dim3(blocks_for(num_idxs + 1)), dim3(256), 0, as_stream(s)>>>(  \
@@ -944,12 +947,14 @@ GKOC_DEF_FMT_CONVERT(gkoc_c64, c64, int64_t, i64)
     extern "C" int gkoc_prefix_sum_nonnegative_##IN(gkoc_stream_t s,           \
                                                     I* counts, int64_t n)      \
     {                                                                          \
+        if (n > 0) gkoc::csr_structure_written(counts, size_t(n) * sizeof(I)); \
         return device_exclusive_scan<I>(as_stream(s), counts, n);              \
     }                                                                          \
     extern "C" int gkoc_prefix_sum_nonnegative_checked_##IN(                   \
         gkoc_stream_t s, I* counts, int64_t n)                                 \
     {                                                                          \
         int over = 0;                                                          \
+        if (n > 0) gkoc::csr_structure_written(counts, size_t(n) * sizeof(I)); \
         const int rc = scan_overflows(as_stream(s), counts, n - 1, sizeof(I),  \
                                       (unsigned long long)(std::numeric_limits<I>::max()), \
                                       &over);                                  \
@@ -961,6 +966,7 @@ GKOC_DEF_FMT_CONVERT(gkoc_c64, c64, int64_t, i64)
                                         I value)                               \
     {                                                                          \
         if (n <= 0) return GKOC_OK;                                            \
+        gkoc::csr_structure_written(data, size_t(n) * sizeof(I));              \
         int64_t nb = ceildiv(n, 256);                                          \
         if (nb > max_stream_blocks) nb = max_stream_blocks;                    \
         fill_idx_kernel<I><<<dim3(unsigned(nb)), dim3(256), 0, as_stream(s)>>>( \
@@ -972,6 +978,7 @@ GKOC_DEF_FMT_CONVERT(gkoc_c64, c64, int64_t, i64)
                                             int64_t n)                         \
     {                                                                          \
         if (n <= 0) return GKOC_OK;                                            \
+        gkoc::csr_structure_written(data, size_t(n) * sizeof(I));              \
         int64_t nb = ceildiv(n, 256);                                          \
         if (nb > max_stream_blocks) nb = max_stream_blocks;                    \
         fill_idx_kernel<I><<<dim3(unsigned(nb)), dim3(256), 0, as_stream(s)>>>( \
@@ -1009,6 +1016,7 @@ extern "C" int gkoc_narrow_i64_to_i32(gkoc_stream_t s, int64_t n, const int64_t*
 extern "C" int gkoc_convert_idxs_to_ptrs_i32_i64(gkoc_stream_t s, int64_t num_idxs,
                                                  const int32_t* idxs, int64_t n, int64_t* ptrs)
 {
+    gkoc::csr_structure_written(ptrs);
     GKOC_REQUIRE(num_idxs >= 0 && n >= 0, GKOC_E_INVALID, "negative size");
     idxs_to_ptrs_kernel<int32_t, int64_t>
         <<<dim3(blocks_for(num_idxs + 1)), dim3(256), 0, as_stream(s)>>>(num_idxs, idxs, n, ptrs);
@@ -1019,6 +1027,7 @@ extern "C" int gkoc_convert_idxs_to_ptrs_i32_i64(gkoc_stream_t s, int64_t num_id
 extern "C" int gkoc_convert_idxs_to_ptrs_i64_i32(gkoc_stream_t s, int64_t num_idxs,
                                                  const int64_t* idxs, int64_t n, int32_t* ptrs)
 {
+    gkoc::csr_structure_written(ptrs);
     GKOC_REQUIRE(num_idxs >= 0 && n >= 0, GKOC_E_INVALID, "negative size");
     idxs_to_ptrs_kernel<int64_t, int32_t>
         <<<dim3(blocks_for(num_idxs + 1)), dim3(256), 0, as_stream(s)>>>(num_idxs, idxs, n, ptrs);

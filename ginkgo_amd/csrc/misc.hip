@@ -247,6 +247,7 @@ extern "C" int gkoc_convert_precision_f64_f32(gkoc_stream_t s, int64_t n, const 
     extern "C" int gkoc_diagonal_convert_to_csr_##TN##_##IN(gkoc_stream_t s, int64_t n, const T* diag,      \
                                                             I* row_ptrs, I* cols, T* vals)                  \
     {                                                                                                       \
+        gkoc::csr_structure_written(row_ptrs); gkoc::csr_structure_written(cols);                           \
         diag_to_csr_kernel<T, I><<<dim3(grid_of(n + 1)), dim3(256), 0, as_stream(s)>>>(n, diag, row_ptrs,   \
                                                                                       cols, vals);          \
         GKOC_LAUNCH_OK();                                                                                   \
@@ -285,6 +286,7 @@ GKOC_DEF_MISC_TI(gkoc_c64, c64, int64_t, i64)
                                                           const I* diag_prefix_sum, I* adj_ptrs,            \
                                                           I* adj_idxs)                                      \
     {                                                                                                       \
+        gkoc::csr_structure_written(adj_ptrs); gkoc::csr_structure_written(adj_idxs);                       \
         remove_diag_kernel<I><<<dim3(grid_of(n_rows + 1)), dim3(256), 0, as_stream(s)>>>(                   \
             n_rows, row_ptrs, cols, diag_prefix_sum, adj_ptrs, adj_idxs);                                   \
         GKOC_LAUNCH_OK();                                                                                   \
@@ -310,6 +312,7 @@ extern "C" int gkoc_fill_array_small(gkoc_stream_t s, void* data, int64_t n, int
 {
     GKOC_REQUIRE(elem_bytes == 1 || elem_bytes == 2 || elem_bytes == 4, GKOC_E_INVALID, "elem_bytes");
     if (n <= 0) return GKOC_OK;
+    gkoc::csr_structure_written(data, size_t(n) * size_t(elem_bytes));
     const dim3 g(grid_of(n));
     if (elem_bytes == 1) {
         fill_small_kernel<uint8_t><<<g, dim3(256), 0, as_stream(s)>>>(n, static_cast<uint8_t*>(data), uint8_t(pattern));

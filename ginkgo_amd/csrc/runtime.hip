@@ -115,7 +115,7 @@ void gate_fence_policy_set(int policy) { g_gate_fence_policy.store(policy < 0 ? 
 // GKOC_TUNE_<n>, else the default chosen by measurement
 int64_t tune_value(int key)
 {
-    static const int64_t defaults[tune_num_keys] = {0, 0, 0, 2, 1, 0, 0, 0, 100, 0, 1, 0, 1, 0, 0, 0, 0, 1};   // measured: the XCD-contiguous order loses 1-8 %
+    static const int64_t defaults[tune_num_keys] = {0, 0, 0, 2, 1, 0, 0, 0, 100, 0, 1, 0, 1, 0, 0, 0, 0, 1, 0};   // measured: the XCD-contiguous order loses 1-8 %
     if (key < 0 || key >= tune_num_keys) return 0;
     if (!g_tune_set[key]) {
         char name[32];
@@ -301,6 +301,7 @@ int gkoc_malloc_managed(void** ptr, size_t bytes, unsigned int flags)
 int gkoc_free(void* ptr)
 {
     gkoc::csr_long_rows_forget(ptr);     // what csr::spmv remembers about a matrix at this address (csr_spmv.hip)
+    gkoc::csr_structure_written(ptr);
     return arena_free(ptr);
 }
 
@@ -331,6 +332,7 @@ int gkoc_tune_get(int key, int64_t* value)
 int gkoc_memcpy_h2d(void* dst, const void* src, size_t bytes, gkoc_stream_t s)
 {
     if (bytes == 0) return GKOC_OK;
+    gkoc::csr_structure_written(dst, bytes);
     GKOC_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, as_stream(s)));
     return GKOC_OK;
 }
@@ -377,6 +379,7 @@ int gkoc_memcpy_d2h(void* dst, const void* src, size_t bytes, gkoc_stream_t s)
 int gkoc_memcpy_d2d(void* dst, const void* src, size_t bytes, gkoc_stream_t s)
 {
     if (bytes == 0) return GKOC_OK;
+    gkoc::csr_structure_written(dst, bytes);
     // a scalar or two (a reduction's result handed on): one wave of our own instead of the
     // runtime's copy path
     // - only where a kernel on the CURRENT device may dereference both pointers: with several devices in
@@ -430,6 +433,7 @@ int gkoc_stream_query(gkoc_stream_t s, int* done)
 int gkoc_memset(void* dst, int value, size_t bytes, gkoc_stream_t s)
 {
     if (bytes == 0) return GKOC_OK;
+    gkoc::csr_structure_written(dst, bytes);
     GKOC_HIP(hipMemsetAsync(dst, value, bytes, as_stream(s)));
     return GKOC_OK;
 }

@@ -123,6 +123,7 @@ using namespace gkoc;
         gkoc_stream_t s, int nd, int64_t g, int restricted, int64_t z0,        \
         int64_t nz, I* row_ptrs, int64_t* nnz_host)                            \
     {                                                                          \
+        gkoc::csr_structure_written(row_ptrs);                                 \
         int rc = check_desc(nd, g, z0, nz);                                    \
         if (rc != GKOC_OK) return rc;                                          \
         const int64_t n_local = nz * (nd == 3 ? g * g : g);                    \
@@ -150,6 +151,7 @@ GKOC_DEF_STENCIL_PTRS(int64_t, i64)
         gkoc_stream_t s, int nd, int64_t g, int restricted, int64_t z0,        \
         int64_t nz, const I* row_ptrs, I* cols, T* vals)                       \
     {                                                                          \
+        gkoc::csr_structure_written(cols);                                     \
         int rc = check_desc(nd, g, z0, nz);                                    \
         if (rc != GKOC_OK) return rc;                                          \
         const int64_t n_local = nz * (nd == 3 ? g * g : g);                    \

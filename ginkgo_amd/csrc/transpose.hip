@@ -90,6 +90,7 @@ extern "C" size_t gkoc_csr_transpose_workspace_bytes(int64_t nnz, int64_t n_cols
         const I* col_idxs, const T* vals, int64_t nnz, I* t_row_ptrs, I* t_col_idxs,        \
         T* t_vals, void* work, size_t work_bytes)                                           \
     {                                                                                       \
+        gkoc::csr_structure_written(t_row_ptrs); gkoc::csr_structure_written(t_col_idxs);   \
         GKOC_REQUIRE(n_rows >= 0 && n_cols >= 0 && nnz >= 0, GKOC_E_INVALID,                \
                      "negative dimension");                                                 \
         GKOC_REQUIRE(t_row_ptrs, GKOC_E_INVALID, "null pointer");                           \

@@ -404,6 +404,7 @@ extern "C" int gkoc_trs_struct_levels(gkoc_trs_struct_t t, int64_t* level_ptrs_h
                                                                    const I* row_ptrs, const I* col_idxs,       \
                                                                    I* l_row_ptrs, I* u_row_ptrs)               \
     {                                                                                                          \
+        gkoc::csr_structure_written(l_row_ptrs); gkoc::csr_structure_written(u_row_ptrs);                      \
         return row_ptrs_l_u<I>(s, n_rows, row_ptrs, col_idxs, l_row_ptrs, u_row_ptrs);                         \
     }
 GKOC_DEF_TRS_I(int32_t, i32)
@@ -428,6 +429,7 @@ GKOC_DEF_TRS_I(int64_t, i64)
         gkoc_stream_t s, int64_t n_rows, const I* rp, const I* ci, const T* v, double weight, const I* l_rp,   \
         I* l_ci, T* l_v)                                                                                       \
     {                                                                                                          \
+        gkoc::csr_structure_written(l_ci);                                                                     \
         return weighted_l_u<false, T, I>(s, n_rows, rp, ci, v, weight, l_rp, l_ci, l_v, nullptr, nullptr,      \
                                          nullptr);                                                             \
     }                                                                                                          \
@@ -435,6 +437,7 @@ GKOC_DEF_TRS_I(int64_t, i64)
         gkoc_stream_t s, int64_t n_rows, const I* rp, const I* ci, const T* v, double weight, const I* l_rp,   \
         I* l_ci, T* l_v, const I* u_rp, I* u_ci, T* u_v)                                                       \
     {                                                                                                          \
+        gkoc::csr_structure_written(l_ci); gkoc::csr_structure_written(u_ci);                                  \
         return weighted_l_u<true, T, I>(s, n_rows, rp, ci, v, weight, l_rp, l_ci, l_v, u_rp, u_ci, u_v);       \
     }
 GKOC_DEF_TRS(double, f64, int32_t, i32)

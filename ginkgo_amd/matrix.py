@@ -338,6 +338,13 @@ class Csr(_SparseBase):
              self.size[0], self.row_ptrs, self.col_idxs, self.values)
         return self
 
+    def structure_changed(self):
+        """row_ptrs / col_idxs were written by the caller (a torch operation, another library) after the
+        matrix had been multiplied: what the SpMV derived from them is dropped (gkoc_csr_structure_changed)"""
+        call("gkoc_csr_structure_changed", C.c_void_p(self.row_ptrs.data_ptr()))
+        call("gkoc_csr_structure_changed", C.c_void_p(self.col_idxs.data_ptr()))
+        return self
+
     def convert_to_ell(self, num_stored_per_row=None, stride=None):
         it = IT[self.col_idxs.dtype]
         if num_stored_per_row is None:

@@ -231,6 +231,12 @@ int gkoc_arena_probe(const void* x, size_t x_bytes, void* y, int read_kb_per_wav
 #define GKOC_TUNE_JACOBI_REHOME 17   /* binding for the unmodified Ginkgo core: 1 (default) jacobi::generate re-allocates
                                       an owning block array that sits in a memory class with vectors in the class of
                                       the matrix' column indices before it fills it; 0: left where raw_alloc put it */
+#define GKOC_TUNE_CSR_OFFSETS 18     /* csr::spmv / advanced_spmv / gkoc_x_csr_spmv_dot, double or float values, 32-bit
+                                      indices, one right-hand side with unit stride: the cached column-offset plan
+                                      (gkoc_csr_structure_changed below, csrc/csr_offsets.hpp).  0 (default): built by
+                                      the second product on the same (row_ptrs, col_idxs), 1: by the first, 2: never
+                                      (the row-segment kernel alone).  Only ever
+                                      for index arrays that are live allocations of gkoc_malloc / gkoc_malloc_role. */
 int gkoc_tune_set(int key, int64_t value);
 int gkoc_tune_get(int key, int64_t* value);
 /* HipHostAllocator (pinned host memory) and HipUnifiedAllocator (managed memory,
@@ -315,6 +321,34 @@ GKOC_DECL_CSR(double, f64, int32_t, i32)
 GKOC_DECL_CSR(double, f64, int64_t, i64)
 GKOC_DECL_CSR(float, f32, int32_t, i32)
 GKOC_DECL_CSR(float, f32, int64_t, i64)
+
+/* The column-offset plan of a CSR matrix (GKOC_TUNE_CSR_OFFSETS, csrc/csr_offsets.hpp).  From the second product
+ * on the same (row_ptrs, col_idxs) the library may keep a description DERIVED FROM THE TWO INDEX ARRAYS (per
+ * 64-row segment the distinct values of col - row, per row which of them it stores) and multiply through it
+ * without reading col_idxs again.  Values are always read live.  Results are bit-identical either way.
+ * CONTRACT (the same kind as Ginkgo's srow): the description is dropped when either array is passed to gkoc_free,
+ * when gkoc_memcpy_h2d / gkoc_memcpy_d2d / gkoc_memset / gkoc_fill_array_{i32,i64,small} /
+ * gkoc_fill_seq_array_{i32,i64} / gkoc_prefix_sum_nonnegative[_checked]_{i32,i64} write a range that overlaps
+ * either allocation, and when either array is an OUTPUT index array (a non-const I*, int32_t* or int64_t*
+ * parameter) of one of: gkoc_csr_sort_by_column_index, gkoc_csr_transpose, gkoc_csr_permute, gkoc_csr_submatrix[_from_index_set],
+ * gkoc_csr_add_diagonal_fill, gkoc_{dense,cdense,ell,sellp,hybrid,fbcsr,diagonal}_[convert_]to_csr,
+ * gkoc_convert_idxs_to_ptrs, gkoc_convert_ptrs_to_idxs, gkoc_aos_to_soa, gkoc_sort_row_major,
+ * gkoc_remove_zeros_fill, gkoc_sum_duplicates_fill, gkoc_stencil_row_ptrs, gkoc_stencil_fill,
+ * gkoc_sparsity_csr_remove_diagonal, gkoc_factorization_initialize_row_ptrs_l_u, gkoc_sor_initialize_weighted_l[_u],
+ * gkoc_dist_split_count / _fill, gkoc_dist_boundary_count / _fill.  Any other writer - another entry of this
+ * library included - is the caller's business: a caller that writes row_ptrs or col_idxs of a
+ * matrix ITSELF (a kernel of its own, another library's copy) after the matrix has been multiplied must call
+ * gkoc_csr_structure_changed with either array before the next product.  Only arrays that are live allocations
+ * of gkoc_malloc / gkoc_malloc_role ever get a plan, so an address cannot be reused behind the library's back.
+ * The analysis synchronises the product's stream once; it is never run inside a stream capture (a product
+ * captured there takes the row-segment kernel; a plan that exists already is used without a synchronisation,
+ * and a graph that holds it must not be replayed after the plan was dropped).
+ * gkoc_csr_plan_info: state -1 none, 0 arrays seen once, 1 plan in use, 2 analysed and rejected (fewer than half
+ * of the segments eligible); eligible / all 64-row segments; bytes of device memory of the plan; products that
+ * ran through it.  Any result pointer may be NULL. */
+int gkoc_csr_structure_changed(const void* index_array);
+int gkoc_csr_plan_info(const void* row_ptrs, const void* col_idxs, int* state, int64_t* eligible_segments,
+                       int64_t* segments, int64_t* bytes, int64_t* products_by_plan);
 
 /* --------------------------------------------------------------- ELL SpMV
  * ell::spmv / advanced_spmv  core/matrix/ell_kernels.hpp:20-34
