@@ -1,11 +1,12 @@
 """The cached column-offset plan of the CSR SpMV (csrc/csr_offsets.hpp, launcher in csrc/csr_spmv.hip).
+The matrices, the host model of the plan and the helpers are tests/csr_offsets_cases.py (checked on the CPU by
+tests/test_csr_offsets_cases_cpu.py); the routes that drop a plan are tests/test_csr_offsets_routes_gpu.py.
 
 Index arrays come from the library's allocator even when tiny (only those ever get a plan).  Every product is
 compared BIT FOR BIT (NaN positions included) with the sequential oracle and with the same product under
 GKOC_TUNE_CSR_OFFSETS = 2 (the row-segment kernel alone), runs twice with the same bits, and the plan's own
 counters (gkoc_csr_plan_info) must show that the offsets kernel did the work: the fallback cannot pass alone.
 """
-import contextlib
 import ctypes as C
 import gc
 
@@ -13,77 +14,16 @@ import numpy as np
 import pytest
 import torch
 
+import csr_offsets_cases as oc
+import csr_spmv_cases as sc
+from csr_offsets_cases import (KEY, KEY_LONG_ROWS, KEY_SEGS_PER_WAVE, arena_csr, arena_tensor, band_rows, bits,
+                               check_all_modes, from_rows, key, plain, plan_info, plan_info_at, reference, run,
+                               two_structures)
+
 pytestmark = pytest.mark.gpu
-
-KEY = 18          # GKOC_TUNE_CSR_OFFSETS
-TORCH_T = {np.dtype(np.float64): torch.float64, np.dtype(np.float32): torch.float32}
-BITS = {np.dtype(np.float64): np.uint64, np.dtype(np.float32): np.uint32}
-
-
-@contextlib.contextmanager
-def key(value):
-    from ginkgo_amd import _lib
-    was = C.c_int64(0)
-    _lib.call("gkoc_tune_get", C.c_int(KEY), C.byref(was))
-    _lib.call("gkoc_tune_set", C.c_int(KEY), C.c_int64(value))
-    try:
-        yield
-    finally:
-        _lib.call("gkoc_tune_set", C.c_int(KEY), C.c_int64(was.value))
-
-
-def arena_tensor(ex, arr, role):
-    """a tensor over a gkoc_malloc_role allocation of its own, whatever its size (executor._ArenaBlock)"""
-    from ginkgo_amd.executor import _ArenaBlock, _TYPESTR
-    arr = np.ascontiguousarray(arr)
-    src = torch.from_numpy(arr)
-    with torch.cuda.device(ex.device):
-        block = _ArenaBlock(arr.nbytes, role, arr.shape, _TYPESTR[src.dtype])
-        t = torch.as_tensor(block, device=ex.device)
-    assert t.data_ptr() == block.ptr
-    t.copy_(src)
-    return t
-
-
-def arena_csr(ex, shape, rp, ci, v):
-    import ginkgo_amd as g
-    from ginkgo_amd.executor import MEM_INDICES, MEM_VALUES
-    return g.Csr(ex, shape, arena_tensor(ex, v, MEM_VALUES), arena_tensor(ex, ci.astype(np.int32), MEM_INDICES),
-                 arena_tensor(ex, rp.astype(np.int32), MEM_INDICES))
-
-
-def plan_info(a):
-    return plan_info_at(a.row_ptrs.data_ptr(), a.col_idxs.data_ptr())
-
-
-def plan_info_at(row_ptrs, col_idxs):
-    from ginkgo_amd import _lib
-    st, el, ns, by, pr = C.c_int(-9), C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
-    _lib.call("gkoc_csr_plan_info", C.c_void_p(row_ptrs), C.c_void_p(col_idxs),
-              C.byref(st), C.byref(el), C.byref(ns), C.byref(by), C.byref(pr))
-    return {"state": st.value, "eligible": el.value, "segments": ns.value, "bytes": by.value, "products": pr.value}
-
-
-def bits(x):
-    x = np.ascontiguousarray(x)
-    return x.view(BITS[x.dtype])
 
 
 # ---------------------------------------------------------------- matrices (host, int32)
-def from_rows(rows, n_cols, dtype, seed=0):
-    """rows: list of column lists in STORAGE order; values uniform in +-[0.5, 1.5)"""
-    rp = np.zeros(len(rows) + 1, np.int32)
-    rp[1:] = np.cumsum([len(r) for r in rows])
-    ci = np.array([c for r in rows for c in r], np.int32)
-    rng = np.random.default_rng(seed)
-    v = (rng.uniform(0.5, 1.5, len(ci)) * rng.choice([-1.0, 1.0], len(ci))).astype(dtype)
-    return (len(rows), n_cols), rp, ci, v
-
-
-def band_rows(n, n_cols, offsets):
-    return [[r + o for o in offsets if 0 <= r + o < n_cols] for r in range(n)]
-
-
 def stencil27(oracle, g, dtype, seed=0):
     rp, ci, v = oracle.stencil_csr(3, g)
     rng = np.random.default_rng(seed)
@@ -101,73 +41,6 @@ def stencil_case(oracle, name, dtype):
         n = int(name.split("-")[1])
         return from_rows(band_rows(n, n, (-1, 0, 1)), n, dtype)
     return from_rows(band_rows(100, 300, (-2, 0, 3, 150, 199)), 300, dtype)
-
-
-# ---------------------------------------------------------------- products
-def run(ex, a, b, mode, c0):
-    """one product, twice from the same input (the same bits): the result"""
-    import ginkgo_amd as g
-    n, dtype = a.size[0], b.dtype
-    db = g.Dense.from_numpy(ex, b.reshape(-1, 1))
-    outs = []
-    for _ in range(2):
-        if mode == "dot":
-            from ginkgo_amd import _lib
-            es = dtype.itemsize
-            nbytes = _lib.lib().gkoc_x_workspace_bytes(C.c_int64(n), C.c_size_t(es))
-            work = ex.alloc(((nbytes + es - 1) // es,), TORCH_T[dtype])
-            dc = g.Dense.from_numpy(ex, np.full((n, 1), np.nan, dtype))
-            dot = g.Dense.from_numpy(ex, np.full((1, 1), np.nan, dtype))
-            a.apply_dot(db, dc, dot, work)
-            outs.append(np.concatenate((dc.to_numpy().reshape(-1), dot.to_numpy().reshape(-1))))
-            continue
-        c_init = np.full((n, 1), np.nan, dtype) if mode in ("plain", "beta0") else c0.reshape(-1, 1)
-        dc = g.Dense.from_numpy(ex, c_init)
-        if mode == "plain":
-            a.apply(db, dc)
-        else:
-            alpha, beta = (-0.75, 1.5) if mode == "adv" else (-0.75, 0.0)
-            a.apply(g.scalar(ex, alpha, dc.dtype), db, g.scalar(ex, beta, dc.dtype), dc)
-        outs.append(dc.to_numpy().reshape(-1))
-    assert np.array_equal(bits(outs[0]), bits(outs[1])), "the same product twice: different bits"
-    return outs[0]
-
-
-def reference(oracle, m, b, mode, c0):
-    _, rp, ci, v = m
-    if mode in ("plain", "dot"):
-        return oracle.csr_spmv(rp, ci, v, b)
-    alpha, beta = (-0.75, 1.5) if mode == "adv" else (-0.75, 0.0)
-    c = c0 if mode == "adv" else np.zeros_like(c0)      # beta = 0 never reads c
-    return oracle.csr_spmv(rp, ci, v, b, alpha, beta, c)
-
-
-def check_all_modes(ex, oracle, m, eligible, modes=("plain", "adv", "beta0", "dot"), b=None):
-    """every mode through the plan (built by the first product: key 1), against the oracle and against key 2"""
-    shape, rp, ci, v = m
-    rng = np.random.default_rng(5)
-    if b is None:
-        b = rng.uniform(-1, 1, shape[1]).astype(v.dtype)
-    c0 = rng.uniform(-1, 1, shape[0]).astype(v.dtype)
-    a = arena_csr(ex, shape, rp, ci, v)
-    n_seg = -(-shape[0] // 64)
-    done = 0
-    for mode in modes:
-        if mode == "dot" and (shape[0] != shape[1] or eligible != n_seg):
-            continue        # (square matrices; the fused entry takes the plan where every segment is eligible)
-        with key(1):
-            got = run(ex, a, b, mode, c0)
-            info = plan_info(a)
-        done += 2
-        assert info["state"] == 1 and info["segments"] == n_seg and info["eligible"] == eligible, (mode, info)
-        assert info["products"] == done, (mode, info)
-        with key(2):
-            old = run(ex, a, b, mode, c0)
-        assert plan_info(a)["products"] == done
-        assert np.array_equal(bits(got), bits(old)), mode
-        ref = reference(oracle, m, b, mode, c0)
-        assert np.array_equal(bits(got[:shape[0]]), bits(ref)), mode
-    return a
 
 
 # ---------------------------------------------------------------- 1. stencils
@@ -263,18 +136,6 @@ def test_absent_slots_do_not_touch_the_sum(gexec, oracle, dtype):
 
 
 # ---------------------------------------------------------------- 4. invalidation
-def two_structures(dtype):
-    """the same row pointers and entry count, other columns"""
-    n = 130
-    first = band_rows(n, n + 8, (-1, 0, 1))
-    second = [[c + 2 if c > r else c for c in row] for r, row in enumerate(first)]
-    return from_rows(first, n + 8, dtype, seed=1), from_rows(second, n + 8, dtype, seed=1)
-
-
-def plain(ex, a, b):
-    return run(ex, a, b, "plain", None)
-
-
 @pytest.mark.parametrize("how", ["memcpy_h2d", "structure_changed", "free"])
 def test_invalidation(gexec, oracle, how):
     from ginkgo_amd import _lib
@@ -390,3 +251,299 @@ def test_foreign_pointers_never_get_a_plan(gexec, oracle):
         for _ in range(2):
             assert np.array_equal(bits(plain(gexec, a, b)), bits(oracle.csr_spmv(rp, ci, v, b)))
         assert plan_info(a)["state"] == -1
+
+
+# ================================================================ kernel and launcher edges (csr_offsets_cases.py)
+CASES = list(oc.builders())
+
+
+def built(name, dtype):
+    if name.startswith("full-"):
+        _, t, lead = name.split("-")
+        return oc.full_stage(np.dtype(t), int(lead))
+    return oc.builders()[name](np.dtype(dtype))
+
+
+# ---------------------------------------------------------------- 8. every builder, every mode
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("name", CASES)
+def test_cases(gexec, oracle, name, dtype):
+    """banded(D): the ND = 8 / ND = 32 dispatch on both sides of D = 8, every multiple of 8 and its successor, 32 and
+    33; mixed_segments; tall (absent slots clamped on both sides of x; the 300-row one is rejected by the share
+    rule); 1 / 63 / 64 / 65 rows; the 50 % share from both sides.  What the plan reports comes from plan_model."""
+    check_all_modes(gexec, oracle, built(name, dtype))
+
+
+@pytest.mark.parametrize("name", oc.full_stage_names())
+def test_full_stage(gexec, oracle, name):
+    """64 rows x 32 entries = the stage's capacity, from every k0 % E: len = CAP .. CAP + E - 1 (the clamp and the
+    NL-th load of a lane)"""
+    m = built(name, None)
+    a = check_all_modes(gexec, oracle, m, eligible=3)
+    assert plan_info(a)["products"] == 6
+
+
+# ---------------------------------------------------------------- 9. two segments per wave
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("name", ["mixed", "full", "banded-9", "rows-65"])
+def test_two_segments_per_wave(gexec, oracle, name, dtype):
+    """GKOC_TUNE_CSR_SEGS_PER_WAVE = 2 on small matrices, the modes without the dot: 8 (mixed), 3 (full stage,
+    banded) and 2 segments, so the last wave owns two segments and owns one; in mixed_segments a wave's first
+    segment has nothing to load while its second has"""
+    if name == "full":
+        m = oc.full_stage(np.dtype(dtype), 16 // np.dtype(dtype).itemsize - 1)
+    else:
+        m = built(name, dtype)
+    with key(2, KEY_SEGS_PER_WAVE):
+        check_all_modes(gexec, oracle, m, modes=("plain", "adv", "beta0"))
+
+
+# ---------------------------------------------------------------- 10. rejected plans
+@pytest.mark.parametrize("k,n", [s for s in oc.SHARES if s != (2, 4)])
+def test_rejected_plans(gexec, oracle, k, n):
+    dtype = np.dtype(np.float64)
+    m = oc.share(k, n, dtype)
+    shape, rp, ci, v = m
+    rng = np.random.default_rng(12)
+    b, c0 = rng.uniform(-1, 1, shape[1]).astype(dtype), rng.uniform(-1, 1, shape[0]).astype(dtype)
+    a = arena_csr(gexec, *m)
+    with key(1):
+        for mode in ("plain", "adv"):                       # four products
+            got = run(gexec, a, b, mode, c0)
+            assert np.array_equal(bits(got), bits(reference(oracle, m, b, mode, c0))), mode
+        info = plan_info(a)
+        assert (info["state"], info["bytes"], info["products"]) == (2, 0, 0), info
+        assert (info["eligible"], info["segments"]) == (k, n), info
+        a.structure_changed()
+        assert plan_info(a)["state"] == -1
+        got = plain(gexec, a, b)                            # two products: analysed again, rejected again
+        assert np.array_equal(bits(got), bits(reference(oracle, m, b, "plain", c0)))
+        info = plan_info(a)
+        assert (info["state"], info["bytes"], info["products"], info["eligible"]) == (2, 0, 0, k), info
+
+
+def test_half_of_the_segments_is_enough(gexec, oracle):
+    a = check_all_modes(gexec, oracle, oc.share(2, 4), modes=("plain", "adv", "beta0"))
+    info = plan_info(a)
+    assert (info["state"], info["eligible"], info["segments"], info["products"]) == (1, 2, 4, 6), info
+
+
+# ---------------------------------------------------------------- 11. hub rows beside the plan
+def hub_case(dtype):
+    shape, rp, ci, v = oc.hub(np.dtype(dtype))
+    m = sc.Mat(rp, ci, v, np.diff(rp), shape)
+    rng = np.random.default_rng(21)
+    b = rng.uniform(-1, 1, shape[1]).astype(dtype)
+    c0 = rng.uniform(-1, 1, shape[0]).astype(dtype)
+    return m, b, c0
+
+
+def hub_product(ex, oracle, a, m, b, c0, mode):
+    """one mode, twice; rows of at most GKOC_CSR_LONG_ROW entries bit-equal to the oracle, row 70 within D eps S
+    (csr_spmv_cases.judge); plain and beta = 0 start from NaN in every row, row 70 and its segment included"""
+    got = run(ex, a, b, mode, c0)
+    if mode == "plain":
+        ref = sc.reference(oracle, m, b)
+    else:
+        beta = 1.5 if mode == "adv" else 0.0
+        ref = sc.reference(oracle, m, b, -0.75, beta, c0 if mode == "adv" else np.zeros_like(c0))
+    assert list(ref.hubs) == [oc.HUB_ROW]
+    sc.judge(got, ref, m)
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_hub_rows_plan_used_then_long_rows_off(gexec, oracle, dtype):
+    """built and multiplied with the long-row path at its default: three kernels write disjoint rows of c, the
+    plan's skip bits hold the long flags (with_long).  Then GKOC_TUNE_CSR_LONG_ROWS = 0: the flags the plan was
+    built with are not the product's, the plan is not used and its counter stands still."""
+    m, b, c0 = hub_case(dtype)
+    a = arena_csr(gexec, m.shape, m.rp, m.ci, m.v)
+    with key(1):
+        done = 0
+        for mode in ("plain", "adv", "beta0"):
+            hub_product(gexec, oracle, a, m, b, c0, mode)
+            done += 2
+            info = plan_info(a)
+            assert (info["state"], info["eligible"], info["segments"], info["products"]) == (1, 3, 4, done), info
+        with key(0, KEY_LONG_ROWS):
+            for mode in ("plain", "adv", "beta0"):
+                hub_product(gexec, oracle, a, m, b, c0, mode)
+                info = plan_info(a)
+                assert (info["state"], info["products"]) == (1, done), info
+        hub_product(gexec, oracle, a, m, b, c0, "adv")       # and used again with the flags back
+        assert plan_info(a)["products"] == done + 2
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_hub_rows_plan_built_without_long_rows(gexec, oracle, dtype):
+    """built under GKOC_TUNE_CSR_LONG_ROWS = 0 (skip bits without long flags), then the key at its default: the
+    long-flagged segment would be multiplied twice or not at all, so the plan is not used"""
+    m, b, c0 = hub_case(dtype)
+    a = arena_csr(gexec, m.shape, m.rp, m.ci, m.v)
+    with key(1):
+        with key(0, KEY_LONG_ROWS):
+            hub_product(gexec, oracle, a, m, b, c0, "adv")
+            info = plan_info(a)
+            assert (info["state"], info["eligible"], info["products"]) == (1, 3, 2), info
+        for mode in ("plain", "adv", "beta0"):
+            hub_product(gexec, oracle, a, m, b, c0, mode)
+            info = plan_info(a)
+            assert (info["state"], info["products"]) == (1, 2), info
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_hub_rows_fused_dot(gexec, oracle, dtype):
+    """gkoc_x_csr_spmv_dot on a (square) matrix with a hub row: the product goes through the plan and the
+    long-row kernels, the dot is a pass of its own with the bits of Dense.compute_dot(b, c)"""
+    import ginkgo_amd as g
+    dtype = np.dtype(dtype)
+    (n, _), rp, ci, v = oc.hub(dtype, square=True)
+    m = sc.Mat(rp, ci, v, np.diff(rp), (n, n))
+    model = oc.plan_model(rp, ci)
+    assert (model.eligible, model.state) == (model.segments - 1, 1)
+    b = np.random.default_rng(22).uniform(-1, 1, n).astype(dtype)
+    a = arena_csr(gexec, (n, n), rp, ci, v)
+    with key(1):
+        got = run(gexec, a, b, "dot", None)
+        info = plan_info(a)
+    assert (info["state"], info["eligible"], info["products"]) == (1, model.eligible, 2), info
+    ref = sc.reference(oracle, m, b)
+    sc.judge(got[:n], ref, m)
+    db, dc = g.Dense.from_numpy(gexec, b.reshape(-1, 1)), g.Dense.from_numpy(gexec, got[:n].reshape(-1, 1))
+    dot = g.Dense.from_numpy(gexec, np.full((1, 1), np.nan, dtype))
+    db.compute_dot(dc, dot)
+    assert np.array_equal(bits(got[n:]), bits(dot.to_numpy().reshape(-1)))
+
+
+# ---------------------------------------------------------------- 12. values are read live
+def test_values_are_read_live(gexec, oracle):
+    from ginkgo_amd import _lib
+    dtype = np.dtype(np.float64)
+    m = oc.mixed_segments(dtype)
+    shape, rp, ci, v = m
+    rng = np.random.default_rng(13)
+    b = rng.uniform(-1, 1, shape[1]).astype(dtype)
+    a = arena_csr(gexec, *m)
+    with key(1):
+        assert np.array_equal(bits(plain(gexec, a, b)), bits(oracle.csr_spmv(rp, ci, v, b)))
+        done = 2
+        for how in ("memcpy_h2d", "memset", "copy_"):
+            new = rng.uniform(-2, 2, len(v)).astype(dtype)
+            gexec.synchronize()
+            if how == "memcpy_h2d":
+                _lib.call("gkoc_memcpy_h2d", C.c_void_p(a.values.data_ptr()), new.ctypes.data_as(C.c_void_p),
+                          C.c_size_t(new.nbytes), gexec.stream)
+            elif how == "memset":
+                new = np.zeros_like(new)
+                _lib.call("gkoc_memset", C.c_void_p(a.values.data_ptr()), C.c_int(0), C.c_size_t(new.nbytes),
+                          gexec.stream)
+            else:
+                a.values.copy_(torch.from_numpy(new))
+            gexec.synchronize()
+            assert plan_info(a)["state"] == 1, how
+            got = plain(gexec, a, b)
+            done += 2
+            assert np.array_equal(bits(got), bits(oracle.csr_spmv(rp, ci, new, b))), how
+            info = plan_info(a)
+            assert (info["state"], info["products"]) == (1, done), (how, info)
+
+
+def test_one_structure_several_value_arrays(gexec, oracle):
+    """two Csr objects over the SAME row_ptrs / col_idxs tensors with value arrays of their own: one plan, both
+    right.  A third whose values start one element into an arena allocation (not 16-byte aligned): the
+    row-segment kernel multiplies it, and the plan's counter does not move."""
+    import ginkgo_amd as g
+    from ginkgo_amd.executor import MEM_VALUES
+    dtype = np.dtype(np.float64)
+    m = oc.mixed_segments(dtype)
+    shape, rp, ci, v = m
+    rng = np.random.default_rng(14)
+    b = rng.uniform(-1, 1, shape[1]).astype(dtype)
+    v2, v3 = rng.uniform(-2, 2, len(v)).astype(dtype), rng.uniform(-2, 2, len(v)).astype(dtype)
+    a1 = arena_csr(gexec, *m)
+    a2 = g.Csr(gexec, shape, arena_tensor(gexec, v2, MEM_VALUES), a1.col_idxs, a1.row_ptrs)
+    block = arena_tensor(gexec, np.concatenate(([0.0], v3)).astype(dtype), MEM_VALUES)
+    a3 = g.Csr(gexec, shape, block[1:], a1.col_idxs, a1.row_ptrs)
+    assert a3.values.data_ptr() % 16 != 0 and a1.values.data_ptr() % 16 == 0 and a2.values.data_ptr() % 16 == 0
+    with key(1):
+        done = 0
+        for a, vals in ((a1, v), (a2, v2), (a1, v), (a2, v2)):
+            assert np.array_equal(bits(plain(gexec, a, b)), bits(oracle.csr_spmv(rp, ci, vals, b)))
+            done += 2
+            info = plan_info(a)
+            assert (info["state"], info["products"]) == (1, done), info
+        assert np.array_equal(bits(plain(gexec, a3, b)), bits(oracle.csr_spmv(rp, ci, v3, b)))
+        info = plan_info(a1)
+        assert (info["state"], info["products"]) == (1, done), info
+
+
+# ---------------------------------------------------------------- 13. eviction
+def _arena_figures(ex):
+    ex.synchronize()
+    info = ex.arena_info()
+    return info["num_allocations"], info["used_bytes"]
+
+
+def test_eviction_at_the_cache_cap(gexec, oracle):
+    """130 live matrices under key 18 = 1 in a cache of 128 plans (offsets_cache_cap): the OLDEST plans make
+    room - at least the first two, more if plans of earlier tests are still alive, and always a prefix of the
+    arrival order; a matrix whose plan was evicted is multiplied again, right, and has a plan again; every buffer
+    of every plan goes back to the allocator (the graveyard is emptied by the release that follows)."""
+    dtype = np.dtype(np.float64)
+    n_mat = oc.CACHE_CAP + 2
+    shape, rp, ci, v = oc.rows_n(65, dtype)
+    b = np.random.default_rng(15).uniform(-1, 1, shape[1]).astype(dtype)
+
+    def round_():
+        mats = []
+        with key(1):
+            for i in range(n_mat):
+                a = arena_csr(gexec, shape, rp, ci, v * (1 + i))
+                assert np.array_equal(bits(plain(gexec, a, b)), bits(oracle.csr_spmv(rp, ci, v * (1 + i), b))), i
+                assert plan_info(a)["state"] == 1
+                mats.append(a)
+            states = [plan_info(a)["state"] for a in mats]
+            gone = states.count(-1)
+            assert gone >= n_mat - oc.CACHE_CAP and states == [-1] * gone + [1] * (n_mat - gone), states
+            for i in range(3):
+                got = plain(gexec, mats[i], b)
+                assert np.array_equal(bits(got), bits(oracle.csr_spmv(rp, ci, v * (1 + i), b))), i
+                info = plan_info(mats[i])
+                # (a NEW plan for each of the three: the plan of mats[2] left when mats[0] came back at the latest)
+                assert info["state"] == 1 and info["products"] == 2, (i, info)
+        return gone
+
+    gone = round_()                       # the warm-up round: the allocator's chunks, the long-row cache's slots
+    gc.collect()
+    before = _arena_figures(gexec)
+    assert round_() == gone
+    gc.collect()
+    assert _arena_figures(gexec) == before
+
+
+# ---------------------------------------------------------------- 14. degenerate shapes
+def test_no_columns_is_never_keyed(gexec, oracle):
+    """n_cols = 0 (no entries; every pointer valid, so n_cols alone decides): the launcher does not key the
+    arrays at all - state -1 after two products, and c = 0"""
+    from ginkgo_amd import _lib
+    from ginkgo_amd.executor import MEM_INDICES, MEM_VALUES, MEM_VECTOR
+    dtype = np.dtype(np.float64)
+    n = 70
+    rp = arena_tensor(gexec, np.zeros(n + 1, np.int32), MEM_INDICES)
+    ci = arena_tensor(gexec, np.zeros(4, np.int32), MEM_INDICES)
+    v = arena_tensor(gexec, np.zeros(4, dtype), MEM_VALUES)
+    x = arena_tensor(gexec, np.zeros(4, dtype), MEM_VECTOR)
+    with key(1):
+        for _ in range(2):
+            y = arena_tensor(gexec, np.full(n, np.nan, dtype), MEM_VECTOR)
+            _lib.call("gkoc_csr_spmv_f64_i32", gexec.stream, n, 0, rp, ci, v, x, 1, y, 1, 1)
+            gexec.synchronize()
+            assert np.array_equal(bits(y.cpu().numpy()), bits(np.zeros(n, dtype)))
+        assert plan_info_at(rp.data_ptr(), ci.data_ptr())["state"] == -1
+
+
+# ---------------------------------------------------------------- 15. fuzz
+@pytest.mark.parametrize("seed", oc.FUZZ_SEEDS)
+def test_fuzz(gexec, oracle, seed):
+    """state, segments and the eligible count from plan_model; plain and advanced, double"""
+    check_all_modes(gexec, oracle, oc.fuzz(seed), modes=("plain", "adv"))
