@@ -34,22 +34,7 @@
 
 #include "common.hpp"
 #include "scan.hpp"
-
-struct gkoc_trs_struct_s {
-    int64_t n_rows;
-    int64_t nnz;             // row_ptrs[n_rows] at generate
-    int is_upper;
-    int64_t n_levels;
-    int64_t* level_ptrs;     // device, n_levels + 1
-    int64_t* level_rows;     // device, n_rows
-    struct segment {
-        int64_t first, last; // levels [first, last)
-        int64_t offset;      // level_ptrs[first]
-        int64_t rows;        // wide: rows of the level; narrow: the largest level of the run
-        bool wide;
-    };
-    std::vector<segment> schedule;
-};
+#include "trs_struct.hpp"
 
 namespace gkoc {
 namespace {

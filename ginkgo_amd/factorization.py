@@ -1,0 +1,187 @@
+"""Incomplete factorizations - mirror of include/ginkgo/core/factorization/{ilu,ic}.hpp
+(factorization::Ilu / Ic; core/factorization/{ilu,ic}.cpp).
+
+`Ilu.build().with_skip_sorting(False).on(exec).generate(csr)` works on a copy of the matrix: it sorts
+the rows (unless told not to), inserts an explicit zero wherever a diagonal entry is missing
+(factorization::add_diagonal_elements), computes the exact ILU(0) in place on the level schedule of the
+lower triangular solve (gkoc_lower_trs_generate_* + gkoc_ilu_factorize_*) and splits the result
+(factorization::initialize_row_ptrs_l_u + initialize_l_u; the column indices of the factors come from
+the Sor set-up entry, which writes the same structure): `get_l_factor()` has a unit diagonal, stored
+last in each row, `get_u_factor()` its diagonal first.
+
+`Ic.build().with_both_factors(True).on(exec).generate(csr)` takes the lower triangle with its diagonal
+(factorization::initialize_l) and computes the exact IC(0) in place (gkoc_ic_factorize_*):
+`get_l_factor()`, and `get_lt_factor()` = its transpose (None with `with_both_factors(False)`).
+
+Both results are bit-identical to the sequential loops stated in include/gko_cdna4.h.  Pivots are not
+checked: a zero or negative pivot gives inf / NaN entries, as in the reference.
+"""
+import ctypes as C
+
+from ._lib import IT, VT, DimensionMismatch, NotSupported, call, lib
+from .executor import MEM_INDICES, MEM_VALUES
+from .matrix import Csr, Fbcsr
+
+
+def row_limits():
+    """the row lengths at which the factorization kernels change path (gkoc_factorization_row_limits)"""
+    limits, count = (C.c_int * 4)(), C.c_int(0)
+    call("gkoc_factorization_row_limits", limits, C.byref(count))
+    return [int(limits[p]) for p in range(count.value)]
+
+
+class _Factory:
+    def __init__(self, cls):
+        self.cls = cls
+        self.skip_sorting = False
+        self.both_factors = True
+        self.exec = None
+
+    def with_skip_sorting(self, v):
+        self.skip_sorting = bool(v)
+        return self
+
+    def on(self, exec_):
+        self.exec = exec_
+        return self
+
+    def generate(self, system_matrix):
+        if isinstance(system_matrix, Fbcsr):
+            # any other matrix type goes through convert_to(Csr), as for Sor
+            csr = system_matrix.convert_to_csr()
+            fact = self.cls(self, csr)
+            csr.exec.synchronize()      # the converted copy is released on return
+            return fact
+        return self.cls(self, system_matrix)
+
+
+class _IcFactory(_Factory):
+    def with_both_factors(self, v):
+        self.both_factors = bool(v)
+        return self
+
+
+class _Factorization:
+    """the work shared by Ilu and Ic: checks, the sorted copy with every diagonal stored, the schedule"""
+
+    def __init__(self, factory, a):
+        name = type(self).__name__
+        if not isinstance(a, Csr):
+            raise NotSupported(f"factorization.{name}.generate needs a Csr system matrix")
+        if a.size[0] != a.size[1]:
+            raise DimensionMismatch(f"factorization.{name} needs a square matrix")
+        if a.dtype not in VT:
+            raise NotSupported(f"factorization.{name}: real value types only")
+        self.exec = factory.exec or a.exec
+        self.size = a.size
+        self.dtype = a.dtype
+        self._it = IT[a.col_idxs.dtype]
+        self._suf = f"{VT[a.dtype]}_{self._it}"
+
+    def _prepared(self, factory, a):
+        """a sorted copy of `a` in which every row stores its diagonal"""
+        ex, n = self.exec, self.size[0]
+        work = Csr(ex, a.size, a.values.clone(), a.col_idxs.clone(), a.row_ptrs, a.strategy)
+        if not factory.skip_sorting and not work.is_sorted_by_column_index():
+            work.sort_by_column_index()
+        idx = a.row_ptrs.dtype
+        shift, missing = ex.alloc((n + 1,), idx, MEM_INDICES), C.c_int64(0)
+        call("gkoc_csr_missing_diagonal_shift_" + self._it, ex.stream, n, n, work.row_ptrs, work.col_idxs,
+             shift, C.byref(missing))
+        if missing.value:
+            nnz = work.values.numel() + missing.value
+            rp, ci = ex.alloc((n + 1,), idx, MEM_INDICES), ex.alloc((nnz,), idx, MEM_INDICES)
+            v = ex.alloc((nnz,), a.dtype, MEM_VALUES)
+            call("gkoc_csr_add_diagonal_fill_" + self._suf, ex.stream, n, work.row_ptrs, work.col_idxs,
+                 work.values, shift, rp, ci, v)
+            ex.synchronize()            # `shift` and the unfilled copy are released here
+            work = Csr(ex, a.size, v, ci, rp, a.strategy)
+        return work
+
+    def _factorize(self, entry, m):
+        """the lower solve's level schedule of `m`, then the in-place factorization on it"""
+        ex, n = self.exec, self.size[0]
+        handle = C.c_void_p()
+        call("gkoc_lower_trs_generate_" + self._it, ex.stream, n, m.row_ptrs, m.col_idxs, C.byref(handle))
+        try:
+            call(entry + self._suf, ex.stream, handle, n, m.row_ptrs, m.col_idxs, m.values)
+        finally:
+            lib().gkoc_trs_struct_destroy(handle)
+
+    def _split(self, m, with_u, diag_sqrt=False):
+        """the factors of the split of `m` as Csr: L (strictly-lower entries, then 1 or the diagonal) and,
+        with_u, U (the diagonal, then the strictly-upper entries).  The index arrays are the ones of the
+        Sor set-up (weight 1); the new entries write the values"""
+        ex, n = self.exec, self.size[0]
+        idx = m.row_ptrs.dtype
+        l_rp = ex.alloc((n + 1,), idx, MEM_INDICES)
+        u_rp = ex.alloc((n + 1,), idx, MEM_INDICES) if with_u else None
+        call("gkoc_factorization_initialize_row_ptrs_l_u_" + self._it, ex.stream, n, m.row_ptrs, m.col_idxs,
+             l_rp, u_rp)
+        out = []
+        for rp in (l_rp, u_rp) if with_u else (l_rp,):
+            nnz = int(rp[-1].item())
+            out += [rp, ex.alloc((nnz,), idx, MEM_INDICES), ex.alloc((nnz,), m.dtype, MEM_VALUES)]
+        src = (ex.stream, n, m.row_ptrs, m.col_idxs, m.values)
+        if with_u:
+            l_rp, l_ci, l_v, u_rp, u_ci, u_v = out
+            call("gkoc_sor_initialize_weighted_l_u_" + self._suf, *src, C.c_double(1.0), l_rp, l_ci, l_v,
+                 u_rp, u_ci, u_v)
+            call("gkoc_factorization_initialize_l_u_" + self._suf, *src, l_rp, l_v, u_rp, u_v)
+            return Csr(ex, self.size, l_v, l_ci, l_rp), Csr(ex, self.size, u_v, u_ci, u_rp)
+        l_rp, l_ci, l_v = out
+        call("gkoc_sor_initialize_weighted_l_" + self._suf, *src, C.c_double(1.0), l_rp, l_ci, l_v)
+        call("gkoc_factorization_initialize_l_" + self._suf, *src, l_rp, l_v, C.c_int(int(diag_sqrt)))
+        return Csr(ex, self.size, l_v, l_ci, l_rp)
+
+    def get_executor(self):
+        return self.exec
+
+    def get_size(self):
+        return self.size
+
+
+class Ilu(_Factorization):
+    """A ~ L U on the pattern of A: L unit lower triangular, U upper triangular (exact ILU(0))."""
+
+    @staticmethod
+    def build():
+        return _Factory(Ilu)
+
+    def __init__(self, factory, a):
+        super().__init__(factory, a)
+        ex = self.exec
+        m = self._prepared(factory, a)
+        self._factorize("gkoc_ilu_factorize_", m)
+        self.l, self.u = self._split(m, True)
+        ex.synchronize()                # the factored copy is released on return
+
+    def get_l_factor(self):
+        return self.l
+
+    def get_u_factor(self):
+        return self.u
+
+
+class Ic(_Factorization):
+    """A ~ L L^T on the pattern of A's lower triangle (exact IC(0))."""
+
+    @staticmethod
+    def build():
+        return _IcFactory(Ic)
+
+    def __init__(self, factory, a):
+        super().__init__(factory, a)
+        ex = self.exec
+        m = self._prepared(factory, a)
+        self.l = self._split(m, False)
+        self._factorize("gkoc_ic_factorize_", self.l)
+        self.both_factors = factory.both_factors
+        self.lt = self.l.transpose() if self.both_factors else None
+        ex.synchronize()                # the prepared copy is released on return
+
+    def get_l_factor(self):
+        return self.l
+
+    def get_lt_factor(self):
+        return self.lt

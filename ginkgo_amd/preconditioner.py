@@ -18,12 +18,18 @@ Sor / GaussSeidel - mirror of include/ginkgo/core/preconditioner/{sor,gauss_seid
 weighted factor(s) on the device (factorization::initialize_row_ptrs_l_u,
 sor::initialize_weighted_l / _l_u) and applies them with the level-scheduled triangular solvers of
 triangular.py: z = L^-1 r, or z = U^-1 L^-1 r for the symmetric form (SSOR).
+
+Ilu / Ic - mirror of include/ginkgo/core/preconditioner/{ilu,ic}.hpp:
+`Ilu.build().with_reverse_apply(False).on(exec).generate(A)` and `Ic.build().on(exec).generate(A)` apply
+the factors of factorization.py (the exact ILU(0) / IC(0)) with the same triangular solvers; A is a
+system matrix or an already generated factorization object.
 """
 import ctypes as C
 
 import numpy as np
 import torch
 
+from . import factorization as _factorization
 from ._lib import IT, VT, JacobiScheme, NotSupported, call
 from .base import LinOp
 from .executor import MEM_INDICES, MEM_VALUES
@@ -430,3 +436,104 @@ class GaussSeidel(Sor):
     @staticmethod
     def build():
         return _GaussSeidelFactory()
+
+
+class _FactorizedFactory:
+    def __init__(self, cls):
+        self.cls = cls
+        self.reverse_apply = False
+        self.skip_sorting = False
+        self.exec = None
+
+    def with_skip_sorting(self, v):
+        """passed on to the factorization when generate gets a system matrix"""
+        self.skip_sorting = bool(v)
+        return self
+
+    def on(self, exec_):
+        self.exec = exec_
+        return self
+
+    def generate(self, system_matrix):
+        return self.cls(self, system_matrix)
+
+
+class _IluFactory(_FactorizedFactory):
+    def with_reverse_apply(self, v):
+        self.reverse_apply = bool(v)
+        return self
+
+
+class _Factorized(LinOp):
+    """two triangular solves on the factors of a factorization object; the vector between them is
+    allocated at generate time, so a captured iteration allocates nothing"""
+    _FACTORIZATION = None
+
+    def __init__(self, factory, a):
+        if not isinstance(a, self._FACTORIZATION):
+            # Ginkgo's default here is ParIlu / ParIc; this backend has the exact ILU(0) / IC(0)
+            a = (self._FACTORIZATION.build().with_skip_sorting(factory.skip_sorting)
+                 .on(factory.exec or a.exec).generate(a))
+        super().__init__(factory.exec or a.exec, a.size)
+        self.factorization = a
+        self.dtype = a.dtype
+        lower, upper = self._factors(a)
+        self._l_solver = LowerTrs.build().on(self.exec).generate(lower)
+        self._u_solver = UpperTrs.build().on(self.exec).generate(upper)
+        self._order = (self._u_solver, self._l_solver) if factory.reverse_apply else \
+            (self._l_solver, self._u_solver)
+        self._tmp = Dense.create(self.exec, (a.size[0], 1), a.dtype)
+
+    def get_l_solver(self):
+        return self._l_solver
+
+    def apply_impl(self, b, x):
+        if self._tmp.size != b.size or self._tmp.dtype != b.dtype:
+            self._tmp = Dense.create(self.exec, b.size, b.dtype)
+        self._order[0].apply(b, self._tmp)
+        self._order[1].apply(self._tmp, x)
+
+    def apply_advanced_impl(self, alpha, b, beta, x):
+        xc = x.clone()
+        self.apply_impl(b, xc)
+        x.scale(beta)
+        x.add_scaled(alpha, xc)
+
+
+class Ilu(_Factorized):
+    """preconditioner::Ilu: z = U^-1 L^-1 r (with_reverse_apply(True): z = L^-1 U^-1 r) with the
+    level-scheduled triangular solvers.  `generate` takes a factorization.Ilu object or a system matrix.
+    A system matrix is factorized here with the exact ILU(0) of factorization.Ilu - Ginkgo's default at
+    this place is the iterative ParIlu, which this backend does not have."""
+    _FACTORIZATION = _factorization.Ilu
+
+    @staticmethod
+    def build():
+        return _IluFactory(Ilu)
+
+    @staticmethod
+    def _factors(f):
+        return f.get_l_factor(), f.get_u_factor()
+
+    def get_u_solver(self):
+        return self._u_solver
+
+
+class Ic(_Factorized):
+    """preconditioner::Ic: z = L^-T L^-1 r with the level-scheduled triangular solvers.  `generate` takes
+    a factorization.Ic object or a system matrix.  A system matrix is factorized here with the exact IC(0)
+    of factorization.Ic - Ginkgo's default at this place is the iterative ParIc, which this backend does
+    not have."""
+    _FACTORIZATION = _factorization.Ic
+
+    @staticmethod
+    def build():
+        return _FactorizedFactory(Ic)
+
+    @staticmethod
+    def _factors(f):
+        lt = f.get_lt_factor()
+        return f.get_l_factor(), f.get_l_factor().transpose() if lt is None else lt
+
+    def get_lh_solver(self):
+        return self._u_solver

@@ -2614,6 +2614,53 @@ GKOC_DECL_TRS(double, f64, int64_t, i64)
 GKOC_DECL_TRS(float, f32, int32_t, i32)
 GKOC_DECL_TRS(float, f32, int64_t, i64)
 
+/* ------------------------------------- ILU(0) / IC(0) (factorization::Ilu / Ic, preconditioner::Ilu / Ic)
+ * The exact incomplete factorizations on the matrix' own pattern, in place, on the level schedule of the
+ * lower triangular solve of the SAME matrix (t from gkoc_lower_trs_generate_*: row i needs exactly the
+ * finished rows k < i with (i, k) stored).  Rows must be sorted by column index.  The arithmetic is fixed
+ * (every multiply and subtract a separate operation in T), so f64 and f32 results are bit-identical to:
+ * ilu_factorize: for i = 0 .. n-1, for every stored k < i ascending: a_ik = a_ik / a_kk (a_kk the finished
+ *   pivot of row k), then for every stored j > k of row k with (i, j) stored: a_ij = a_ij - a_ik * a_kj.
+ *   Every row must store its diagonal.
+ * ic_factorize: the matrix is lower triangular with the diagonal LAST in every row.  For every stored
+ *   (i, j), j <= i, columns ascending: s = a_ij; for ascending k < j with (i, k) and (j, k) stored:
+ *   s = s - l_ik * l_jk; l_ij = s / l_jj for j < i, l_ii = sqrt(s).
+ * Pivots are not checked: a zero or negative one gives IEEE inf / NaN entries and GKOC_OK.
+ * GKOC_E_INVALID before any kernel touches the values: a null structure, one of the upper triangle, of
+ * another n_rows or another number of stored entries, row pointers that do not ascend from 0 to that
+ * number, a column outside the matrix, a row without a stored diagonal, for ic a row whose last entry is
+ * not its diagonal.  Set-up: the calls take scratch from the arena and synchronise the stream once (for the
+ * checks); they are not meant to be captured.  One launch per level with more than W rows, one
+ * single-workgroup launch per run of smaller levels, as for the solve; no kernel waits for another workgroup.
+ * row_limits: the row lengths at which the kernels change path, ascending, in limits_host[0 .. *count_host)
+ * (at most 4): a matrix whose LONGEST row has at most limits[0] entries is factorized by groups of limits[0]
+ * lanes per row, ..., at most limits[count-1] entries by a whole wave per row with the row in registers; in a
+ * matrix with longer rows, those rows are streamed through memory by their wave.
+ * initialize_l_u / initialize_l (factorization::initialize_l_u / initialize_l) write the VALUES of the split; they
+ * write no index array.  The index arrays of L and U are exactly those of the Sor set-up: row pointers from
+ * gkoc_factorization_initialize_row_ptrs_l_u_*, column indices as gkoc_sor_initialize_weighted_l[_u]_* writes them
+ * (L: strictly-lower columns in storage order, then the diagonal; U: the diagonal, then the strictly-upper
+ * columns in storage order).  initialize_l_u: l_v = the strictly-lower values in storage order, then an explicit
+ * 1; u_v = the diagonal (1 where none is stored), then the strictly-upper values in storage order.  initialize_l:
+ * l_v = the strictly-lower values in storage order, then the diagonal (1 where none is stored), replaced by its
+ * square root with diag_sqrt != 0. */
+int gkoc_factorization_row_limits(int* limits_host, int* count_host);
+#define GKOC_DECL_FACTORIZATION(T, TN, I, IN)                                                                \
+    int gkoc_ilu_factorize_##TN##_##IN(gkoc_stream_t s, gkoc_trs_struct_t t, int64_t n_rows,                 \
+                                       const I* row_ptrs, const I* col_idxs, T* vals);                       \
+    int gkoc_ic_factorize_##TN##_##IN(gkoc_stream_t s, gkoc_trs_struct_t t, int64_t n_rows,                  \
+                                      const I* row_ptrs, const I* col_idxs, T* vals);                        \
+    int gkoc_factorization_initialize_l_u_##TN##_##IN(gkoc_stream_t s, int64_t n_rows, const I* rp,          \
+                                                      const I* ci, const T* v, const I* l_rp, T* l_v,        \
+                                                      const I* u_rp, T* u_v);                                \
+    int gkoc_factorization_initialize_l_##TN##_##IN(gkoc_stream_t s, int64_t n_rows, const I* rp,            \
+                                                    const I* ci, const T* v, const I* l_rp, T* l_v,          \
+                                                    int diag_sqrt);
+GKOC_DECL_FACTORIZATION(double, f64, int32_t, i32)
+GKOC_DECL_FACTORIZATION(double, f64, int64_t, i64)
+GKOC_DECL_FACTORIZATION(float, f32, int32_t, i32)
+GKOC_DECL_FACTORIZATION(float, f32, int64_t, i64)
+
 #ifdef __cplusplus
 }
 #endif
