@@ -22,7 +22,9 @@ triangular.py: z = L^-1 r, or z = U^-1 L^-1 r for the symmetric form (SSOR).
 Ilu / Ic - mirror of include/ginkgo/core/preconditioner/{ilu,ic}.hpp:
 `Ilu.build().with_reverse_apply(False).on(exec).generate(A)` and `Ic.build().on(exec).generate(A)` apply
 the factors of factorization.py (the exact ILU(0) / IC(0)) with the same triangular solvers; A is a
-system matrix or an already generated factorization object.
+system matrix or an already generated factorization object.  `with_l_solver(factory)` / `with_u_solver(factory)`
+(Ic: `with_l_solver` only) replace the level-scheduled solvers by anything with `.on(exec).generate(csr)`,
+e.g. `LowerIsai.build().with_sparsity_power(2)` of isai.py: one SpMV per factor instead of a launch per level.
 """
 import ctypes as C
 
@@ -443,11 +445,17 @@ class _FactorizedFactory:
         self.cls = cls
         self.reverse_apply = False
         self.skip_sorting = False
+        self.l_solver = self.u_solver = None
         self.exec = None
 
     def with_skip_sorting(self, v):
         """passed on to the factorization when generate gets a system matrix"""
         self.skip_sorting = bool(v)
+        return self
+
+    def with_l_solver(self, factory):
+        """the factory (anything with .on(exec).generate(csr)) of the solver for L; default LowerTrs"""
+        self.l_solver = factory
         return self
 
     def on(self, exec_):
@@ -461,6 +469,11 @@ class _FactorizedFactory:
 class _IluFactory(_FactorizedFactory):
     def with_reverse_apply(self, v):
         self.reverse_apply = bool(v)
+        return self
+
+    def with_u_solver(self, factory):
+        """the factory (anything with .on(exec).generate(csr)) of the solver for U; default UpperTrs"""
+        self.u_solver = factory
         return self
 
 
@@ -477,9 +490,7 @@ class _Factorized(LinOp):
         super().__init__(factory.exec or a.exec, a.size)
         self.factorization = a
         self.dtype = a.dtype
-        lower, upper = self._factors(a)
-        self._l_solver = LowerTrs.build().on(self.exec).generate(lower)
-        self._u_solver = UpperTrs.build().on(self.exec).generate(upper)
+        self._l_solver, self._u_solver = self._solvers(factory, a)
         self._order = (self._u_solver, self._l_solver) if factory.reverse_apply else \
             (self._l_solver, self._u_solver)
         self._tmp = Dense.create(self.exec, (a.size[0], 1), a.dtype)
@@ -504,16 +515,18 @@ class Ilu(_Factorized):
     """preconditioner::Ilu: z = U^-1 L^-1 r (with_reverse_apply(True): z = L^-1 U^-1 r) with the
     level-scheduled triangular solvers.  `generate` takes a factorization.Ilu object or a system matrix.
     A system matrix is factorized here with the exact ILU(0) of factorization.Ilu - Ginkgo's default at
-    this place is the iterative ParIlu, which this backend does not have."""
+    this place is the iterative ParIlu, which this backend does not have.  `with_l_solver` / `with_u_solver`
+    take a factory for the solver of either factor (e.g. LowerIsai / UpperIsai); default LowerTrs / UpperTrs."""
     _FACTORIZATION = _factorization.Ilu
 
     @staticmethod
     def build():
         return _IluFactory(Ilu)
 
-    @staticmethod
-    def _factors(f):
-        return f.get_l_factor(), f.get_u_factor()
+    def _solvers(self, factory, f):
+        l_factory, u_factory = factory.l_solver or LowerTrs.build(), factory.u_solver or UpperTrs.build()
+        return (l_factory.on(self.exec).generate(f.get_l_factor()),
+                u_factory.on(self.exec).generate(f.get_u_factor()))
 
     def get_u_solver(self):
         return self._u_solver
@@ -523,17 +536,28 @@ class Ic(_Factorized):
     """preconditioner::Ic: z = L^-T L^-1 r with the level-scheduled triangular solvers.  `generate` takes
     a factorization.Ic object or a system matrix.  A system matrix is factorized here with the exact IC(0)
     of factorization.Ic - Ginkgo's default at this place is the iterative ParIc, which this backend does
-    not have."""
+    not have.  `with_l_solver` takes a factory for the solver S of L (e.g. LowerIsai); the solver of L^T is then
+    S.transpose(), as in Ginkgo, so that z = S^T S r stays symmetric - a solver without transpose() (LowerTrs)
+    is refused there."""
     _FACTORIZATION = _factorization.Ic
 
     @staticmethod
     def build():
         return _FactorizedFactory(Ic)
 
-    @staticmethod
-    def _factors(f):
+    def _solvers(self, factory, f):
+        if factory.l_solver is not None:
+            # as in Ginkgo: lh_solver = l_solver->conj_transpose(), so that M^-1 = S^T S stays symmetric
+            lower = factory.l_solver.on(self.exec).generate(f.get_l_factor())
+            if not hasattr(lower, "transpose"):
+                raise NotSupported(f"Ic: the solver for L^T is the transpose of the given l_solver, and "
+                                   f"{type(lower).__name__} has no transpose(); give a solver that has one "
+                                   "(LowerIsai) or leave the default level-scheduled pair")
+            return lower, lower.transpose()
         lt = f.get_lt_factor()
-        return f.get_l_factor(), f.get_l_factor().transpose() if lt is None else lt
+        upper = f.get_l_factor().transpose() if lt is None else lt
+        return (LowerTrs.build().on(self.exec).generate(f.get_l_factor()),
+                UpperTrs.build().on(self.exec).generate(upper))
 
     def get_lh_solver(self):
         return self._u_solver

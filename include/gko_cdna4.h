@@ -2661,6 +2661,42 @@ GKOC_DECL_FACTORIZATION(double, f64, int64_t, i64)
 GKOC_DECL_FACTORIZATION(float, f32, int32_t, i32)
 GKOC_DECL_FACTORIZATION(float, f32, int64_t, i64)
 
+/* ------------------------------------- triangular ISAI (preconditioner::LowerIsai / UpperIsai)
+ * isai::generate_tri_inverse (reference/preconditioner/isai_kernels.cpp): the incomplete sparse approximate
+ * inverse W of a triangular matrix A on a given pattern, (W A)(i, S_i) = e_i(S_i) for every row i, S_i = the
+ * columns stored in row i of the pattern.  The entry writes the VALUES w_v only: every index pointer is const,
+ * the pattern (w_rp, w_ci) is the caller's - A's own arrays (sparsity power 1; the same pointers may be
+ * passed) or the pattern of |A|^p made with gkoc_csr_spgemm_count / _expand, gkoc_sort_row_major,
+ * gkoc_sum_duplicates_* and gkoc_convert_idxs_to_ptrs.
+ * Input: A is triangular on the stated side (is_lower != 0: lower), rows sorted by column, the diagonal
+ * stored as the LAST entry of every row (lower) or the FIRST (upper) - the layouts of factorization::Ilu / Ic
+ * and of the Sor set-up.  Row i of the pattern is sorted, lies on the same side and contains i.
+ * The arithmetic is fixed (every multiply and subtract a separate operation in T), so f64 and f32 results are
+ * bit-identical to:
+ * lower: c_0 < ... < c_{m-1} = i the columns of S_i.  For t = m-1 down to 0: s = (c_t == i) ? 1 : 0; for
+ *   u = m-1 down to t+1, whenever (c_u, c_t) is stored in A: s = s - w[c_u] * a[c_u, c_t];
+ *   w[c_t] = s / a[c_t, c_t].
+ * upper: the mirror image: c_0 = i < ... < c_{m-1}, t ascending, u ascending from 0 to t-1.
+ * If any w of a row is not finite, the row becomes all zeros with 1 on the diagonal (Ginkgo's rule).
+ * GKOC_E_INVALID before any kernel touches w_v: null pointers, row pointers (of A or of the pattern) that do
+ * not ascend from 0, a column outside the matrix, an entry of A or of the pattern on the wrong side, a row of
+ * A or of the pattern whose last (lower) / first (upper) entry is not its diagonal.  Set-up: the call takes
+ * scratch from the arena and synchronises the stream once (for the checks); it is not meant to be captured.
+ * All rows go in ONE launch (no row depends on another): a group of 16, 32 or 64 lanes per row, chosen from
+ * the longest pattern row of the call, lane = stored entry; a pattern row longer than the last limit is
+ * streamed through w_v by its wave.  No length cap, no serial path, every entry of w_v written by one lane.
+ * row_limits: the pattern-row lengths at which the kernel changes path, ascending, in
+ * limits_host[0 .. *count_host) (at most 4). */
+int gkoc_isai_row_limits(int* limits_host, int* count_host);
+#define GKOC_DECL_ISAI(T, TN, I, IN)                                                                         \
+    int gkoc_isai_generate_tri_inverse_##TN##_##IN(gkoc_stream_t s, int64_t n_rows, int is_lower,            \
+                                                   const I* a_rp, const I* a_ci, const T* a_v,               \
+                                                   const I* w_rp, const I* w_ci, T* w_v);
+GKOC_DECL_ISAI(double, f64, int32_t, i32)
+GKOC_DECL_ISAI(double, f64, int64_t, i64)
+GKOC_DECL_ISAI(float, f32, int32_t, i32)
+GKOC_DECL_ISAI(float, f32, int64_t, i64)
+
 #ifdef __cplusplus
 }
 #endif
