@@ -335,6 +335,8 @@ class Cg(_IterativeSolver):
         mode = self.params.get("hip_graph", "auto")
         if mode is False or not fuse_norm or lag < 1 or cols != 1:
             return None
+        if not getattr(self.preconditioner, "capturable", True):
+            return None     # its application reads back from the device (Multigrid with an inner solver)
         if mode == "auto" and rows >= (1 << 21):
             return None
         rn, max_iters, rn_id = None, float("inf"), 0

@@ -2697,6 +2697,96 @@ GKOC_DECL_ISAI(double, f64, int64_t, i64)
 GKOC_DECL_ISAI(float, f32, int32_t, i32)
 GKOC_DECL_ISAI(float, f32, int64_t, i64)
 
+/* ------------------------------------- Pgm aggregation (multigrid::Pgm) and its grid transfers
+ * One level of an aggregation multigrid hierarchy: rows of A are grouped into aggregates (agg), the coarse
+ * operator is A_c = P^T A P with P(i, agg_i) = 1, and P / P^T are applied from agg and the member lists, never
+ * stored as matrices.  The aggregation is integers only and does not depend on thread order; it is specified
+ * here bit for bit (tests/pgm_refs.py restates it in numpy).
+ * Input: A is an n x n CSR matrix without duplicate entries (unsorted input is sorted on a copy by the caller;
+ * the caller's matrix is never changed).
+ * Weights: W has the pattern of A u A^T, rows sorted; w_ij = 0.5 |a_ij| + 0.5 |a_ji| (a missing entry counts
+ * as 0; both products are exact, so the sum does not depend on the order); d_i = w_ii, 0 if not stored.  W is
+ * made with entries that exist already: the triplets of A and, rows and columns exchanged, of A^T
+ * (gkoc_convert_ptrs_to_idxs), gkoc_dense_absolute, gkoc_dense_scale by 0.5, and the triplet pipeline
+ * (gkoc_sort_row_major, gkoc_sum_duplicates_count / _fill: a run is 0 + v0 or 0 + v0 + v1,
+ * gkoc_convert_idxs_to_ptrs); d with gkoc_csr_extract_diagonal.
+ * Strength and key: for j != i stored in row i of W, s_ij = w_ij / max(d_i, d_j), ONE division in T.  A
+ * candidate whose s is not >= 0 (NaN from 0 / 0) is skipped.  Candidates are ordered by the key (s_ij, h_ij, j),
+ * compared lexicographically, the largest is the best.  h_ij is a symmetric 32-bit hash of the pair: with
+ * lo = min(i, j), hi = max(i, j), both truncated to uint32, all arithmetic mod 2^32:
+ *   h = (lo * 0x9E3779B1) ^ (hi * 0x85EBCA77);  h ^= h >> 15;  h *= 0x2C1B3C6D;  h ^= h >> 12.
+ * This departs from Ginkgo's (weight, column) rule on purpose: on equal weights every row points at its
+ * largest-index neighbour and almost no pair is mutual (12^3 27-point stencil: 15 rounds, 1558 of 1728 rows
+ * left to the fallback, 1728 -> 1496; with the hash 5 rounds, 29 rows left, 1728 -> 826).  The hash only
+ * decides ties.
+ * Rounds: at most max_iterations (the caller's loop).  agg starts as all -1.  EVERY ROUND READS THE AGGREGATION
+ * AS IT WAS WHEN THE ROUND BEGAN (Ginkgo's kernels race here).
+ *   select: for every row i with agg_i == -1, u_i = the best unaggregated neighbour, g_i = the best aggregated
+ *     one.  If u_i exists i proposes to it (proposals[i] = u_i); else if g_i exists i joins
+ *     (proposals[i] = -2 - agg[g_i]); else i proposes to itself (proposals[i] = i).  Aggregated rows get -1.
+ *   match: a joining row gets its aggregate; a proposing row i with proposal k gets agg_i = min(i, k) if k
+ *     proposes to i (k == i: a singleton).  Each row writes only its own entry.  *unassigned_host = the rows
+ *     that still hold -1.  The caller stops if that is 0, equals the previous round's count, or is
+ *     < max_unassign_ratio * n.
+ *   leftover (once, if rows are left): reads agg_before, writes agg: agg_i = agg_before[g_i] if g_i exists,
+ *     else i; assigned rows are copied.
+ *   renumber: agg holds root row indices (agg[agg[i]] == agg[i]); the coarse index of an aggregate is the rank
+ *     of its root among all roots, ascending.  *num_aggregates_host = n_c.
+ * Coarse operator: map_entries turns the triplets (i, j, a_ij) of the sorted fine matrix, in storage order,
+ * into matrix_data entries (agg_i, agg_j, a_ij) (the layout of gkoc_soa_to_aos); gkoc_aos_to_soa,
+ * gkoc_sort_row_major (stable), gkoc_sum_duplicates_* (0 + v0 + v1 + ... in storage order) and
+ * gkoc_convert_idxs_to_ptrs make A_c of them.  Explicit zeros stay stored.
+ * Transfers, on (rows, cols, ld) like the dense entries: the member lists hold the rows of every aggregate in
+ * ascending order (member_ptrs: n_c + 1 entries; made with gkoc_sort_row_major on (agg_i, i)).
+ *   restrict:    b_c[J, c] = the sum over the members i of J, ascending, of r[i, c], sequential in T from 0 -
+ *                bit-identical to a row-sorted CSR product with P^T.
+ *   prolong_add: x[i, c] = x[i, c] + e[agg_i, c].
+ * Both read 4 or 8 bytes per fine row, check their host arguments only and never synchronise;
+ * check_transfers validates agg, member_ptrs and members ONCE, at generate.
+ * GKOC_E_INVALID before any kernel writes: null pointers, row pointers of W that do not ascend from 0, a
+ * column outside the matrix (select, leftover); a proposal outside the matrix (match); an entry of agg that is
+ * not a root (renumber); agg outside [0, n_coarse), a row or column index outside the matrix (map_entries);
+ * agg outside [0, n_coarse), member pointers that do not ascend from 0 to n_rows, a member outside the matrix
+ * (check_transfers); a stride smaller than the number of columns (restrict, prolong_add).
+ * select, match, leftover, renumber, map_entries and check_transfers are set-up entries: they take scratch from
+ * the arena and synchronise the stream.  No kernel uses an atomic: every output element has one writer.
+ * select / leftover: a group of 16, 32 or 64 lanes per row, chosen from the longest row of W of the call,
+ * lane = stored entry, the lexicographic maximum reduced across the group; a longer row is streamed by its
+ * wave.  No length cap, no serial path.  row_limits: the row lengths of W at which the kernel changes path,
+ * ascending, in limits_host[0 .. *count_host) (at most 4).
+ * The column-offset plan (above) and these entries: agg and the proposals are state of the aggregation, of the
+ * index width of the entry (gkoc_pgm_i32 / gkoc_pgm_i64) - never row_ptrs or col_idxs of a matrix, so the
+ * entries that write them do not belong to the plan's contract and notify nothing; the coarse triplets leave
+ * map_entries as matrix_data entries and become index arrays only through gkoc_aos_to_soa and
+ * gkoc_sort_row_major, which the contract lists.  Host results are long long. */
+typedef int32_t gkoc_pgm_i32;
+typedef int64_t gkoc_pgm_i64;
+int gkoc_pgm_row_limits(int* limits_host, int* count_host);
+#define GKOC_DECL_PGM_IDX(I, A, IN)                                                                          \
+    int gkoc_pgm_match_##IN(gkoc_stream_t s, int64_t n_rows, const I* proposals, A* agg,                     \
+                            long long* unassigned_host);                                                     \
+    int gkoc_pgm_renumber_##IN(gkoc_stream_t s, int64_t n_rows, A* agg, long long* num_aggregates_host);     \
+    int gkoc_pgm_check_transfers_##IN(gkoc_stream_t s, int64_t n_rows, int64_t n_coarse, const I* agg,       \
+                                      const I* member_ptrs, const I* members);
+GKOC_DECL_PGM_IDX(int32_t, gkoc_pgm_i32, i32)
+GKOC_DECL_PGM_IDX(int64_t, gkoc_pgm_i64, i64)
+#define GKOC_DECL_PGM(T, TN, I, A, IN)                                                                       \
+    int gkoc_pgm_select_##TN##_##IN(gkoc_stream_t s, int64_t n_rows, const I* w_rp, const I* w_ci,           \
+                                    const T* w_v, const T* d, const I* agg, A* proposals);                   \
+    int gkoc_pgm_leftover_##TN##_##IN(gkoc_stream_t s, int64_t n_rows, const I* w_rp, const I* w_ci,         \
+                                      const T* w_v, const T* d, const I* agg_before, A* agg);                \
+    int gkoc_pgm_map_entries_##TN##_##IN(gkoc_stream_t s, int64_t nnz, int64_t n_rows, int64_t n_coarse,     \
+                                         const I* agg, const I* row_idxs, const I* col_idxs, const T* vals,  \
+                                         void* entries);                                                     \
+    int gkoc_pgm_restrict_##TN##_##IN(gkoc_stream_t s, int64_t n_coarse, int64_t cols, const I* member_ptrs, \
+                                      const I* members, const T* r, int64_t ldr, T* b_coarse, int64_t ldb);  \
+    int gkoc_pgm_prolong_add_##TN##_##IN(gkoc_stream_t s, int64_t n_rows, int64_t cols, const I* agg,        \
+                                         const T* e, int64_t lde, T* x, int64_t ldx);
+GKOC_DECL_PGM(double, f64, int32_t, gkoc_pgm_i32, i32)
+GKOC_DECL_PGM(double, f64, int64_t, gkoc_pgm_i64, i64)
+GKOC_DECL_PGM(float, f32, int32_t, gkoc_pgm_i32, i32)
+GKOC_DECL_PGM(float, f32, int64_t, gkoc_pgm_i64, i64)
+
 #ifdef __cplusplus
 }
 #endif
