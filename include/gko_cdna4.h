@@ -2787,6 +2787,144 @@ GKOC_DECL_PGM(double, f64, int64_t, gkoc_pgm_i64, i64)
 GKOC_DECL_PGM(float, f32, int32_t, gkoc_pgm_i32, i32)
 GKOC_DECL_PGM(float, f32, int64_t, gkoc_pgm_i64, i64)
 
+/* ------------------------------------- Batched solvers (gko::batch): batch::matrix::Csr / Ell, batch::MultiVector,
+ * batch::solver::Cg / Bicgstab, batch::preconditioner::Jacobi (scalar), log::BatchConvergence
+ * `items` independent systems share ONE sparsity pattern - an ordinary Csr pattern (row_ptrs, col_idxs) or Ell
+ * pattern (ell_k slots, column-major with ell_stride, padding -1), int32 only - and every item has its own
+ * values: items x nnz (Csr) or items x (ell_k * ell_stride) (Ell), item after item.  A multi-vector is
+ * items x rows x cols, row-major with a row stride ld >= cols, item after item (item stride rows * ld).  The
+ * solvers take ONE right-hand side per item (cols == 1; ldb / ldx are the row strides of b and x).
+ * The arithmetic is fixed: every multiply, add, subtract, divide and sqrt is a separate operation in T, so f64
+ * and f32 results are bit-identical to the following (tests/batch_refs.py restates it in numpy).
+ * Product y = A u: y_i = the sequential sum from +0 over the stored entries of row i in storage order of
+ *   a_ij * u_j; Ell: the slots 0 .. ell_k-1 in order, padding slots skipped.  Bit-identical to the row loop of the
+ *   single-matrix reference.  advanced: x = (alpha * y) + (beta * x), alpha and beta one per item.
+ * Reduction R_W(t_0 .. t_{n-1}), W a power of two: p_l (l < W) = the sequential sum from +0 of t_l, t_{l+W},
+ *   t_{l+2W}, ...; then for d = W/2, W/4, ..., 1: p_l = p_l + p_{l+d} for l < d; the result is p_0.
+ *   dot(u, v) = R_W(u_i * v_i), nrm(u) = sqrt(R_W(u_i * u_i)).  W depends on the number of rows alone: 64 up to
+ *   64 rows, 128 up to 128, 256 up to 768, 512 beyond; gkoc_batch_plan reports it.
+ * Preconditioner M: GKOC_BATCH_IDENTITY: z = r.  GKOC_BATCH_JACOBI: z_i = dinv_i * r_i with dinv_i = 1 / a_ii for
+ *   the first stored entry of row i with column i, dinv_i = 1 where none is stored or a_ii == 0.  The solver
+ *   kernel builds dinv from the item's own values in its prologue: there is no generate entry.
+ * Threshold: tau = T(tol) (GKOC_BATCH_ABSOLUTE) or T(tol) * nrm(b) (GKOC_BATCH_RELATIVE).  stop(res, it) means
+ *   res <= tau, or res is NaN, or it == max_iterations.  converged = (res <= tau) at the end.
+ * Cg, per item: r = b - A x; z = M r; p = z; rho = dot(r, z); res = nrm(r); it = 0.  Loop: if stop: end;
+ *   t = A p; alpha = rho / dot(p, t); x_i = x_i + alpha * p_i; r_i = r_i - alpha * t_i; res = nrm(r); it += 1;
+ *   if stop: end; z = M r; rho_new = dot(r, z); beta = rho_new / rho; p_i = z_i + beta * p_i; rho = rho_new.
+ * Bicgstab, per item: r = b - A x; r_hat = r; p = v = 0; rho_old = alpha = omega = 1; res = nrm(r); it = 0.
+ *   Loop: if stop: end; rho = dot(r_hat, r); beta = (rho / rho_old) * (alpha / omega);
+ *   p_i = r_i + beta * (p_i - omega * v_i); p_hat = M p; v = A p_hat; alpha = rho / dot(r_hat, v);
+ *   s_i = r_i - alpha * v_i; res = nrm(s); if res <= tau or res is NaN: x_i = x_i + alpha * p_hat_i; it += 1;
+ *   end; s_hat = M s; t = A s_hat; omega = dot(t, s) / dot(t, t);
+ *   x_i = (x_i + alpha * p_hat_i) + omega * s_hat_i; r_i = s_i - omega * t_i; res = nrm(r); rho_old = rho;
+ *   it += 1.
+ * Breakdown: no guard beyond IEEE arithmetic; a zero denominator gives inf or NaN and the NaN rule stops the
+ *   item with converged = 0.  An item's result depends on nothing but that item.
+ * Outputs per item: iteration_counts (int), residual_norms (T), converged (int: 0 / 1); x is updated in place.
+ * The solve is ONE launch: one workgroup of W threads per item, thread l owns the rows l, l + W, ..., every item
+ * leaves the loop on its own.  No atomics, no waiting between workgroups.
+ * LDS residency.  A workgroup uses up to 81920 bytes, half of a CU's LDS, so that two workgroups share a CU (one
+ * workgroup with all 163840 bytes was measured and lost at 1024 rows).  2 * W values of it hold the partials of
+ * R_W; a vector takes n values rounded up to 16 bytes.  The vectors of a solver have a FIXED residency order
+ * (the inputs of the products first, x last; bracketed ones exist with Jacobi only - with M = I z, p_hat and
+ * s_hat are r, p and s themselves):
+ *   Cg:        p, r, t, [z, dinv,] x                              4 or 6 vectors
+ *   Bicgstab:  [p_hat, s_hat,] p, s, r, r_hat, v, t, [dinv,] x    7 or 10 vectors
+ * The first `resident_vectors` of the order live in LDS, as many as fit; the others live in the caller's
+ * workspace, workspace_bytes per item, except x, which is then updated in the caller's array.  The item's matrix
+ * values are NOT cached in LDS (values_cached is always 0): the copy was measured and cost more in workgroups
+ * per CU than it saved in reads.  No system size is refused: a system too large for LDS runs from the workspace.
+ * Results do not depend on the residency.
+ * gkoc_batch_plan is host only (no device call): for solver / format / precond (the codes below), value_bytes
+ * (4 or 8), n_rows and the stored values per item (Csr: nnz, Ell: ell_k * ell_stride) it fills the plan the
+ * launcher uses.
+ * The hot entries (solvers, apply, multi-vector, conversions) check host arguments only and never synchronise:
+ * GKOC_E_INVALID for null pointers, negative sizes, short strides, an unknown code, a workspace smaller than
+ * items * workspace_bytes.  The pattern is checked ONCE, when a batch matrix is made, by the set-up entries
+ * gkoc_batch_csr_check_i32 / gkoc_batch_ell_check_i32, which synchronise: GKOC_E_INVALID for row pointers that do
+ * not ascend from 0 to nnz, a column outside the matrix, an Ell slot that is neither -1 nor inside.
+ * Multi-vector: scale x = alpha * x; add_scaled x = x + alpha * b; alpha is items x alpha_cols with alpha_cols 1
+ * (one scalar per item) or cols (one per column).  compute_dot / compute_norm2: result[item, col] = dot / nrm of
+ * the columns, R_W with the W of `rows`.
+ * Values-only conversions for all items at once (the shared pattern is converted once, as a single matrix, with
+ * gkoc_csr_convert_to_ell / gkoc_ell_count_nonzeros_per_row + gkoc_ell_to_csr): csr_to_ell_values writes EVERY
+ * slot (the k-th stored entry of row i at i + k * ell_stride, 0 elsewhere); ell_to_csr_values writes the stored
+ * slots of a row in slot order, padding skipped wherever it sits.
+ * Every index pointer of these entries is const: none writes an index array, none belongs to the column-offset
+ * plan's contract.  The iteration counts and converged flags are plain int. */
+#define GKOC_BATCH_CG 0
+#define GKOC_BATCH_BICGSTAB 1
+#define GKOC_BATCH_CSR 0
+#define GKOC_BATCH_ELL 1
+#define GKOC_BATCH_IDENTITY 0
+#define GKOC_BATCH_JACOBI 1
+#define GKOC_BATCH_ABSOLUTE 0
+#define GKOC_BATCH_RELATIVE 1
+typedef struct {
+    int32_t w;                /* workgroup width = the W of R_W */
+    int32_t resident_vectors; /* the first so many of the residency order live in LDS */
+    int32_t total_vectors;
+    int32_t values_cached;    /* 1: the item's values are copied to LDS (always 0, see above) */
+    int64_t lds_bytes;        /* dynamic LDS of the launch */
+    int64_t workspace_bytes;  /* per item */
+} gkoc_batch_plan_info;
+int gkoc_batch_plan(int solver, int format, int precond, int value_bytes, int64_t n_rows,
+                    int64_t stored_per_item, gkoc_batch_plan_info* plan_host);
+int gkoc_batch_csr_check_i32(gkoc_stream_t s, int64_t n_rows, int64_t n_cols, int64_t nnz,
+                             const int32_t* row_ptrs, const int32_t* col_idxs);
+int gkoc_batch_ell_check_i32(gkoc_stream_t s, int64_t n_rows, int64_t n_cols, int64_t ell_k, int64_t ell_stride,
+                             const int32_t* ell_cols);
+#define GKOC_DECL_BATCH_SOLVER(NAME, T, TN)                                                                  \
+    int gkoc_batch_##NAME##_csr_##TN##_i32(                                                                  \
+        gkoc_stream_t s, int64_t items, int64_t n_rows, int64_t nnz, const int32_t* row_ptrs,                \
+        const int32_t* col_idxs, const T* vals, int precond, const T* b, int64_t ldb, T* x, int64_t ldx,     \
+        double tol, int tol_type, int64_t max_iterations, void* workspace, size_t workspace_bytes,           \
+        int* iteration_counts, T* residual_norms, int* converged);                                           \
+    int gkoc_batch_##NAME##_ell_##TN##_i32(                                                                  \
+        gkoc_stream_t s, int64_t items, int64_t n_rows, int64_t ell_k, int64_t ell_stride,                   \
+        const int32_t* ell_cols, const T* vals, int precond, const T* b, int64_t ldb, T* x, int64_t ldx,     \
+        double tol, int tol_type, int64_t max_iterations, void* workspace, size_t workspace_bytes,           \
+        int* iteration_counts, T* residual_norms, int* converged);
+GKOC_DECL_BATCH_SOLVER(cg, double, f64)
+GKOC_DECL_BATCH_SOLVER(cg, float, f32)
+GKOC_DECL_BATCH_SOLVER(bicgstab, double, f64)
+GKOC_DECL_BATCH_SOLVER(bicgstab, float, f32)
+#define GKOC_DECL_BATCH(T, TN)                                                                               \
+    int gkoc_batch_csr_apply_##TN##_i32(gkoc_stream_t s, int64_t items, int64_t n_rows, int64_t n_cols,      \
+                                        int64_t nnz, const int32_t* row_ptrs, const int32_t* col_idxs,       \
+                                        const T* vals, const T* b, int64_t ldb, T* x, int64_t ldx,           \
+                                        int64_t cols);                                                       \
+    int gkoc_batch_csr_advanced_apply_##TN##_i32(                                                            \
+        gkoc_stream_t s, int64_t items, int64_t n_rows, int64_t n_cols, int64_t nnz, const T* alpha,         \
+        const int32_t* row_ptrs, const int32_t* col_idxs, const T* vals, const T* b, int64_t ldb,            \
+        const T* beta, T* x, int64_t ldx, int64_t cols);                                                     \
+    int gkoc_batch_ell_apply_##TN##_i32(gkoc_stream_t s, int64_t items, int64_t n_rows, int64_t n_cols,      \
+                                        int64_t ell_k, int64_t ell_stride, const int32_t* ell_cols,          \
+                                        const T* vals, const T* b, int64_t ldb, T* x, int64_t ldx,           \
+                                        int64_t cols);                                                       \
+    int gkoc_batch_ell_advanced_apply_##TN##_i32(                                                            \
+        gkoc_stream_t s, int64_t items, int64_t n_rows, int64_t n_cols, int64_t ell_k, int64_t ell_stride,   \
+        const T* alpha, const int32_t* ell_cols, const T* vals, const T* b, int64_t ldb, const T* beta,      \
+        T* x, int64_t ldx, int64_t cols);                                                                    \
+    int gkoc_batch_scale_##TN(gkoc_stream_t s, int64_t items, int64_t rows, int64_t cols, const T* alpha,    \
+                              int64_t alpha_cols, T* x, int64_t ldx);                                        \
+    int gkoc_batch_add_scaled_##TN(gkoc_stream_t s, int64_t items, int64_t rows, int64_t cols,               \
+                                   const T* alpha, int64_t alpha_cols, const T* b, int64_t ldb, T* x,        \
+                                   int64_t ldx);                                                             \
+    int gkoc_batch_compute_dot_##TN(gkoc_stream_t s, int64_t items, int64_t rows, int64_t cols, const T* a,  \
+                                    int64_t lda, const T* b, int64_t ldb, T* result);                        \
+    int gkoc_batch_compute_norm2_##TN(gkoc_stream_t s, int64_t items, int64_t rows, int64_t cols,            \
+                                      const T* a, int64_t lda, T* result);                                   \
+    int gkoc_batch_csr_to_ell_values_##TN##_i32(gkoc_stream_t s, int64_t items, int64_t n_rows, int64_t nnz, \
+                                                const int32_t* row_ptrs, int64_t ell_k, int64_t ell_stride,  \
+                                                const T* csr_vals, T* ell_vals);                             \
+    int gkoc_batch_ell_to_csr_values_##TN##_i32(gkoc_stream_t s, int64_t items, int64_t n_rows,              \
+                                                int64_t ell_k, int64_t ell_stride, const int32_t* ell_cols,  \
+                                                int64_t nnz, const int32_t* row_ptrs, const T* ell_vals,     \
+                                                T* csr_vals);
+GKOC_DECL_BATCH(double, f64)
+GKOC_DECL_BATCH(float, f32)
+
 #ifdef __cplusplus
 }
 #endif
