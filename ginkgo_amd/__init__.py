@@ -2,7 +2,7 @@
 
 Thin host-side mirror of the gko::Executor / gko::LinOp / solver-factory
 interface over the C ABI of libgko_cdna4.so (include/gko_cdna4.h): CSR / ELL /
-SELL-P / Fbcsr SpMV, block-Jacobi, level-scheduled triangular solves with Sor / SSOR, ILU(0) / IC(0) with Ilu / Ic, triangular ISAI (LowerIsai / UpperIsai), Pgm aggregation and a Multigrid solver / preconditioner, batched Cg / Bicgstab on batch Csr / Ell (ginkgo_amd.batch), BLAS-1 and the fused CG steps as hand-written HIP
+SELL-P / Fbcsr SpMV, block-Jacobi, level-scheduled triangular solves with Sor / SSOR, ILU(0) / IC(0) with Ilu / Ic, triangular ISAI (LowerIsai / UpperIsai), general and spd ISAI (GeneralIsai / SpdIsai), Pgm aggregation and a Multigrid solver / preconditioner, batched Cg / Bicgstab on batch Csr / Ell (ginkgo_amd.batch), BLAS-1 and the fused CG steps as hand-written HIP
 kernels.  Importing the package does not need a GPU; creating a
 Cdna4Executor does, and there is no CPU fallback.
 """
@@ -13,7 +13,7 @@ from .matrix import (Coo, Csr, Dense, DeviceMatrixData, Ell, Fbcsr, Hybrid, Sell
                      stencil_csr)
 from .preconditioner import GaussSeidel, Ic, Ilu, Jacobi, Sor, compute_storage_scheme
 from .triangular import LowerTrs, UpperTrs
-from .isai import LowerIsai, UpperIsai
+from .isai import GeneralIsai, LowerIsai, SpdIsai, UpperIsai
 from .multigrid import Multigrid, Pgm
 from . import multigrid
 from . import batch
@@ -22,7 +22,7 @@ from .solver import Cg, Gmres, Identity, ortho_method
 from .krylov import Bicg, Bicgstab, Cgs, Chebyshev, Fcg, Gcr, Ir, Minres, PipeCg
 from . import stop
 
-__all__ = ["LowerTrs", "UpperTrs", "LowerIsai", "UpperIsai", "Pgm", "Multigrid", "multigrid", "batch", "Sor", "GaussSeidel", "Ilu", "Ic", "factorization","Coo", "DeviceMatrixData", "entry_dtype", "Hybrid", "Bicg", "Bicgstab", "Chebyshev", "Gcr", "Ir", "Minres", "Cgs", "Fcg", "PipeCg", "Cdna4Executor", "Csr", "Dense", "Ell", "Fbcsr", "Sellp", "scalar",
+__all__ = ["LowerTrs", "UpperTrs", "LowerIsai", "UpperIsai", "GeneralIsai", "SpdIsai", "Pgm", "Multigrid", "multigrid", "batch", "Sor", "GaussSeidel", "Ilu", "Ic", "factorization","Coo", "DeviceMatrixData", "entry_dtype", "Hybrid", "Bicg", "Bicgstab", "Chebyshev", "Gcr", "Ir", "Minres", "Cgs", "Fcg", "PipeCg", "Cdna4Executor", "Csr", "Dense", "Ell", "Fbcsr", "Sellp", "scalar",
            "stencil_csr", "Jacobi", "compute_storage_scheme", "Cg", "Gmres", "ortho_method", "Identity",
            "stop", "GkoError", "NotCompiled", "NotSupported",
            "DimensionMismatch", "LIB_PATH"]

@@ -22,6 +22,11 @@ entry (a zero pivot) becomes the identity's row, as in Ginkgo.
 `with_excess_limit`, `with_excess_solver_factory` and `with_excess_solver_reduction` are accepted for API
 compatibility and have no effect: Ginkgo moves rows longer than 32 entries into an excess system that an
 iterative solver handles; the kernel here has no cap on the row length, so no row is ever moved.
+
+`GeneralIsai` and `SpdIsai` (preconditioner::GeneralIsai / SpdIsai) take the system matrix itself: nothing is
+factorised, every row of W solves one small dense system with partial pivoting
+(gkoc_isai_generate_general_inverse_*), so generate is one launch per path.  GeneralIsai applies W (one SpMV),
+SpdIsai applies W^T W (two SpMVs over a lower triangular W); see the classes.
 """
 import ctypes as C
 
@@ -30,7 +35,7 @@ import torch
 from ._lib import IT, VT, DimensionMismatch, GkoError, NotSupported, call
 from .base import LinOp
 from .executor import MEM_INDICES, MEM_VALUES
-from .matrix import Csr, DeviceMatrixData, Fbcsr
+from .matrix import Csr, Dense, DeviceMatrixData, Fbcsr
 
 
 def row_limits():
@@ -115,7 +120,8 @@ def _pattern_power(ex, a, power):
 
 
 class _Isai(LinOp):
-    _LOWER = True
+    _ENTRY, _FLAG = "gkoc_isai_generate_tri_inverse_", 1    # the generate entry and its is_lower / spd argument
+    _LOWER_PATTERN = False      # W lives on the lower triangle of the pattern (SpdIsai)
     _OTHER = None       # the class of the transpose, set below
 
     def __init__(self, factory, a):
@@ -139,9 +145,11 @@ class _Isai(LinOp):
             rp, ci = a.row_ptrs, a.col_idxs
         else:
             rp, ci = _pattern_power(ex, a, self.sparsity_power)
+        if self._LOWER_PATTERN:
+            rp, ci = _lower_pattern(ex, a.size, rp, ci, a.dtype)
         w = ex.alloc((ci.numel(),), a.dtype, MEM_VALUES)
-        call(f"gkoc_isai_generate_tri_inverse_{VT[a.dtype]}_{IT[ci.dtype]}", ex.stream, n,
-             C.c_int(int(self._LOWER)), a.row_ptrs, a.col_idxs, a.values, rp, ci, w)
+        call(f"{self._ENTRY}{VT[a.dtype]}_{IT[ci.dtype]}", ex.stream, n, C.c_int(self._FLAG), a.row_ptrs,
+             a.col_idxs, a.values, rp, ci, w)
         self.inverse = Csr(ex, a.size, w, ci, rp)
         ex.synchronize()                # a sorted copy is released on return
 
@@ -171,7 +179,7 @@ class _Isai(LinOp):
 
 class LowerIsai(_Isai):
     """W ~ L^-1 on the pattern of |L|^power for a lower triangular L; apply is one CSR SpMV."""
-    _LOWER = True
+    _FLAG = 1
 
     @staticmethod
     def build():
@@ -180,7 +188,7 @@ class LowerIsai(_Isai):
 
 class UpperIsai(_Isai):
     """W ~ U^-1 on the pattern of |U|^power for an upper triangular U; apply is one CSR SpMV."""
-    _LOWER = False
+    _FLAG = 0
 
     @staticmethod
     def build():
@@ -188,3 +196,101 @@ class UpperIsai(_Isai):
 
 
 LowerIsai._OTHER, UpperIsai._OTHER = UpperIsai, LowerIsai
+
+
+def general_row_limits():
+    """the pattern-row lengths at which the general / spd generate kernel changes path; the last one is the
+    cap, the longest pattern row it takes (gkoc_isai_general_row_limits)"""
+    limits, count = (C.c_int * 4)(), C.c_int(0)
+    call("gkoc_isai_general_row_limits", limits, C.byref(count))
+    return [int(limits[p]) for p in range(count.value)]
+
+
+def _lower_pattern(ex, size, rp, ci, dtype):
+    """(row_ptrs, col_idxs) of the lower triangle, diagonal included, of the sorted pattern (rp, ci): the index
+    arrays of the Sor / Ic set-up (every row must store its diagonal, which then is its last entry)"""
+    n, it = size[0], IT[ci.dtype]
+    shift, missing = ex.alloc((n + 1,), rp.dtype), C.c_int64(0)
+    call("gkoc_csr_missing_diagonal_shift_" + it, ex.stream, n, n, rp, ci, shift, C.byref(missing))
+    if missing.value:
+        raise GkoError(f"SpdIsai: {missing.value} rows of the system matrix store no diagonal entry")
+    l_rp = ex.alloc((n + 1,), rp.dtype, MEM_INDICES)
+    call("gkoc_factorization_initialize_row_ptrs_l_u_" + it, ex.stream, n, rp, ci, l_rp, None)
+    nnz = int(l_rp[-1].item())
+    l_ci = ex.alloc((nnz,), ci.dtype, MEM_INDICES)
+    ones, unused = ex.alloc((ci.numel(),), dtype).fill_(1), ex.alloc((nnz,), dtype)
+    call(f"gkoc_sor_initialize_weighted_l_{VT[dtype]}_{it}", ex.stream, n, rp, ci, ones, C.c_double(1.0), l_rp,
+         l_ci, unused)
+    ex.synchronize()                    # `shift`, `ones` and `unused` are released on return
+    return l_rp, l_ci
+
+
+class GeneralIsai(_Isai):
+    """W ~ A^-1 on the pattern of |A|^power for any square A: (W A)(i, S_i) = e_i(S_i), one small dense system
+    per row, solved by Gauss-Jordan with partial pivoting (gkoc_isai_generate_general_inverse_*, spd = 0; the
+    arithmetic is stated in include/gko_cdna4.h).  Nothing is factorised and no row depends on another, so
+    generate is one launch (two if the pattern has rows on both sides of 64 entries).  apply is one CSR SpMV.
+
+    With power 1 W shares A's row_ptrs / col_idxs; with power p > 1 the pattern is made as for LowerIsai.
+    Unsorted input is sorted on a copy unless with_skip_sorting(True); the caller's matrix is never changed.
+
+    There is no excess system: Ginkgo moves rows longer than 32 entries to an iterative solver; here pattern
+    rows up to general_row_limits()[-1] entries are solved exactly and a longer one is refused (NotSupported).
+    with_excess_limit, with_excess_solver_factory and with_excess_solver_reduction are accepted without effect."""
+
+    _ENTRY, _FLAG = "gkoc_isai_generate_general_inverse_", 0
+
+    @staticmethod
+    def build():
+        return _IsaiFactory(GeneralIsai)
+
+
+GeneralIsai._OTHER = GeneralIsai        # transpose(): a GeneralIsai around Csr.transpose() of the inverse
+
+
+class SpdIsai(_Isai):
+    """W^T W ~ A^-1 for a symmetric positive definite A, W lower triangular on the lower triangle (diagonal
+    included) of the pattern of |A|^power: row i of W solves its dense system (both triangles of A are read)
+    and is divided by the square root of its diagonal entry (gkoc_isai_generate_general_inverse_*, spd = 1).
+    Every row of A must store its diagonal.  The lower pattern comes from the index arrays of the Sor / Ic
+    set-up; W^T is made once at generate with Csr.transpose().
+
+    apply is x = W^T (W b), two CSR SpMVs through an intermediate vector that is kept per column count and
+    value type (allocated at the first apply with that shape); apply(alpha, b, beta, x) is
+    x = alpha W^T (W b) + beta x.  No apply copies to the host or synchronises.
+
+    get_approximate_inverse() returns W; transpose() returns self (the operator is symmetric).  As for
+    GeneralIsai there is no excess system: rows up to general_row_limits()[-1] entries are solved exactly,
+    longer ones refused, and the three excess setters are accepted without effect."""
+    _ENTRY, _FLAG, _LOWER_PATTERN = "gkoc_isai_generate_general_inverse_", 1, True
+
+    @staticmethod
+    def build():
+        return _IsaiFactory(SpdIsai)
+
+    def __init__(self, factory, a):
+        super().__init__(factory, a)
+        self.inverse_t = self.inverse.transpose()
+        self._between = {}
+
+    def _intermediate(self, b):
+        key = (b.size[1], b.dtype)
+        t = self._between.get(key)
+        if t is None:
+            t = self._between[key] = Dense.create(self.exec, (self.size[0], b.size[1]), b.dtype)
+        return t
+
+    def transpose(self):
+        return self
+
+    conj_transpose = transpose
+
+    def apply_impl(self, b, x):
+        t = self._intermediate(b)
+        self.inverse.apply_impl(b, t)
+        self.inverse_t.apply_impl(t, x)
+
+    def apply_advanced_impl(self, alpha, b, beta, x):
+        t = self._intermediate(b)
+        self.inverse.apply_impl(b, t)
+        self.inverse_t.apply_advanced_impl(alpha, t, beta, x)

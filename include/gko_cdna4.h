@@ -2697,6 +2697,57 @@ GKOC_DECL_ISAI(double, f64, int64_t, i64)
 GKOC_DECL_ISAI(float, f32, int32_t, i32)
 GKOC_DECL_ISAI(float, f32, int64_t, i64)
 
+/* ------------------------------------- general and spd ISAI (preconditioner::GeneralIsai / SpdIsai)
+ * isai::generate_general_inverse (reference/preconditioner/isai_kernels.cpp): the VALUES w_v of the incomplete
+ * sparse approximate inverse W of a square matrix A on a given pattern, (W A)(i, S_i) = e_i(S_i) for every row
+ * i.  A need not be triangular and nothing is factorised: every row solves a small dense system with pivoting.
+ * Every index pointer is const; the pattern (w_rp, w_ci) is the caller's - A's own arrays (the same pointers
+ * may be passed), the pattern of |A|^p made as for the triangular entry, or (spd) its lower triangle.
+ * Input: A is square, rows sorted by column.  Row i of the pattern is sorted and contains i; for spd != 0 every
+ * column of pattern row i is <= i, so i is its last entry.  For row i let c_0 < ... < c_{m-1} be its pattern
+ * columns and p the position of i among them (spd: p = m-1).
+ * The dense system: M is m x m, M[j][k] = a[c_k, c_j] where A stores that entry and 0 elsewhere - this is
+ * (A(S_i, S_i))^T, and BOTH triangles of A are read in the spd case too.  The right-hand side is r = e_p.
+ * The solve is Gauss-Jordan with implicit partial pivoting, every multiply, subtract and divide a separate
+ * operation in T, so f64 and f32 results are bit-identical to: for col = 0 .. m-1
+ *   1. the pivot q(col) is the row not yet used as a pivot with the largest |M[r][col]|; on a tie the smallest r;
+ *   2. for every row r != q, used as a pivot earlier or not, f = M[r][col] / M[q][col];
+ *   3. with that f, for k = col+1 .. m-1: M[r][k] = M[r][k] - f * M[q][k] (no skip when f is zero);
+ *   4. with the same f, r[r] = r[r] - f * r[q].
+ * After all columns w[c_col] = r[q(col)] / M[q(col)][col].
+ * NaN: a NaN anywhere in M ends in a non-finite w whatever pivot is taken - every row is a pivot once, a NaN
+ * pivot poisons every other right-hand side and a NaN elsewhere in the column poisons its own - so the order
+ * among NaNs is free.  The kernel (and tests/isai_general_refs.py) count a NaN as the largest magnitude.
+ * spd scaling: after the solve d = sqrt(w[c_{m-1}]), then w[c_t] = w[c_t] / d for every t (correctly rounded
+ * sqrt and division); W^T W then approximates A^-1.
+ * Non-finite rule: if any w of a row is not finite, the row becomes all zeros with 1 at position p (Ginkgo's
+ * rule, and the triangular entry's).  This covers a zero pivot and, for spd, a negative or zero w[c_{m-1}].
+ * An element's sequence of updates does not depend on the data layout, so lane = row or lane = column,
+ * registers or LDS give the same bits.
+ * GKOC_E_INVALID before any kernel touches w_v: null pointers, row pointers (of A or of the pattern) that do
+ * not ascend from 0, a column outside the matrix, a row of A or of the pattern that is not strictly ascending,
+ * a pattern row without its diagonal, for spd a pattern entry above the diagonal.  GKOC_E_NOT_SUPPORTED, also
+ * before any write: a pattern row longer than the cap (the message names the length and the cap).  n_rows = 0
+ * is GKOC_OK.  Set-up: the call takes scratch from the arena and synchronises the stream once (for the checks);
+ * it is not meant to be captured.
+ * Launch: all rows of a path go in ONE launch (no row depends on another).  Pattern rows of at most 64 entries
+ * are solved by a group of 16, 32 or 64 lanes chosen from the longest pattern row of the call, lane = row of M,
+ * M in LDS; rows of 65 .. cap entries by one workgroup each, M in LDS.  A call with rows on both sides of 64
+ * launches twice, each launch skipping the other's rows.  Every entry of w_v is written by exactly one lane;
+ * there are no atomics on values.  There is no excess system: Ginkgo moves rows above 32 entries to an
+ * iterative solver, here rows up to the cap are solved exactly and longer ones are refused.
+ * general_row_limits: the pattern-row lengths at which the kernel changes path, ascending, in
+ * limits_host[0 .. *count_host) (at most 4); the LAST one is the cap (128 for both value types). */
+int gkoc_isai_general_row_limits(int* limits_host, int* count_host);
+#define GKOC_DECL_ISAI_GENERAL(T, TN, I, IN)                                                                 \
+    int gkoc_isai_generate_general_inverse_##TN##_##IN(gkoc_stream_t s, int64_t n_rows, int spd,             \
+                                                       const I* a_rp, const I* a_ci, const T* a_v,           \
+                                                       const I* w_rp, const I* w_ci, T* w_v);
+GKOC_DECL_ISAI_GENERAL(double, f64, int32_t, i32)
+GKOC_DECL_ISAI_GENERAL(double, f64, int64_t, i64)
+GKOC_DECL_ISAI_GENERAL(float, f32, int32_t, i32)
+GKOC_DECL_ISAI_GENERAL(float, f32, int64_t, i64)
+
 /* ------------------------------------- Pgm aggregation (multigrid::Pgm) and its grid transfers
  * One level of an aggregation multigrid hierarchy: rows of A are grouped into aggregates (agg), the coarse
  * operator is A_c = P^T A P with P(i, agg_i) = 1, and P / P^T are applied from agg and the member lists, never

@@ -1,7 +1,9 @@
 """Triangular ISAI on the IC(0) factor of the 27-point Laplacian (natural ordering: 7 (g - 1) + 1 levels): the
 generate time for the sparsity powers 1 and 2, one application of Ic with the level-scheduled solvers
 (LowerTrs / UpperTrs) against Ic with the ISAI solvers (two CSR SpMVs), and CG with both as iterations and as
-time to the same reduction.  f64 / int32.  (development / measurement tool)
+time to the same reduction; and SpdIsai (powers 1 and 2) and GeneralIsai (power 1) of the system matrix itself,
+which need no factorization: generate, nnz(W), one application, CG.  f64 / int32.  (development / measurement
+tool)
 
     python tools/isai_bench.py [grid ...]       default: 64 128
 
@@ -39,7 +41,7 @@ def apply_us(op, reps):
     return t * 1e6 / reps
 
 
-def cg(a, precond, reduction=1e-10):
+def cg(a, precond, reduction=1e-10, must_converge=True):
     s = (g.Cg.build()
          .with_criteria(g.stop.Iteration.build().with_max_iters(5000),
                         g.stop.ResidualNorm.build().with_reduction_factor(reduction))
@@ -49,8 +51,8 @@ def cg(a, precond, reduction=1e-10):
     s.apply(rhs, x)
     x.fill(0.0)
     _, t = wall(lambda: s.apply(rhs, x))
-    assert s.has_converged
-    return s.num_iterations, t
+    assert s.has_converged or not must_converge
+    return s.num_iterations if s.has_converged else -1, t
 
 
 for grid in grids:
@@ -77,6 +79,18 @@ for grid in grids:
         t_apply = apply_us(m, 50)
         its, t_cg = cg(a, m)
         print(f"  LowerIsai power {power}: generate {t_gen*1e3:9.1f} ms, nnz(W) = {nnz};  Ic + ISAI: apply "
+              f"{t_apply:10.1f} us;  CG {its:4d} iterations, {t_cg*1e3:9.2f} ms to 1e-10", flush=True)
+        del m
+    for cls, power in ((g.SpdIsai, 1), (g.SpdIsai, 2), (g.GeneralIsai, 1)):
+        def dense_solve_isai():
+            return cls.build().with_sparsity_power(power).on(ex).generate(a)
+        dense_solve_isai()                              # warm-up: code objects, arena
+        m, t_gen = wall(dense_solve_isai)
+        nnz = m.get_approximate_inverse().get_num_stored_elements()
+        t_apply = apply_us(m, 50)
+        # W of GeneralIsai is not symmetric: CG with it is shown for comparison, -1 = not converged
+        its, t_cg = cg(a, m, must_converge=cls is g.SpdIsai)
+        print(f"  {cls.__name__} power {power}: generate {t_gen*1e3:9.1f} ms, nnz(W) = {nnz};  apply "
               f"{t_apply:10.1f} us;  CG {its:4d} iterations, {t_cg*1e3:9.2f} ms to 1e-10", flush=True)
         del m
     jac = g.Jacobi.build().with_max_block_size(1).on(ex).generate(a)
