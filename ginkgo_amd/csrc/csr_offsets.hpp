@@ -22,7 +22,7 @@
 //   * the loads of the NEXT group's values are issued as soon as the registers are free, i.e. before the
 //     row phase of this one, and all x loads of this group before them (vmcnt is in-order: an x load issued
 //     behind the value loads would be waited for behind them);
-//   * row phase, lane = row: for d = 0 .. D-1 (compile-time index, wave-uniform exit in steps of 8) the load
+//   * row phase, lane = row: for d = 0 .. ND-1 (compile-time index; ND = 8 or 32 slots per kernel) the load
 //     of x[clamp(row + off_d)] is unconditional and in bounds, the value of an absent slot is never used:
 //     sum += v * x only where bit d of the mask is set, separate multiply and add, ascending d = storage
 //     order - the operations of the sequential reference in its order, hence its bits; an absent slot
@@ -90,32 +90,62 @@ __global__ __launch_bounds__(256) void csr_offsets_build_kernel(int64_t n_rows, 
 }
 
 // One workgroup: skip[w] = bit per segment "eligible" (| the long-row flags of csr_long_rows.hpp: what the
-// row-segment kernel leaves out when it runs beside this kernel), *count = eligible segments.
+// row-segment kernel leaves out when it runs beside this kernel), count[0] = eligible segments, count[1] = the
+// largest D of the plan (the launcher picks the product kernel's number of diagonal slots by it).
 __global__ __launch_bounds__(1024) void csr_offsets_finish_kernel(int64_t n_seg, const int32_t* __restrict__ seg_tab,
                                                                   const uint32_t* __restrict__ long_bits,
                                                                   uint32_t* __restrict__ skip,
                                                                   unsigned long long* __restrict__ count)
 {
     __shared__ long long part[16];
+    __shared__ int d_max;
+    if (threadIdx.x == 0) d_max = 0;
+    __syncthreads();
     const int64_t n_words = (n_seg + 31) / 32;
     long long mine = 0;
+    int my_d = 0;
     for (int64_t w = threadIdx.x; w < n_words; w += 1024) {
         uint32_t bits = 0;
         for (int j = 0; j < 32; ++j) {
             const int64_t s = w * 32 + j;
-            if (s < n_seg && seg_tab[s * OFFS_TAB] > 0) bits |= 1u << j;
+            const int D = s < n_seg ? seg_tab[s * OFFS_TAB] : 0;
+            if (D > 0) bits |= 1u << j;
+            my_d = D > my_d ? D : my_d;
         }
         mine += __popc(bits);
         skip[w] = long_bits != nullptr ? (bits | long_bits[w]) : bits;
     }
+    atomicMax(&d_max, my_d);
     const long long total = block_sum<1024>(mine, part);
-    if (threadIdx.x == 0) *count = static_cast<unsigned long long>(total);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        count[0] = static_cast<unsigned long long>(total);
+        count[1] = static_cast<unsigned long long>(d_max);
+    }
 }
 
 // T = double / float, 32-bit indices.  ADV: c = alpha A x + beta c.  DOT: also this wave's part of <x, c>
 // (gkoc_x_csr_spmv_dot_*; the same lane-to-row assignment, per-wave butterfly and slot as the row-segment
 // kernel, so the folded value has the same bits).
-template <typename T, bool ADV, bool DOT>
+//
+// The schedule of a group, which the wait counts of the compiled kernel depend on (vmcnt retires in order; a
+// load issued under a condition makes the compiler count at the join as if it had not been issued, and every
+// later wait is then too strict by that many loads):
+//   1. the group's row-pointer, mask and ND x loads, from offsets that are already in scalar registers - ND,
+//      the number of diagonal slots, is the KERNEL's (8 or 32, picked by the launcher from the plan's largest
+//      D), not the segment's: a count that depended on the segment would be a condition again.  A segment with
+//      fewer offsets has offset 0 and mask bit 0 in the slots it lacks: in-bounds loads that no sum reads;
+//   2. the scalar loads of the NEXT unit (D, row pointers, offsets): under way while the values arrive;
+//   3. the group's values, in flight since the previous group's step 4, go to the stage: all NL chunks of
+//      every lane, no branch (entries at or behind `len` are never read: pos < len for every stored slot);
+//   4. the NL value loads of the next group, ALWAYS issued, from ONE load site in the loop (and one in front
+//      of it), so v[] has one register home and the compiler a static count of loads behind every x load;
+//   5. the row phase: the wait in front of its last x leaves the NL loads of step 4 in flight.
+// "Always" because the loop runs over the groups that HAVE a successor; the wave's last group does 1 - 3 and 5
+// behind it.  (Issuing step 4 there too, as re-reads of the group's last 16 bytes, was measured: with two
+// segments per wave every second prefetch is then a dummy, and the kernel was 3.7 % slower than with the
+// conditional prefetch it replaced, docs/KERNELS.md 36.)
+template <typename T, bool ADV, bool DOT, int ND>
 __global__ __launch_bounds__(64, 2) void csr_spmv_pipe3_kernel_offsets(
     int32_t n_rows, int32_t n_cols, int64_t n_segments, int spw, const int32_t* __restrict__ row_ptrs,
     const T* __restrict__ vals, const T* __restrict__ x, T* __restrict__ c, const T* __restrict__ alpha_p,
@@ -126,15 +156,14 @@ __global__ __launch_bounds__(64, 2) void csr_spmv_pipe3_kernel_offsets(
     constexpr int E = 16 / sizeof(T);                  // entries per lane and load
     constexpr int CAP = GR * OFFS_MAX;                 // entries of a group at most
     constexpr int NL = CAP / (64 * E) + 1;             // loads per lane: the stream starts up to E - 1 entries early
-    constexpr int GPS = 64 / GR;                       // groups per segment
     // (a native vector type: an array of structs of this size is not kept in registers by the compiler)
     typedef T VT __attribute__((ext_vector_type(E)));
-    __shared__ __attribute__((aligned(16))) T stage[CAP + E];
+    __shared__ __attribute__((aligned(16))) T stage[NL * 64 * E];
 
     const int lane = threadIdx.x;
     const int64_t wave_id = blockIdx.x;
     const int64_t sb = wave_id * spw;
-    const int n_units = int((sb + spw < n_segments ? int64_t(spw) : n_segments - sb)) * GPS;
+    const int n_units = int(sb + spw < n_segments ? int64_t(spw) : n_segments - sb);
     T alpha = T(1), beta = T(0);
     if (ADV) {
         alpha = alpha_p[0];
@@ -143,33 +172,55 @@ __global__ __launch_bounds__(64, 2) void csr_spmv_pipe3_kernel_offsets(
     T dot_acc = T(0);
 
     // what the wave knows about a group before it streams it: wave-uniform, read with scalar loads (which the
-    // vector loads in flight do not wait for)
+    // vector loads in flight do not wait for) one group ahead, the segment's offsets included
     struct unit {
-        int D;          // 0: nothing to do (segment not eligible, or no rows)
+        int u;          // index among the wave's units; n_units and above: there is none
+        int D;
         int row0;
-        int k0a, len;   // aligned stream start; entries from there to the group's end (0: none)
-        const int32_t* tab;
+        int k0a, len;   // aligned stream start; entries from there to the group's end.  0: nothing to do
+                        // (behind the wave's last unit, segment not eligible; or a structure rewritten behind
+                        // the plan's back, which alone gives an eligible segment no entries)
+        int32_t off[ND];
     };
-    auto unit_of = [&](int u) {
+    // what unit_of reads: straight-line scalar loads, every address one of a unit the wave owns (the last
+    // one again behind the end); nothing here waits for them
+    struct unit_raw {
+        int u, row0, k0, k1, D;
+        int32_t off[ND];
+    };
+    auto read_unit = [&](int u) {
+        unit_raw r;
+        r.u = u;
+        const int64_t s = sb + (u < n_units ? u : n_units - 1);
+        const int32_t* tab = seg_tab + s * OFFS_TAB;
+        r.row0 = int(s * 64);
+        const int last = r.row0 + GR < n_rows ? r.row0 + GR : n_rows;
+        r.k0 = row_ptrs[r.row0];
+        r.k1 = row_ptrs[last];
+        r.D = tab[0];
+#pragma unroll
+        for (int d = 0; d < ND; ++d) r.off[d] = tab[1 + d];
+        return r;
+    };
+    auto unit_from = [&](const unit_raw& r) {
         unit q;
-        const int64_t s = sb + u / GPS;
-        q.row0 = int(s * 64) + (u % GPS) * GR;
-        q.tab = seg_tab + s * OFFS_TAB;
-        q.D = (u < n_units && q.row0 < n_rows) ? q.tab[0] : 0;
-        q.k0a = q.len = 0;
-        if (q.D > 0) {
-            const int last = q.row0 + GR < n_rows ? q.row0 + GR : n_rows;
-            const int k0 = row_ptrs[q.row0];
-            const int k1 = row_ptrs[last];
-            q.k0a = k0 & ~(E - 1);
-            q.len = k1 > k0 ? k1 - q.k0a : 0;
-            // (a structure rewritten behind the plan's back must not write outside the stage)
-            if (q.len > CAP + E - 1) q.len = CAP + E - 1;
-        }
+        q.u = r.u;
+        q.D = r.D;
+        q.row0 = r.row0;
+#pragma unroll
+        for (int d = 0; d < ND; ++d) q.off[d] = r.off[d];
+        q.k0a = r.k0 & ~(E - 1);
+        int len = r.k1 - q.k0a;
+        // (a structure rewritten behind the plan's back must not write outside the stage)
+        if (len > CAP + E - 1) len = CAP + E - 1;
+        q.len = (r.u < n_units && r.D > 0 && r.D <= ND && r.k1 > r.k0) ? len : 0;
         return q;
     };
-    // Every load is unconditional: a lane behind the group's end reads the 16 bytes that hold the group's last
-    // entry again (inside the array; one access for all such lanes), and what it reads is not stored.
+    auto unit_of = [&](int u) { return unit_from(read_unit(u)); };
+    // The value loads of a group with len > 0: unconditional, a lane behind the group's end reads the 16 bytes
+    // that hold the group's last entry again (one access for all such lanes), and what it reads is not read by
+    // any row.  INVARIANT: every address lies within [k0a, k0a + len) of a group that this wave owns.  There are
+    // two load sites, this one in front of the loop and one in it, and v[] has one register home.
     VT v[NL];
     auto load_vals = [&](const unit& q) {
         const int last_chunk = (q.len - 1) & ~(E - 1);
@@ -179,39 +230,59 @@ __global__ __launch_bounds__(64, 2) void csr_spmv_pipe3_kernel_offsets(
             v[t] = *reinterpret_cast<const VT*>(vals + (int64_t(q.k0a) + (k < last_chunk ? k : last_chunk)));
         }
     };
-    // one group; ND = 8 or 32 diagonal slots (compile-time indices: x and the values stay in registers)
-    auto group = [&](auto nd_c, const unit& cur, const unit& nxt, int u) {
-        constexpr int ND = decltype(nd_c)::value;
-        const int row = cur.row0 + lane;
-        const bool valid = lane < GR && row < n_rows;
+    // A group in two halves, so that the loop below can put the next group's value loads between them.
+    // What a lane keeps from one half to the other; diagonal slots are compile-time indices (x and the values
+    // stay in registers).
+    struct lane_state {
+        int row, rs_raw;
+        bool valid;
+        uint32_t mask_raw;
+        T sum, bdot;
+        T xv[ND];
+    };
+    // first half (cur.len > 0, its values in v[]): the group's own loads, the scalar loads of the next unit,
+    // the values to the stage.  Returns with v[] free.
+    auto head = [&](const unit& cur, lane_state& ls, unit_raw& nxt_raw) {
+        ls.row = cur.row0 + lane;
+        ls.valid = ls.row < n_rows;
         const int last = cur.row0 + GR < n_rows ? cur.row0 + GR : n_rows;
-        const int rs = row_ptrs[valid ? row : last] - cur.k0a;
-        uint32_t mask = row_mask[valid ? row : cur.row0];
-        if (!valid) mask = 0u;
-        T sum = T(0), bdot = T(0);
-        if (ADV && beta != T(0)) sum = c[valid ? row : cur.row0] * beta;
-        if (DOT) bdot = x[valid ? row : cur.row0];
+        // (first what the row phase needs first)
+        ls.rs_raw = row_ptrs[ls.valid ? ls.row : last];
+        ls.mask_raw = row_mask[ls.valid ? ls.row : cur.row0];
+        ls.sum = T(0);
+        ls.bdot = T(0);
+        if (ADV && beta != T(0)) ls.sum = c[ls.valid ? ls.row : cur.row0] * beta;
+        if (DOT) ls.bdot = x[ls.valid ? ls.row : cur.row0];
         // clamp(row + off_d): the column itself for a stored entry, anything in bounds for an absent slot
         // (the sum wraps for those at worst)
         const int ncm1 = n_cols - 1;
-        T xv[ND];
 #pragma unroll
         for (int d = 0; d < ND; ++d) {
-            const int idx = int(uint32_t(row) + uint32_t(cur.tab[1 + d]));
-            xv[d] = x[idx < 0 ? 0 : (idx > ncm1 ? ncm1 : idx)];
+            const int idx = int(uint32_t(ls.row) + uint32_t(cur.off[d]));
+            ls.xv[d] = x[idx < 0 ? 0 : (idx > ncm1 ? ncm1 : idx)];
         }
-        if (cur.len > 0) {
+        nxt_raw = read_unit(cur.u + 1);
 #pragma unroll
-            for (int t = 0; t < NL; ++t) {
-                const int k = (t * 64 + lane) * E;
-                if (k < cur.len) *reinterpret_cast<VT*>(&stage[k]) = v[t];
-            }
-        }
+        for (int t = 0; t < NL; ++t) *reinterpret_cast<VT*>(&stage[(t * 64 + lane) * E]) = v[t];
         wave_lds_sync();
-        // the registers are free: the next group's values are under way during this group's row phase
-        if (nxt.D > 0 && nxt.len > 0) load_vals(nxt);
-#pragma unroll
-        for (int d0 = 0; d0 < ND; d0 += 8) {
+        // (nothing that waits - for the scalar loads above, for x, the mask or the row pointer - moves up in
+        // front of the stage write or, in the loop, in front of the value loads that follow)
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // the wave's next group with values behind the unit read ahead, u >= n_units if there is none
+    auto next_group = [&](const unit_raw& nxt_raw) {
+        unit nxt = unit_from(nxt_raw);
+        while (nxt.u < n_units && nxt.len == 0) nxt = unit_of(nxt.u + 1);
+        return nxt;
+    };
+    // second half: the row phase and the store
+    auto rows = [&](const unit& cur, lane_state& ls) {
+        __builtin_amdgcn_sched_barrier(0);
+        const int rs = ls.rs_raw - cur.k0a;
+        const uint32_t mask = ls.valid ? ls.mask_raw : 0u;
+        T sum = ls.sum;
+        auto slots = [&](auto d0_c) {
+            constexpr int d0 = decltype(d0_c)::value;
             T val[8];
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
@@ -226,31 +297,51 @@ __global__ __launch_bounds__(64, 2) void csr_spmv_pipe3_kernel_offsets(
             }
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const T pr = ADV ? (alpha * val[i]) * xv[d0 + i] : val[i] * xv[d0 + i];
+                const T pr = ADV ? (alpha * val[i]) * ls.xv[d0 + i] : val[i] * ls.xv[d0 + i];
                 sum = ((mask >> (d0 + i)) & 1u) != 0 ? sum + pr : sum;
             }
+        };
+        slots(std::integral_constant<int, 0>{});
+        if constexpr (ND > 8) {
+            slots(std::integral_constant<int, 8>{});
+            slots(std::integral_constant<int, 16>{});
+            slots(std::integral_constant<int, 24>{});
         }
-        if (valid) c[row] = sum;
+        // (the sum of EVERY lane is complete here: without this the compiler moves the row phase under the
+        // `valid` branch below, whose other side reaches the next group with this group's x loads unwaited-for
+        // and puts write-after-load waits between the next group's x loads)
+        asm volatile("" : "+v"(sum));
+        if (ls.valid) c[ls.row] = sum;
         if constexpr (DOT) {
             // (the row-segment kernel's lane for this row is row % 64 too)
-            const T term = bdot * sum;
-            if (valid) dot_acc += term;
+            const T term = ls.bdot * sum;
+            if (ls.valid) dot_acc += term;
         }
         wave_lds_sync();
     };
 
-    unit cur = unit_of(0);
-    if (cur.D > 0 && cur.len > 0) load_vals(cur);
-    for (int u = 0; u < n_units; ++u) {
-        const unit nxt = unit_of(u + 1);
-        if (cur.D > 8) {
-            group(std::integral_constant<int, OFFS_MAX>{}, cur, nxt, u);
-        } else if (cur.D > 0) {
-            group(std::integral_constant<int, 8>{}, cur, nxt, u);
-        } else if (nxt.D > 0 && nxt.len > 0) {
-            load_vals(nxt);
+    if (n_units > 0) {
+        unit cur = unit_of(0);
+        while (cur.u < n_units && cur.len == 0) cur = unit_of(cur.u + 1);
+        if (cur.u < n_units) {
+            lane_state ls;
+            unit_raw nxt_raw;
+            load_vals(cur);
+            // Every group that has a successor: the successor's NL value loads are issued between the halves,
+            // ALWAYS (the loop is left in front of them otherwise), so they are under way during the row phase
+            // and no wait of the row phase asks for them.  The wave's last group runs behind the loop with
+            // nothing but its own loads in flight.
+            head(cur, ls, nxt_raw);
+            unit nxt = next_group(nxt_raw);
+            while (nxt.u < n_units) {
+                load_vals(nxt);
+                rows(cur, ls);
+                cur = nxt;
+                head(cur, ls, nxt_raw);
+                nxt = next_group(nxt_raw);
+            }
+            rows(cur, ls);
         }
-        cur = nxt;
     }
     if constexpr (DOT) {
         dot_acc = wave_sum(dot_acc);

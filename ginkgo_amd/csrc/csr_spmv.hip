@@ -376,6 +376,7 @@ std::mutex g_off_mtx;
 struct offsets_plan {
     int state = 0;                  // 0: seen once, 1: in use, 2: rejected (fewer than half of the segments eligible)
     int64_t n_seg = 0, eligible = 0;
+    int max_d = 0;                  // the largest D of a segment: picks the product kernel's diagonal slots
     int32_t* seg_tab = nullptr;     // device: OFFS_TAB int32 per segment
     uint32_t* row_mask = nullptr;   // device: one word per row
     uint32_t* skip = nullptr;       // device: bit per segment the row-segment kernel leaves out (eligible | long-flagged)
@@ -416,7 +417,8 @@ void offsets_release(std::vector<offsets_plan>& gone)
     g_off_graveyard.clear();
 }
 
-// the analysis: one pass over the column indices, the eligible count comes back with one stream synchronisation
+// the analysis: one pass over the column indices, the eligible count and the largest D come back with one
+// stream synchronisation
 int offsets_build(hipStream_t st, int64_t n_rows, const int32_t* row_ptrs, const int32_t* col_idxs,
                   const csr_long_info& lng, offsets_plan& pl)
 {
@@ -427,8 +429,8 @@ int offsets_build(hipStream_t st, int64_t n_rows, const int32_t* row_ptrs, const
     bool ok = arena_malloc(&tab, tab_bytes, GKOC_MEM_INDICES) == GKOC_OK &&
               arena_malloc(&mask, mask_bytes, GKOC_MEM_INDICES) == GKOC_OK &&
               arena_malloc(&skip, skip_bytes, GKOC_MEM_INDICES) == GKOC_OK &&
-              arena_malloc(&count_dev, 8, GKOC_MEM_VECTOR) == GKOC_OK;
-    unsigned long long count = 0;
+              arena_malloc(&count_dev, 16, GKOC_MEM_VECTOR) == GKOC_OK;
+    unsigned long long count[2] = {0, 0};
     if (ok) {
         csr_offsets_build_kernel<int32_t><<<dim3(unsigned(ceildiv(n_seg, int64_t(4)))), dim3(256), 0, st>>>(
             n_rows, row_ptrs, col_idxs, static_cast<int32_t*>(tab), static_cast<uint32_t*>(mask));
@@ -436,13 +438,14 @@ int offsets_build(hipStream_t st, int64_t n_rows, const int32_t* row_ptrs, const
             n_seg, static_cast<const int32_t*>(tab), lng.count > 0 ? lng.bits : nullptr,
             static_cast<uint32_t*>(skip), static_cast<unsigned long long*>(count_dev));
         ok = hipGetLastError() == hipSuccess &&
-             hipMemcpyAsync(&count, count_dev, 8, hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipMemcpyAsync(count, count_dev, 16, hipMemcpyDeviceToHost, st) == hipSuccess &&
              hipStreamSynchronize(st) == hipSuccess;
     }
     (void)hipGetLastError();
     if (count_dev) (void)arena_free(count_dev);
     pl.n_seg = n_seg;
-    pl.eligible = ok ? int64_t(count) : 0;
+    pl.eligible = ok ? int64_t(count[0]) : 0;
+    pl.max_d = ok ? int(count[1]) : 0;
     if (!ok || pl.eligible == 0 || pl.eligible * 100 < n_seg * offsets_min_share) {
         if (tab) (void)arena_free(tab);
         if (mask) (void)arena_free(mask);
@@ -518,16 +521,25 @@ offsets_plan* offsets_plan_for(hipStream_t st, int64_t n_rows, int64_t n_cols, c
     return &pl;
 }
 
-// the product of the plan's segments
+// the product of the plan's segments: 8 diagonal slots where no segment of the plan has more offsets, else 32
+// (one straight-line body per kernel, csr_offsets.hpp; a segment with fewer offsets is right in either)
+// The price: in a plan that has wide segments the narrow ones issue 24 dead x loads each - 5 % on a matrix with
+// one wide segment in eight, nothing with one in two (docs/KERNELS.md 36).
 template <typename T, bool ADV, bool DOT>
 void launch_offsets_kernel(hipStream_t st, const offsets_plan& pl, const segment_plan& p, int64_t n_rows,
                            int64_t n_cols, const T* alpha, const int32_t* row_ptrs, const T* vals, const T* b,
                            const T* beta, T* c, T* dot_partial)
 {
     const dim3 grid(static_cast<unsigned>(p.n_waves)), block(64);
-    csr_spmv_pipe3_kernel_offsets<T, ADV, DOT><<<grid, block, 0, st>>>(
-        int32_t(n_rows), int32_t(n_cols), p.n_seg, p.spw, row_ptrs, vals, b, c, alpha, beta, pl.seg_tab,
-        pl.row_mask, dot_partial);
+    if (pl.max_d > 8) {
+        csr_spmv_pipe3_kernel_offsets<T, ADV, DOT, OFFS_MAX><<<grid, block, 0, st>>>(
+            int32_t(n_rows), int32_t(n_cols), p.n_seg, p.spw, row_ptrs, vals, b, c, alpha, beta, pl.seg_tab,
+            pl.row_mask, dot_partial);
+    } else {
+        csr_spmv_pipe3_kernel_offsets<T, ADV, DOT, 8><<<grid, block, 0, st>>>(
+            int32_t(n_rows), int32_t(n_cols), p.n_seg, p.spw, row_ptrs, vals, b, c, alpha, beta, pl.seg_tab,
+            pl.row_mask, dot_partial);
+    }
 }
 
 // The hub rows' kernels run BEHIND the row-segment kernel on the caller's stream.  (Round 6 also ran them
@@ -875,8 +887,10 @@ int launch_csr_dot(gkoc_stream_t s, int64_t n, const I* row_ptrs,
     // one segment per wave below 4 M rows, as in the plain kernel (a rank's share of a
     // strong-scaling run is that small: 2.1 M rows at 8 ranks, 255 -> 24x us per CG iteration)
     using lay = pipe_layout<T>;
+    // (GKOC_TUNE_CSR_SEGS_PER_WAVE forces one or two here as in the plain product; the workspace has a slot per
+    // segment, so either fits, and both kernels below take their waves and dot_partial slots from the same p)
     segment_plan p;
-    GKOC_TRY(plan_segments(n, &p));
+    GKOC_TRY(plan_segments(n, &p, tune_value(GKOC_TUNE_CSR_SEGS_PER_WAVE)));
     T* partial = static_cast<T*>(work);
     T* scratch = partial + (fused_workspace_bytes(n, sizeof(T)) / sizeof(T) - fold_chunks);
     const dim3 grid(static_cast<unsigned>(p.n_waves)), block(64);

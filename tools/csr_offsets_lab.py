@@ -5,7 +5,12 @@
   * the cost of the analysis: the second product from entry to return and to completion;
   * the stencil with every other segment made ineligible (an unsorted row): plan + row-segment kernel in one
     product against the row-segment kernel alone - the "at least half of the segments" rule of csr_spmv.hip.
-usage: python tools/csr_offsets_lab.py [GRID]      prints one JSON object"""
+A variant of the kernel that is not in the tree (a step of a change kept apart to be measured, say) is a second
+library built from a copy of the sources: --lib PATH loads that one instead of ginkgo_amd/lib, --only-kernels
+skips the analysis and the half-eligible matrix.  Two libraries cannot share one process' buffers, so such runs are
+taken alternately, a process each, on the same matrix and vectors (same seeds).
+usage: python tools/csr_offsets_lab.py [GRID] [--lib PATH] [--only-kernels]      prints one JSON object"""
+import argparse
 import ctypes as C
 import json
 import os
@@ -18,6 +23,14 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ginkgo_amd as g                      # noqa: E402
 from ginkgo_amd import _lib                 # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("grid", nargs="?", type=int, default=256)
+ap.add_argument("--lib", default=None, help="libgko_cdna4.so to load instead of the tree's")
+ap.add_argument("--only-kernels", action="store_true", help="the four kernel timings and the bit check only")
+args = ap.parse_args()
+if args.lib:
+    _lib.LIB_PATH = os.path.abspath(args.lib)
 
 KEY = 18
 ex = g.Cdna4Executor.create(0)
@@ -56,9 +69,9 @@ def wall(step):
     return (t1 - t) * 1e3, (time.perf_counter() - t) * 1e3
 
 
-grid = int(sys.argv[1]) if len(sys.argv) > 1 else 256
+grid = args.grid
 n = grid ** 3
-out = {"grid": grid}
+out = {"grid": grid, "lib": _lib.LIB_PATH if args.lib else "tree"}
 a = g.stencil_csr(ex, 3, grid)
 x = g.Dense.from_numpy(ex, np.random.default_rng(1).uniform(-1, 1, n))
 y = g.Dense.create(ex, (n, 1))
@@ -73,8 +86,12 @@ out["row_segment_kernel_ms"] = timed(plain)
 out["row_segment_kernel_fused_dot_ms"] = timed(fused)
 old_bits = (y.values.clone().view(torch.int64), dot.values.clone().view(torch.int64))
 tune(0)
-out["first_product_ms(entry_to_return, to_completion)"] = wall(plain)
-out["second_product_with_analysis_ms(entry_to_return, to_completion)"] = wall(plain)
+if args.only_kernels:
+    plain()
+    plain()
+else:
+    out["first_product_ms(entry_to_return, to_completion)"] = wall(plain)
+    out["second_product_with_analysis_ms(entry_to_return, to_completion)"] = wall(plain)
 out["plan"] = info(a)
 out["offsets_kernel_ms"] = timed(plain)
 out["offsets_kernel_fused_dot_ms"] = timed(fused)
@@ -86,6 +103,9 @@ out["row_segment_kernel_fused_dot_again_ms"] = timed(fused)
 tune(0)
 out["offsets_kernel_again_ms"] = timed(plain)
 out["offsets_kernel_fused_dot_again_ms"] = timed(fused)
+if args.only_kernels:
+    print(json.dumps(out, indent=1))
+    sys.exit(0)
 
 # every other segment made ineligible: the first two entries of its first row swapped (an unsorted row)
 b = g.stencil_csr(ex, 3, grid)

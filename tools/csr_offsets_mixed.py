@@ -1,0 +1,57 @@
+"""The plain CSR product on a plan that MIXES narrow and wide segments (csrc/csr_offsets.hpp picks 8 or 32 diagonal
+slots per plan, from its largest D): 2^22 rows, one 64-row segment in SHARE has the 9 offsets 0 .. 8, the others the
+3 offsets 0 .. 2; every segment is eligible.  HIP events, 30 launches per figure, the row-segment kernel
+(GKOC_TUNE_CSR_OFFSETS = 2) and the offsets kernel, with the sum of y as a check.
+usage: python tools/csr_offsets_mixed.py [--share SHARE] [--lib PATH]      (--lib: as in tools/csr_offsets_lab.py)
+prints one JSON object"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import ginkgo_amd as g                      # noqa: E402
+from ginkgo_amd import _lib                 # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--lib", default=None)
+ap.add_argument("--share", type=int, default=2)
+args = ap.parse_args()
+if args.lib:
+    _lib.LIB_PATH = os.path.abspath(args.lib)
+import csr_offsets_cases as oc              # noqa: E402  (tests/: arena_csr, plan_info)
+
+ex = g.Cdna4Executor.create(0)
+n = 1 << 22
+seg = np.arange(n) // 64
+wide = (seg % args.share) == (args.share - 1)          # one segment in `share` has 9 offsets
+cnt = np.where(wide, 9, 3).astype(np.int64)
+rp = np.zeros(n + 1, np.int64)
+rp[1:] = np.cumsum(cnt)
+row_of = np.repeat(np.arange(n), cnt)
+ci = (row_of + (np.arange(rp[-1]) - rp[row_of])).astype(np.int32)
+v = np.random.default_rng(0).uniform(0.5, 1.5, len(ci))
+a = oc.arena_csr(ex, (n, n + 16), rp.astype(np.int32), ci, v)
+x = g.Dense.from_numpy(ex, np.random.default_rng(1).uniform(-1, 1, n + 16))
+y = g.Dense.create(ex, (n, 1))
+out = {"lib": "--lib" if args.lib else "tree", "share_of_wide_segments": "1/%d" % args.share, "nnz": int(rp[-1])}
+for k, name in ((2, "row_segment_kernel_ms"), (1, "offsets_kernel_ms")):
+    _lib.call("gkoc_tune_set", oc.C.c_int(18), oc.C.c_int64(k))
+    for _ in range(5):
+        a.apply(x, y)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(30):
+        a.apply(x, y)
+    e1.record()
+    torch.cuda.synchronize()
+    out[name] = round(e0.elapsed_time(e1) / 30, 5)
+    out[name + "_sum"] = float(y.values.double().sum().item())
+out["plan"] = oc.plan_info(a)
+print(json.dumps(out))
