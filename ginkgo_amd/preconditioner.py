@@ -21,8 +21,9 @@ triangular.py: z = L^-1 r, or z = U^-1 L^-1 r for the symmetric form (SSOR).
 
 Ilu / Ic - mirror of include/ginkgo/core/preconditioner/{ilu,ic}.hpp:
 `Ilu.build().with_reverse_apply(False).on(exec).generate(A)` and `Ic.build().on(exec).generate(A)` apply
-the factors of factorization.py (the exact ILU(0) / IC(0)) with the same triangular solvers; A is a
-system matrix or an already generated factorization object.  `with_l_solver(factory)` / `with_u_solver(factory)`
+the factors of factorization.py (the exact ILU(0) / IC(0), or with `with_factorization(factory)` those of the
+fixed-point sweeps ParIlu / ParIc) with the same triangular solvers; A is a system matrix or an already
+generated factorization object.  `with_l_solver(factory)` / `with_u_solver(factory)`
 (Ic: `with_l_solver` only) replace the level-scheduled solvers by anything with `.on(exec).generate(csr)`,
 e.g. `LowerIsai.build().with_sparsity_power(2)` of isai.py: one SpMV per factor instead of a launch per level.
 """
@@ -446,11 +447,19 @@ class _FactorizedFactory:
         self.reverse_apply = False
         self.skip_sorting = False
         self.l_solver = self.u_solver = None
+        self.factorization = None
         self.exec = None
 
     def with_skip_sorting(self, v):
-        """passed on to the factorization when generate gets a system matrix"""
+        """passed on to the factorization when generate gets a system matrix and no factorization factory
+        was given"""
         self.skip_sorting = bool(v)
+        return self
+
+    def with_factorization(self, factory):
+        """the factory of the factorization of a system matrix, e.g.
+        factorization.ParIlu.build().with_iterations(3); default: the exact factorization.Ilu / Ic"""
+        self.factorization = factory
         return self
 
     def with_l_solver(self, factory):
@@ -480,13 +489,21 @@ class _IluFactory(_FactorizedFactory):
 class _Factorized(LinOp):
     """two triangular solves on the factors of a factorization object; the vector between them is
     allocated at generate time, so a captured iteration allocates nothing"""
-    _FACTORIZATION = None
+    _FACTORIZATION = None       # what factorizes a system matrix by default
+    _FACTORIZATIONS = ()        # the generated objects that are taken as they are
 
     def __init__(self, factory, a):
-        if not isinstance(a, self._FACTORIZATION):
-            # Ginkgo's default here is ParIlu / ParIc; this backend has the exact ILU(0) / IC(0)
-            a = (self._FACTORIZATION.build().with_skip_sorting(factory.skip_sorting)
-                 .on(factory.exec or a.exec).generate(a))
+        if not isinstance(a, self._FACTORIZATIONS):
+            # Ginkgo's default here is ParIlu / ParIc; this backend's is the exact ILU(0) / IC(0), and the
+            # iterative one comes in through with_factorization
+            if factory.factorization is not None:
+                a = factory.factorization.on(factory.exec or a.exec).generate(a)
+            else:
+                a = (self._FACTORIZATION.build().with_skip_sorting(factory.skip_sorting)
+                     .on(factory.exec or a.exec).generate(a))
+            if not isinstance(a, self._FACTORIZATIONS):
+                raise NotSupported(f"{type(self).__name__}: with_factorization gave a {type(a).__name__}, "
+                                   "which is no factorization this preconditioner can apply")
         super().__init__(factory.exec or a.exec, a.size)
         self.factorization = a
         self.dtype = a.dtype
@@ -513,11 +530,13 @@ class _Factorized(LinOp):
 
 class Ilu(_Factorized):
     """preconditioner::Ilu: z = U^-1 L^-1 r (with_reverse_apply(True): z = L^-1 U^-1 r) with the
-    level-scheduled triangular solvers.  `generate` takes a factorization.Ilu object or a system matrix.
-    A system matrix is factorized here with the exact ILU(0) of factorization.Ilu - Ginkgo's default at
-    this place is the iterative ParIlu, which this backend does not have.  `with_l_solver` / `with_u_solver`
-    take a factory for the solver of either factor (e.g. LowerIsai / UpperIsai); default LowerTrs / UpperTrs."""
+    level-scheduled triangular solvers.  `generate` takes a factorization.Ilu / ParIlu object or a system
+    matrix.  A system matrix is factorized here with the exact ILU(0) of factorization.Ilu - Ginkgo's default
+    at this place is the iterative ParIlu, which `with_factorization(factorization.ParIlu.build()...)` selects:
+    no level schedule is built for the factorization then.  `with_l_solver` / `with_u_solver` take a factory
+    for the solver of either factor (e.g. LowerIsai / UpperIsai); default LowerTrs / UpperTrs."""
     _FACTORIZATION = _factorization.Ilu
+    _FACTORIZATIONS = (_factorization.Ilu, _factorization.ParIlu)
 
     @staticmethod
     def build():
@@ -534,12 +553,13 @@ class Ilu(_Factorized):
 
 class Ic(_Factorized):
     """preconditioner::Ic: z = L^-T L^-1 r with the level-scheduled triangular solvers.  `generate` takes
-    a factorization.Ic object or a system matrix.  A system matrix is factorized here with the exact IC(0)
-    of factorization.Ic - Ginkgo's default at this place is the iterative ParIc, which this backend does
-    not have.  `with_l_solver` takes a factory for the solver S of L (e.g. LowerIsai); the solver of L^T is then
+    a factorization.Ic / ParIc object or a system matrix.  A system matrix is factorized here with the exact
+    IC(0) of factorization.Ic - Ginkgo's default at this place is the iterative ParIc, which
+    `with_factorization(factorization.ParIc.build()...)` selects.  `with_l_solver` takes a factory for the solver S of L (e.g. LowerIsai); the solver of L^T is then
     S.transpose(), as in Ginkgo, so that z = S^T S r stays symmetric - a solver without transpose() (LowerTrs)
     is refused there."""
     _FACTORIZATION = _factorization.Ic
+    _FACTORIZATIONS = (_factorization.Ic, _factorization.ParIc)
 
     @staticmethod
     def build():
