@@ -18,11 +18,16 @@
 // (a resident group of 64 rows; 32-row groups with an 8 KB stage were measured 2.8 x slower, docs/KERNELS.md 36):
 //   * the group's values are streamed exactly like there - 16-byte loads per lane, contiguous per wave, all
 //     of a group in flight at once - and parked in LDS AS VALUES (the whole group is resident before its row
-//     phase: at most 64 x 32 entries, so no lane needs resume state);
+//     phase: at most 64 x ND entries, ND the kernel's number of diagonal slots, so no lane needs resume state);
+//     the stream, the stage and the x loads are sized by ND: NL = ND / E + 1 loads of E = 16 / sizeof(T) entries
+//     per lane (double 5 / 9 / 15 / 17 for ND = 8 / 16 / 28 / 32, float 3 / 5 / 8 / 9), NL x 64 x E entries of LDS
+//     (double 5 / 9 / 15 / 17 KiB) - the 27-point stencil runs with 15 value and 28 x loads per lane, not 17 and 32;
 //   * the loads of the NEXT group's values are issued as soon as the registers are free, i.e. before the
 //     row phase of this one, and all x loads of this group before them (vmcnt is in-order: an x load issued
 //     behind the value loads would be waited for behind them);
-//   * row phase, lane = row: for d = 0 .. ND-1 (compile-time index; ND = 8 or 32 slots per kernel) the load
+//   * row phase, lane = row: a row's entries start at the stream's lead plus the wave's exclusive prefix sum of
+//     popc(mask) (one mask bit per stored entry: row_ptrs[row] is not read; the two ends of the group come from
+//     scalar loads); for d = 0 .. ND-1 (compile-time index; ND = 8, 16, 28 or 32 slots per kernel) the load
 //     of x[clamp(row + off_d)] is unconditional and in bounds, the value of an absent slot is never used:
 //     sum += v * x only where bit d of the mask is set, separate multiply and add, ascending d = storage
 //     order - the operations of the sequential reference in its order, hence its bits; an absent slot
@@ -124,6 +129,21 @@ __global__ __launch_bounds__(1024) void csr_offsets_finish_kernel(int64_t n_seg,
     }
 }
 
+// Exclusive prefix sum of v over the 64 lanes of a wave in six DPP steps: four shifts within the rows of 16
+// lanes, then lane 15 of a row into the next row and lane 31 into the upper half.  A lane without a source keeps
+// the 0 of `old`.  No LDS crossbar (ds_bpermute) and no index registers.
+__device__ __forceinline__ int wave_exclusive_sum(int v)
+{
+    int s = v;
+    s += __builtin_amdgcn_update_dpp(0, s, 0x111, 0xf, 0xf, false);   // row_shr:1
+    s += __builtin_amdgcn_update_dpp(0, s, 0x112, 0xf, 0xf, false);   // row_shr:2
+    s += __builtin_amdgcn_update_dpp(0, s, 0x114, 0xf, 0xf, false);   // row_shr:4
+    s += __builtin_amdgcn_update_dpp(0, s, 0x118, 0xf, 0xf, false);   // row_shr:8
+    s += __builtin_amdgcn_update_dpp(0, s, 0x142, 0xa, 0xf, false);   // row_bcast:15, rows 1 and 3
+    s += __builtin_amdgcn_update_dpp(0, s, 0x143, 0xc, 0xf, false);   // row_bcast:31, rows 2 and 3
+    return s - v;
+}
+
 // T = double / float, 32-bit indices.  ADV: c = alpha A x + beta c.  DOT: also this wave's part of <x, c>
 // (gkoc_x_csr_spmv_dot_*; the same lane-to-row assignment, per-wave butterfly and slot as the row-segment
 // kernel, so the folded value has the same bits).
@@ -131,20 +151,27 @@ __global__ __launch_bounds__(1024) void csr_offsets_finish_kernel(int64_t n_seg,
 // The schedule of a group, which the wait counts of the compiled kernel depend on (vmcnt retires in order; a
 // load issued under a condition makes the compiler count at the join as if it had not been issued, and every
 // later wait is then too strict by that many loads):
-//   1. the group's row-pointer, mask and ND x loads, from offsets that are already in scalar registers - ND,
-//      the number of diagonal slots, is the KERNEL's (8 or 32, picked by the launcher from the plan's largest
-//      D), not the segment's: a count that depended on the segment would be a condition again.  A segment with
-//      fewer offsets has offset 0 and mask bit 0 in the slots it lacks: in-bounds loads that no sum reads;
+//   1. the group's mask and ND x loads, from offsets that are already in scalar registers - ND, the number of
+//      diagonal slots, is the KERNEL's (8, 16, 28 or 32: the smallest that holds the plan's largest D, picked by
+//      the launcher), not the segment's: a count that depended on the segment would be a condition again.  A
+//      segment with fewer offsets has offset 0 and mask bit 0 in the slots it lacks: in-bounds loads that no sum
+//      reads;
 //   2. the scalar loads of the NEXT unit (D, row pointers, offsets): under way while the values arrive;
 //   3. the group's values, in flight since the previous group's step 4, go to the stage: all NL chunks of
 //      every lane, no branch (entries at or behind `len` are never read: pos < len for every stored slot);
 //   4. the NL value loads of the next group, ALWAYS issued, from ONE load site in the loop (and one in front
 //      of it), so v[] has one register home and the compiler a static count of loads behind every x load;
-//   5. the row phase: the wait in front of its last x leaves the NL loads of step 4 in flight.
+//   5. the row phase: the prefix sum of the row lengths waits for the mask alone (vmcnt(NL + ND): the first load
+//      of the group), the wait in front of the last x leaves the NL loads of step 4 in flight.
+// Compiled for double, ND = 28: stage write vmcnt(43) .. (29) = the group's own 29 loads behind the values, row
+// phase vmcnt(43) .. vmcnt(15), no vmcnt wait between the top of a group and its last x load; 153 VGPRs (fused
+// dot 157), 15 KiB of LDS: 3 waves per SIMD by registers, 10 waves per CU by LDS (docs/KERNELS.md 36).
 // "Always" because the loop runs over the groups that HAVE a successor; the wave's last group does 1 - 3 and 5
 // behind it.  (Issuing step 4 there too, as re-reads of the group's last 16 bytes, was measured: with two
 // segments per wave every second prefetch is then a dummy, and the kernel was 3.7 % slower than with the
 // conditional prefetch it replaced, docs/KERNELS.md 36.)
+// __launch_bounds__(64, 3) on the 28-slot kernels changes neither their registers nor, measurably, their time
+// (docs/KERNELS.md 36): all instantiations keep (64, 2).
 template <typename T, bool ADV, bool DOT, int ND>
 __global__ __launch_bounds__(64, 2) void csr_spmv_pipe3_kernel_offsets(
     int32_t n_rows, int32_t n_cols, int64_t n_segments, int spw, const int32_t* __restrict__ row_ptrs,
@@ -154,8 +181,11 @@ __global__ __launch_bounds__(64, 2) void csr_spmv_pipe3_kernel_offsets(
 {
     constexpr int GR = 64;                             // rows of a resident group = the segment
     constexpr int E = 16 / sizeof(T);                  // entries per lane and load
-    constexpr int CAP = GR * OFFS_MAX;                 // entries of a group at most
+    constexpr int CAP = GR * ND;                       // entries of a group at most: D <= ND offsets a row
     constexpr int NL = CAP / (64 * E) + 1;             // loads per lane: the stream starts up to E - 1 entries early
+    static_assert(ND >= 8 && ND <= OFFS_MAX && ND % 4 == 0, "bodies of eight slots and a last one of ND - 24");
+    // (the stage takes a whole stream: `len` is clamped to CAP + E - 1 below)
+    static_assert(NL * 64 * E >= CAP + E - 1, "stage too small");
     // (a native vector type: an array of structs of this size is not kept in registers by the compiler)
     typedef T VT __attribute__((ext_vector_type(E)));
     __shared__ __attribute__((aligned(16))) T stage[NL * 64 * E];
@@ -177,6 +207,7 @@ __global__ __launch_bounds__(64, 2) void csr_spmv_pipe3_kernel_offsets(
         int u;          // index among the wave's units; n_units and above: there is none
         int D;
         int row0;
+        int lead;       // entries of the previous group in front of this one's first: k0 - k0a < E
         int k0a, len;   // aligned stream start; entries from there to the group's end.  0: nothing to do
                         // (behind the wave's last unit, segment not eligible; or a structure rewritten behind
                         // the plan's back, which alone gives an eligible segment no entries)
@@ -210,6 +241,7 @@ __global__ __launch_bounds__(64, 2) void csr_spmv_pipe3_kernel_offsets(
 #pragma unroll
         for (int d = 0; d < ND; ++d) q.off[d] = r.off[d];
         q.k0a = r.k0 & ~(E - 1);
+        q.lead = r.k0 - q.k0a;
         int len = r.k1 - q.k0a;
         // (a structure rewritten behind the plan's back must not write outside the stage)
         if (len > CAP + E - 1) len = CAP + E - 1;
@@ -234,7 +266,7 @@ __global__ __launch_bounds__(64, 2) void csr_spmv_pipe3_kernel_offsets(
     // What a lane keeps from one half to the other; diagonal slots are compile-time indices (x and the values
     // stay in registers).
     struct lane_state {
-        int row, rs_raw;
+        int row;
         bool valid;
         uint32_t mask_raw;
         T sum, bdot;
@@ -245,9 +277,7 @@ __global__ __launch_bounds__(64, 2) void csr_spmv_pipe3_kernel_offsets(
     auto head = [&](const unit& cur, lane_state& ls, unit_raw& nxt_raw) {
         ls.row = cur.row0 + lane;
         ls.valid = ls.row < n_rows;
-        const int last = cur.row0 + GR < n_rows ? cur.row0 + GR : n_rows;
         // (first what the row phase needs first)
-        ls.rs_raw = row_ptrs[ls.valid ? ls.row : last];
         ls.mask_raw = row_mask[ls.valid ? ls.row : cur.row0];
         ls.sum = T(0);
         ls.bdot = T(0);
@@ -278,35 +308,39 @@ __global__ __launch_bounds__(64, 2) void csr_spmv_pipe3_kernel_offsets(
     // second half: the row phase and the store
     auto rows = [&](const unit& cur, lane_state& ls) {
         __builtin_amdgcn_sched_barrier(0);
-        const int rs = ls.rs_raw - cur.k0a;
         const uint32_t mask = ls.valid ? ls.mask_raw : 0u;
+        // The row's start in the stage.  The build kernel sets one mask bit per stored entry, so the rows in
+        // front of this one hold the wave's exclusive prefix sum of popc(mask) entries, behind the `lead` entries
+        // of the previous group: row_ptrs[row] is not loaded.  With popc(mask) <= D <= ND (unit_from) every
+        // index below is at most lead + 64 ND - 1 < CAP + E - 1: inside the stage whatever row_ptrs holds, also
+        // for a structure rewritten behind the plan's back.  Waits for the mask load only.
+        const int rs = cur.lead + wave_exclusive_sum(__popc(mask));
         T sum = ls.sum;
         auto slots = [&](auto d0_c) {
             constexpr int d0 = decltype(d0_c)::value;
-            T val[8];
+            constexpr int NB = ND - d0 < 8 ? ND - d0 : 8;      // (the last body of 28 slots has four)
+            T val[NB];
 #pragma unroll
-            for (int i = 0; i < 8; ++i) {
+            for (int i = 0; i < NB; ++i) {
                 // entries of the row in front of slot d = stored slots below d
                 const int pos = rs + __popc(mask & ((1u << (d0 + i)) - 1u));
                 val[i] = stage[pos];
             }
 #pragma unroll
-            for (int i = 0; i < 8; ++i) {
+            for (int i = 0; i < NB; ++i) {
                 // (keeps the eight LDS reads together in front of the arithmetic)
                 asm volatile("" : "+v"(val[i]));
             }
 #pragma unroll
-            for (int i = 0; i < 8; ++i) {
+            for (int i = 0; i < NB; ++i) {
                 const T pr = ADV ? (alpha * val[i]) * ls.xv[d0 + i] : val[i] * ls.xv[d0 + i];
                 sum = ((mask >> (d0 + i)) & 1u) != 0 ? sum + pr : sum;
             }
         };
         slots(std::integral_constant<int, 0>{});
-        if constexpr (ND > 8) {
-            slots(std::integral_constant<int, 8>{});
-            slots(std::integral_constant<int, 16>{});
-            slots(std::integral_constant<int, 24>{});
-        }
+        if constexpr (ND > 8) slots(std::integral_constant<int, 8>{});
+        if constexpr (ND > 16) slots(std::integral_constant<int, 16>{});
+        if constexpr (ND > 24) slots(std::integral_constant<int, 24>{});
         // (the sum of EVERY lane is complete here: without this the compiler moves the row phase under the
         // `valid` branch below, whose other side reaches the next group with this group's x loads unwaited-for
         // and puts write-after-load waits between the next group's x loads)

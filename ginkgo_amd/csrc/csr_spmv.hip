@@ -521,24 +521,40 @@ offsets_plan* offsets_plan_for(hipStream_t st, int64_t n_rows, int64_t n_cols, c
     return &pl;
 }
 
-// the product of the plan's segments: 8 diagonal slots where no segment of the plan has more offsets, else 32
-// (one straight-line body per kernel, csr_offsets.hpp; a segment with fewer offsets is right in either)
-// The price: in a plan that has wide segments the narrow ones issue 24 dead x loads each - 5 % on a matrix with
-// one wide segment in eight, nothing with one in two (docs/KERNELS.md 36).
+// the product of the plan's segments: the kernel with the fewest diagonal slots (8, 16, 28 or 32) that holds the
+// plan's largest D - its value stream, its stage and its x loads are sized by the slot count (one straight-line
+// body per kernel, csr_offsets.hpp; a segment with fewer offsets is right in any wider kernel).  28 is the 27-point
+// stencil's.
+// The price: in a plan that has wide segments the narrow ones issue dead x loads - 5 % on a matrix with one
+// segment of 9 offsets in eight of 3 under the 32-slot kernel, nothing with one in two (docs/KERNELS.md 36).
+template <typename T, bool ADV, bool DOT, int ND>
+void launch_offsets_kernel_nd(hipStream_t st, const offsets_plan& pl, const segment_plan& p, int64_t n_rows,
+                              int64_t n_cols, const T* alpha, const int32_t* row_ptrs, const T* vals, const T* b,
+                              const T* beta, T* c, T* dot_partial)
+{
+    const dim3 grid(static_cast<unsigned>(p.n_waves)), block(64);
+    csr_spmv_pipe3_kernel_offsets<T, ADV, DOT, ND><<<grid, block, 0, st>>>(
+        int32_t(n_rows), int32_t(n_cols), p.n_seg, p.spw, row_ptrs, vals, b, c, alpha, beta, pl.seg_tab,
+        pl.row_mask, dot_partial);
+}
+
 template <typename T, bool ADV, bool DOT>
 void launch_offsets_kernel(hipStream_t st, const offsets_plan& pl, const segment_plan& p, int64_t n_rows,
                            int64_t n_cols, const T* alpha, const int32_t* row_ptrs, const T* vals, const T* b,
                            const T* beta, T* c, T* dot_partial)
 {
-    const dim3 grid(static_cast<unsigned>(p.n_waves)), block(64);
-    if (pl.max_d > 8) {
-        csr_spmv_pipe3_kernel_offsets<T, ADV, DOT, OFFS_MAX><<<grid, block, 0, st>>>(
-            int32_t(n_rows), int32_t(n_cols), p.n_seg, p.spw, row_ptrs, vals, b, c, alpha, beta, pl.seg_tab,
-            pl.row_mask, dot_partial);
+    auto go = [&](auto nd) {
+        launch_offsets_kernel_nd<T, ADV, DOT, decltype(nd)::value>(st, pl, p, n_rows, n_cols, alpha, row_ptrs, vals,
+                                                                   b, beta, c, dot_partial);
+    };
+    if (pl.max_d <= 8) {
+        go(std::integral_constant<int, 8>{});
+    } else if (pl.max_d <= 16) {
+        go(std::integral_constant<int, 16>{});
+    } else if (pl.max_d <= 28) {
+        go(std::integral_constant<int, 28>{});
     } else {
-        csr_spmv_pipe3_kernel_offsets<T, ADV, DOT, 8><<<grid, block, 0, st>>>(
-            int32_t(n_rows), int32_t(n_cols), p.n_seg, p.spw, row_ptrs, vals, b, c, alpha, beta, pl.seg_tab,
-            pl.row_mask, dot_partial);
+        go(std::integral_constant<int, OFFS_MAX>{});
     }
 }
 

@@ -1,8 +1,9 @@
-"""The plain CSR product on a plan that MIXES narrow and wide segments (csrc/csr_offsets.hpp picks 8 or 32 diagonal
-slots per plan, from its largest D): 2^22 rows, one 64-row segment in SHARE has the 9 offsets 0 .. 8, the others the
+"""The plain CSR product on a plan that MIXES narrow and wide segments (csrc/csr_offsets.hpp picks 8, 16, 28 or 32
+diagonal slots per plan, from its largest D): 2^22 rows, one 64-row segment in SHARE has the 9 offsets 0 .. 8, the others the
 3 offsets 0 .. 2; every segment is eligible.  HIP events, 30 launches per figure, the row-segment kernel
 (GKOC_TUNE_CSR_OFFSETS = 2) and the offsets kernel, with the sum of y as a check.
-usage: python tools/csr_offsets_mixed.py [--share SHARE] [--lib PATH]      (--lib: as in tools/csr_offsets_lab.py)
+usage: python tools/csr_offsets_mixed.py [--share SHARE] [--lib PATH]      (--lib: as in tools/csr_offsets_lab.py;
+a SHARE above the 65536 segments leaves no wide segment: the pure 3-offset plan)
 prints one JSON object"""
 import argparse
 import json
