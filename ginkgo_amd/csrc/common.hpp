@@ -106,7 +106,7 @@ int csr_spmv_complex(gkoc_stream_t s, int64_t n_rows, int64_t nrhs, const I* row
 int gate_fence_policy();
 void gate_fence_policy_set(int policy);
 // tuning switches (runtime.hip; keys = GKOC_TUNE_* of gko_cdna4.h)
-constexpr int tune_num_keys = 19;
+constexpr int tune_num_keys = 20;
 int64_t tune_value(int key);
 
 #ifdef __HIPCC__

@@ -13,6 +13,16 @@
 // keyed by the two arrays, and drops it when either is freed or written.  The VALUES are read live by every
 // product.  Segments that are not eligible (unsorted rows, duplicate columns, more than 32 offsets) stay
 // with the row-segment kernel.
+// The plan is kept BY CLASS: two segments whose 33 table words (D, 32 zero-padded offsets) and 64 mask words (0
+// for a row at or behind n_rows) are equal bit for bit share one entry of cls_tab / cls_mask, and a segment
+// keeps its class id alone (seg_class, 4 bytes).  In a matrix from a structured mesh nearly every segment
+// repeats another (the 27-point stencil 256^3: 27 classes among 262 144 segments), so a product streams 4 bytes a
+// segment where the per-segment table and the per-row masks were 388, and the class tables stay in cache.  A
+// structure without repetition has one class per segment: the same bytes plus the id.  The classes are found
+// behind the build kernel (csr_offsets_hash_kernel .. csr_offsets_compact_kernel below): a 64-bit hash per
+// segment, a stable sort of (hash, segment), the first segment of a run of equal hashes is its leader, and a
+// member joins the leader's class only after comparing all 97 words with it - a hash collision costs a class of
+// its own, never a wrong table.
 //
 // csr_spmv_pipe3_kernel_offsets: a wave owns the segments the row-segment kernel's wave would own.  Per segment
 // (a resident group of 64 rows; 32-row groups with an 8 KB stage were measured 2.8 x slower, docs/KERNELS.md 36):
@@ -129,6 +139,128 @@ __global__ __launch_bounds__(1024) void csr_offsets_finish_kernel(int64_t n_seg,
     }
 }
 
+// ---- classes of equal segments ------------------------------------------------------------------------------
+// The class key of a segment: word w < 64 is the mask of row 64 seg + w (0 at or behind n_rows), word 64 + j the
+// j-th table word.  Lane l holds words l and (l < OFFS_TAB) 64 + l.
+struct class_words {
+    uint32_t mask, tab;
+};
+__device__ __forceinline__ class_words class_words_of(int64_t n_rows, int64_t seg, int lane,
+                                                      const int32_t* __restrict__ seg_tab,
+                                                      const uint32_t* __restrict__ row_mask)
+{
+    const int64_t row = seg * 64 + lane;
+    class_words w;
+    w.mask = row < n_rows ? row_mask[row] : 0u;
+    w.tab = lane < OFFS_TAB ? uint32_t(seg_tab[seg * OFFS_TAB + lane]) : 0u;
+    return w;
+}
+
+__device__ __forceinline__ unsigned long long class_mix(unsigned long long z)      // (the splitmix64 finalizer)
+{
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+
+// One wave per segment: hash[seg] = the sum over the 97 key words of mix(position, word), cut to the bits of
+// `keep` (all of them; fewer only to provoke collisions: GKOC_TUNE_CSR_OFFSETS_HASH_BITS), ids[seg] = seg.
+__global__ __launch_bounds__(256) void csr_offsets_hash_kernel(int64_t n_rows, int64_t n_seg,
+                                                               const int32_t* __restrict__ seg_tab,
+                                                               const uint32_t* __restrict__ row_mask,
+                                                               unsigned long long keep,
+                                                               unsigned long long* __restrict__ hash,
+                                                               uint32_t* __restrict__ ids)
+{
+    const int64_t seg = int64_t(blockIdx.x) * 4 + threadIdx.x / 64;
+    const int lane = threadIdx.x % 64;
+    if (seg >= n_seg) return;
+    const class_words w = class_words_of(n_rows, seg, lane, seg_tab, row_mask);
+    unsigned long long h = class_mix((static_cast<unsigned long long>(lane) << 32) | w.mask);
+    if (lane < OFFS_TAB) h += class_mix((static_cast<unsigned long long>(64 + lane) << 32) | w.tab);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) h += __shfl_xor(h, o, 64);
+    if (lane == 0) {
+        hash[seg] = h & keep;
+        ids[seg] = uint32_t(seg);
+    }
+}
+
+// One wave per position i of the sorted (hash, segment) pairs.  The leader of i is the first position that holds
+// the same hash (a binary search; the sort is stable, so the leader is the run's lowest segment).  is_new[i] = 1
+// where the segment opens a class: it is the leader, or one of its 97 words differs from the leader's.
+__global__ __launch_bounds__(256) void csr_offsets_leader_kernel(int64_t n_rows, int64_t n_seg,
+                                                                 const int32_t* __restrict__ seg_tab,
+                                                                 const uint32_t* __restrict__ row_mask,
+                                                                 const unsigned long long* __restrict__ hash_sorted,
+                                                                 const uint32_t* __restrict__ ids_sorted,
+                                                                 uint32_t* __restrict__ leader,
+                                                                 uint32_t* __restrict__ is_new)
+{
+    const int64_t i = int64_t(blockIdx.x) * 4 + threadIdx.x / 64;
+    const int lane = threadIdx.x % 64;
+    if (i >= n_seg) return;
+    const unsigned long long h = hash_sorted[i];
+    int64_t lo = 0, hi = i;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) / 2;
+        if (hash_sorted[mid] < h) {
+            lo = mid + 1;
+        } else {
+            hi = mid;
+        }
+    }
+    bool same = true;
+    if (lo != i) {
+        const class_words a = class_words_of(n_rows, int64_t(ids_sorted[i]), lane, seg_tab, row_mask);
+        const class_words b = class_words_of(n_rows, int64_t(ids_sorted[lo]), lane, seg_tab, row_mask);
+        same = __all(a.mask == b.mask && a.tab == b.tab) != 0;
+    }
+    if (lane == 0) {
+        leader[i] = uint32_t(lo);
+        is_new[i] = (lo == i || !same) ? 1u : 0u;
+    }
+}
+
+// count[2] = the number of classes, from the exclusive scan of is_new over the sorted order (class_at); count[3] =
+// the number of stored entries (the launcher sizes the product by it)
+__global__ void csr_offsets_class_count_kernel(int64_t n_seg, const uint32_t* __restrict__ is_new,
+                                               const uint32_t* __restrict__ class_at, int64_t n_rows,
+                                               const int32_t* __restrict__ row_ptrs,
+                                               unsigned long long* __restrict__ count)
+{
+    count[2] = static_cast<unsigned long long>(class_at[n_seg - 1]) + is_new[n_seg - 1];
+    const int32_t nnz = row_ptrs[n_rows];
+    count[3] = nnz > 0 ? static_cast<unsigned long long>(nnz) : 0ull;
+}
+
+// One wave per sorted position: the segment's class id - its own where it opens a class, its leader's otherwise -
+// and, where it opens one, the class' table and masks.
+__global__ __launch_bounds__(256) void csr_offsets_compact_kernel(int64_t n_rows, int64_t n_seg,
+                                                                  const int32_t* __restrict__ seg_tab,
+                                                                  const uint32_t* __restrict__ row_mask,
+                                                                  const uint32_t* __restrict__ ids_sorted,
+                                                                  const uint32_t* __restrict__ leader,
+                                                                  const uint32_t* __restrict__ is_new,
+                                                                  const uint32_t* __restrict__ class_at,
+                                                                  int32_t* __restrict__ seg_class,
+                                                                  int32_t* __restrict__ cls_tab,
+                                                                  uint32_t* __restrict__ cls_mask)
+{
+    const int64_t i = int64_t(blockIdx.x) * 4 + threadIdx.x / 64;
+    const int lane = threadIdx.x % 64;
+    if (i >= n_seg) return;
+    const int64_t seg = int64_t(ids_sorted[i]);
+    const bool opens = is_new[i] != 0;
+    const int64_t cid = int64_t(opens ? class_at[i] : class_at[leader[i]]);
+    if (lane == 0) seg_class[seg] = int32_t(cid);
+    if (opens) {
+        const class_words w = class_words_of(n_rows, seg, lane, seg_tab, row_mask);
+        cls_mask[cid * 64 + lane] = w.mask;
+        if (lane < OFFS_TAB) cls_tab[cid * OFFS_TAB + lane] = int32_t(w.tab);
+    }
+}
+
 // Exclusive prefix sum of v over the 64 lanes of a wave in six DPP steps: four shifts within the rows of 16
 // lanes, then lane 15 of a row into the next row and lane 31 into the upper half.  A lane without a source keeps
 // the 0 of `old`.  No LDS crossbar (ds_bpermute) and no index registers.
@@ -156,7 +288,9 @@ __device__ __forceinline__ int wave_exclusive_sum(int v)
 //      the launcher), not the segment's: a count that depended on the segment would be a condition again.  A
 //      segment with fewer offsets has offset 0 and mask bit 0 in the slots it lacks: in-bounds loads that no sum
 //      reads;
-//   2. the scalar loads of the NEXT unit (D, row pointers, offsets): under way while the values arrive;
+//   2. the scalar loads of the NEXT unit (row pointers; D and the offsets from its class' table, whose address
+//      needs no load: the class ids of the wave's segments are in registers since the kernel's start): under way
+//      while the values arrive;
 //   3. the group's values, in flight since the previous group's step 4, go to the stage: all NL chunks of
 //      every lane, no branch (entries at or behind `len` are never read: pos < len for every stored slot);
 //   4. the NL value loads of the next group, ALWAYS issued, from ONE load site in the loop (and one in front
@@ -164,20 +298,25 @@ __device__ __forceinline__ int wave_exclusive_sum(int v)
 //   5. the row phase: the prefix sum of the row lengths waits for the mask alone (vmcnt(NL + ND): the first load
 //      of the group), the wait in front of the last x leaves the NL loads of step 4 in flight.
 // Compiled for double, ND = 28: stage write vmcnt(43) .. (29) = the group's own 29 loads behind the values, row
-// phase vmcnt(43) .. vmcnt(15), no vmcnt wait between the top of a group and its last x load; 153 VGPRs (fused
-// dot 157), 15 KiB of LDS: 3 waves per SIMD by registers, 10 waves per CU by LDS (docs/KERNELS.md 36).
+// phase vmcnt(43) .. vmcnt(15), no vmcnt wait between the top of a group and its last x load; 155 VGPRs (fused
+// dot 159), 15 KiB of LDS: 3 waves per SIMD by registers, 10 waves per CU by LDS (docs/KERNELS.md 36).
 // "Always" because the loop runs over the groups that HAVE a successor; the wave's last group does 1 - 3 and 5
 // behind it.  (Issuing step 4 there too, as re-reads of the group's last 16 bytes, was measured: with two
 // segments per wave every second prefetch is then a dummy, and the kernel was 3.7 % slower than with the
 // conditional prefetch it replaced, docs/KERNELS.md 36.)
 // __launch_bounds__(64, 3) on the 28-slot kernels changes neither their registers nor, measurably, their time
 // (docs/KERNELS.md 36): all instantiations keep (64, 2).
-template <typename T, bool ADV, bool DOT, int ND>
+// NT: the value stream is loaded and c stored non-temporally (`global_load_dwordx4 ... nt`, counted by vmcnt like
+// any load: the waits above are the same).  A value is used once per product, and with NT the stream does not
+// pass through the L2 and Infinity Cache lines that serve the re-reads of x: -5 % on the 27-point stencil 256^3
+// (3.6 GB of values).  A product whose bytes FIT the 256 MiB Infinity Cache is served from it call after call,
+// and there NT costs 18 - 25 % (docs/KERNELS.md 36): the launcher sets it by the product's bytes.
+template <typename T, bool ADV, bool DOT, int ND, bool NT>
 __global__ __launch_bounds__(64, 2) void csr_spmv_pipe3_kernel_offsets(
     int32_t n_rows, int32_t n_cols, int64_t n_segments, int spw, const int32_t* __restrict__ row_ptrs,
     const T* __restrict__ vals, const T* __restrict__ x, T* __restrict__ c, const T* __restrict__ alpha_p,
-    const T* __restrict__ beta_p, const int32_t* __restrict__ seg_tab, const uint32_t* __restrict__ row_mask,
-    T* __restrict__ dot_partial)
+    const T* __restrict__ beta_p, const int32_t* __restrict__ seg_class, const int32_t* __restrict__ cls_tab,
+    const uint32_t* __restrict__ cls_mask, T* __restrict__ dot_partial)
 {
     constexpr int GR = 64;                             // rows of a resident group = the segment
     constexpr int E = 16 / sizeof(T);                  // entries per lane and load
@@ -200,12 +339,19 @@ __global__ __launch_bounds__(64, 2) void csr_spmv_pipe3_kernel_offsets(
         beta = beta_p[0];
     }
     T dot_acc = T(0);
+    // The class ids of ALL the wave's segments (spw is 1 or 2: plan_segments), read up front: the address of a
+    // class' table depends on its id, and with the ids in registers before the first unit is read no table
+    // address is waited for inside the loop - read_unit stays straight-line scalar loads.  (A wave's only or
+    // last segment is read twice.)
+    const int32_t cid0 = seg_class[n_units > 0 ? sb : 0];
+    const int32_t cid1 = seg_class[n_units > 1 ? sb + 1 : (n_units > 0 ? sb : 0)];
 
     // what the wave knows about a group before it streams it: wave-uniform, read with scalar loads (which the
     // vector loads in flight do not wait for) one group ahead, the segment's offsets included
     struct unit {
         int u;          // index among the wave's units; n_units and above: there is none
         int D;
+        int cid;        // the segment's class: row cid of cls_tab, rows 64 cid .. of cls_mask
         int row0;
         int lead;       // entries of the previous group in front of this one's first: k0 - k0a < E
         int k0a, len;   // aligned stream start; entries from there to the group's end.  0: nothing to do
@@ -216,14 +362,16 @@ __global__ __launch_bounds__(64, 2) void csr_spmv_pipe3_kernel_offsets(
     // what unit_of reads: straight-line scalar loads, every address one of a unit the wave owns (the last
     // one again behind the end); nothing here waits for them
     struct unit_raw {
-        int u, row0, k0, k1, D;
+        int u, row0, k0, k1, D, cid;
         int32_t off[ND];
     };
     auto read_unit = [&](int u) {
         unit_raw r;
         r.u = u;
-        const int64_t s = sb + (u < n_units ? u : n_units - 1);
-        const int32_t* tab = seg_tab + s * OFFS_TAB;
+        const int uc = u < n_units ? u : n_units - 1;
+        const int64_t s = sb + uc;
+        r.cid = uc == 0 ? cid0 : cid1;
+        const int32_t* tab = cls_tab + int64_t(r.cid) * OFFS_TAB;
         r.row0 = int(s * 64);
         const int last = r.row0 + GR < n_rows ? r.row0 + GR : n_rows;
         r.k0 = row_ptrs[r.row0];
@@ -237,6 +385,7 @@ __global__ __launch_bounds__(64, 2) void csr_spmv_pipe3_kernel_offsets(
         unit q;
         q.u = r.u;
         q.D = r.D;
+        q.cid = r.cid;
         q.row0 = r.row0;
 #pragma unroll
         for (int d = 0; d < ND; ++d) q.off[d] = r.off[d];
@@ -259,7 +408,13 @@ __global__ __launch_bounds__(64, 2) void csr_spmv_pipe3_kernel_offsets(
 #pragma unroll
         for (int t = 0; t < NL; ++t) {
             const int k = (t * 64 + lane) * E;
-            v[t] = *reinterpret_cast<const VT*>(vals + (int64_t(q.k0a) + (k < last_chunk ? k : last_chunk)));
+            const VT* from =
+                reinterpret_cast<const VT*>(vals + (int64_t(q.k0a) + (k < last_chunk ? k : last_chunk)));
+            if constexpr (NT) {
+                v[t] = __builtin_nontemporal_load(from);
+            } else {
+                v[t] = *from;
+            }
         }
     };
     // A group in two halves, so that the loop below can put the next group's value loads between them.
@@ -277,8 +432,9 @@ __global__ __launch_bounds__(64, 2) void csr_spmv_pipe3_kernel_offsets(
     auto head = [&](const unit& cur, lane_state& ls, unit_raw& nxt_raw) {
         ls.row = cur.row0 + lane;
         ls.valid = ls.row < n_rows;
-        // (first what the row phase needs first)
-        ls.mask_raw = row_mask[ls.valid ? ls.row : cur.row0];
+        // (first what the row phase needs first; a class' mask of a row at or behind n_rows is 0)
+        // (a scalar base and the lane as a 32-bit offset: no address pair kept in vector registers)
+        ls.mask_raw = (cls_mask + int64_t(cur.cid) * 64)[threadIdx.x];
         ls.sum = T(0);
         ls.bdot = T(0);
         if (ADV && beta != T(0)) ls.sum = c[ls.valid ? ls.row : cur.row0] * beta;
@@ -345,7 +501,11 @@ __global__ __launch_bounds__(64, 2) void csr_spmv_pipe3_kernel_offsets(
         // `valid` branch below, whose other side reaches the next group with this group's x loads unwaited-for
         // and puts write-after-load waits between the next group's x loads)
         asm volatile("" : "+v"(sum));
-        if (ls.valid) c[ls.row] = sum;
+        if constexpr (NT) {
+            if (ls.valid) __builtin_nontemporal_store(sum, &c[ls.row]);
+        } else {
+            if (ls.valid) c[ls.row] = sum;
+        }
         if constexpr (DOT) {
             // (the row-segment kernel's lane for this row is row % 64 too)
             const T term = ls.bdot * sum;

@@ -22,11 +22,14 @@
 //                        + n_cols*sizeof(T) (b once) + n*sizeof(T) (c).
 #include <algorithm>
 #include <atomic>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <tuple>
 #include <type_traits>
 #include <vector>
+
+#include <rocprim/rocprim.hpp>
 
 #include "common.hpp"
 #include "csr_long_rows.hpp"
@@ -377,8 +380,11 @@ struct offsets_plan {
     int state = 0;                  // 0: seen once, 1: in use, 2: rejected (fewer than half of the segments eligible)
     int64_t n_seg = 0, eligible = 0;
     int max_d = 0;                  // the largest D of a segment: picks the product kernel's diagonal slots
-    int32_t* seg_tab = nullptr;     // device: OFFS_TAB int32 per segment
-    uint32_t* row_mask = nullptr;   // device: one word per row
+    int64_t n_classes = 0;          // distinct (table, masks) among the segments (csr_offsets.hpp)
+    int64_t nnz = 0;                // stored entries when the plan was built: sizes the product (offsets_nt_min_bytes)
+    int32_t* seg_class = nullptr;   // device: the class id of every segment
+    int32_t* cls_tab = nullptr;     // device: OFFS_TAB int32 per class
+    uint32_t* cls_mask = nullptr;   // device: 64 words per class, one per row of a segment
     uint32_t* skip = nullptr;       // device: bit per segment the row-segment kernel leaves out (eligible | long-flagged)
     bool with_long = false;         // skip holds the long-row flags too
     int64_t bytes = 0, products = 0;
@@ -391,6 +397,9 @@ constexpr size_t offsets_cache_cap = 128;
 // at least this share of the segments must be eligible, in per cent (docs/KERNELS.md: measured on a stencil
 // whose every other segment is not)
 constexpr int64_t offsets_min_share = 50;
+// the MI355X's Infinity Cache, 256 MiB: a product that streams more than this per call cannot live in it, and its
+// value stream and result bypass it (measured on both sides of it: docs/KERNELS.md 36)
+constexpr int64_t offsets_nt_min_bytes = int64_t(256) << 20;
 
 // buffers of dropped plans that could not be released at once (inside a stream capture the device cannot be
 // synchronised): released with the next plan that goes.  Guarded by g_off_mtx.
@@ -402,7 +411,8 @@ void offsets_release(std::vector<offsets_plan>& gone)
 {
     std::vector<void*> bufs;
     for (auto& pl : gone) {
-        for (void* b : {static_cast<void*>(pl.seg_tab), static_cast<void*>(pl.row_mask), static_cast<void*>(pl.skip)}) {
+        for (void* b : {static_cast<void*>(pl.seg_class), static_cast<void*>(pl.cls_tab),
+                        static_cast<void*>(pl.cls_mask), static_cast<void*>(pl.skip)}) {
             if (b) bufs.push_back(b);
         }
     }
@@ -417,48 +427,146 @@ void offsets_release(std::vector<offsets_plan>& gone)
     g_off_graveyard.clear();
 }
 
-// the analysis: one pass over the column indices, the eligible count and the largest D come back with one
-// stream synchronisation
+// scratch of the class search for n segments, in bytes, and where its parts lie
+struct class_scratch {
+    size_t hash, hash_sorted, ids, ids_sorted, leader, is_new, class_at, prim, prim_bytes, total;
+};
+class_scratch class_scratch_of(int64_t n)
+{
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    size_t sort_bytes = 0, scan_bytes = 0;
+    unsigned long long* k = nullptr;
+    uint32_t* v = nullptr;
+    (void)rocprim::radix_sort_pairs(nullptr, sort_bytes, k, k, v, v, size_t(n), 0, 64, hipStream_t(nullptr));
+    (void)rocprim::exclusive_scan(nullptr, scan_bytes, v, v, uint32_t(0), size_t(n), rocprim::plus<uint32_t>(),
+                                  hipStream_t(nullptr));
+    class_scratch c;
+    size_t at = 0;
+    auto part = [&](size_t bytes) {
+        const size_t here = at;
+        at += up(bytes);
+        return here;
+    };
+    c.hash = part(size_t(n) * 8);
+    c.hash_sorted = part(size_t(n) * 8);
+    c.ids = part(size_t(n) * 4);
+    c.ids_sorted = part(size_t(n) * 4);
+    c.leader = part(size_t(n) * 4);
+    c.is_new = part(size_t(n) * 4);
+    c.class_at = part(size_t(n) * 4);
+    c.prim_bytes = sort_bytes > scan_bytes ? sort_bytes : scan_bytes;
+    c.prim = part(c.prim_bytes);
+    c.total = at;
+    return c;
+}
+
+// The analysis.  One pass over the column indices gives the per-segment tables and the per-row masks; behind it,
+// on the same stream, the class search of csr_offsets.hpp (hash, stable sort of (hash, segment), compare with the
+// run's leader, scan).  The eligible count, the largest D and the number of classes come back with ONE stream
+// synchronisation.  An accepted plan is then compacted - a class id per segment, a table and 64 masks per class,
+// sized by the count - and the per-segment tables, the per-row masks and the scratch are freed behind a second,
+// short synchronisation (the compaction reads them): what a plan keeps is 4 n_seg + 388 n_classes bytes
+// (+ the skip bits), 1 MiB for the 27-point stencil 256^3 where tables and masks were 97 MiB.
 int offsets_build(hipStream_t st, int64_t n_rows, const int32_t* row_ptrs, const int32_t* col_idxs,
                   const csr_long_info& lng, offsets_plan& pl)
 {
     const int64_t n_seg = ceildiv(n_rows, int64_t(64));
     const size_t tab_bytes = size_t(n_seg) * OFFS_TAB * 4, mask_bytes = size_t(n_rows) * 4;
     const size_t skip_bytes = size_t(ceildiv(n_seg, int64_t(32))) * 4;
-    void *tab = nullptr, *mask = nullptr, *skip = nullptr, *count_dev = nullptr;
-    bool ok = arena_malloc(&tab, tab_bytes, GKOC_MEM_INDICES) == GKOC_OK &&
+    const size_t ids_bytes = size_t(n_seg) * 4;
+    const class_scratch cs = class_scratch_of(n_seg);
+    // (cut to its low bits only to provoke collisions: the tests of the compare-with-the-leader path)
+    const int64_t hash_bits = tune_value(GKOC_TUNE_CSR_OFFSETS_HASH_BITS);
+    const unsigned long long keep = (hash_bits < 0 || hash_bits >= 64) ? ~0ull : ((1ull << hash_bits) - 1ull);
+    void *tab = nullptr, *mask = nullptr, *skip = nullptr, *count_dev = nullptr, *ids = nullptr, *work = nullptr;
+    void *ctab = nullptr, *cmask = nullptr;
+    bool ok = n_seg > 0 && arena_malloc(&tab, tab_bytes, GKOC_MEM_INDICES) == GKOC_OK &&
               arena_malloc(&mask, mask_bytes, GKOC_MEM_INDICES) == GKOC_OK &&
               arena_malloc(&skip, skip_bytes, GKOC_MEM_INDICES) == GKOC_OK &&
-              arena_malloc(&count_dev, 16, GKOC_MEM_VECTOR) == GKOC_OK;
-    unsigned long long count[2] = {0, 0};
+              arena_malloc(&ids, ids_bytes, GKOC_MEM_INDICES) == GKOC_OK &&
+              arena_malloc(&work, cs.total, GKOC_MEM_INDICES) == GKOC_OK &&
+              arena_malloc(&count_dev, 32, GKOC_MEM_VECTOR) == GKOC_OK;
+    char* w = static_cast<char*>(work);
+    auto at = [&](size_t off) { return static_cast<void*>(w + off); };
+    const dim3 seg_grid(unsigned(ceildiv(n_seg, int64_t(4)))), seg_block(256);
+    unsigned long long count[4] = {0, 0, 0, 0};
     if (ok) {
-        csr_offsets_build_kernel<int32_t><<<dim3(unsigned(ceildiv(n_seg, int64_t(4)))), dim3(256), 0, st>>>(
+        const int32_t* tab_c = static_cast<const int32_t*>(tab);
+        const uint32_t* mask_c = static_cast<const uint32_t*>(mask);
+        csr_offsets_build_kernel<int32_t><<<seg_grid, seg_block, 0, st>>>(
             n_rows, row_ptrs, col_idxs, static_cast<int32_t*>(tab), static_cast<uint32_t*>(mask));
         csr_offsets_finish_kernel<<<dim3(1), dim3(1024), 0, st>>>(
-            n_seg, static_cast<const int32_t*>(tab), lng.count > 0 ? lng.bits : nullptr,
-            static_cast<uint32_t*>(skip), static_cast<unsigned long long*>(count_dev));
+            n_seg, tab_c, lng.count > 0 ? lng.bits : nullptr, static_cast<uint32_t*>(skip),
+            static_cast<unsigned long long*>(count_dev));
+        csr_offsets_hash_kernel<<<seg_grid, seg_block, 0, st>>>(
+            n_rows, n_seg, tab_c, mask_c, keep, static_cast<unsigned long long*>(at(cs.hash)),
+            static_cast<uint32_t*>(at(cs.ids)));
+        size_t prim_bytes = cs.prim_bytes;
         ok = hipGetLastError() == hipSuccess &&
-             hipMemcpyAsync(count, count_dev, 16, hipMemcpyDeviceToHost, st) == hipSuccess &&
-             hipStreamSynchronize(st) == hipSuccess;
+             rocprim::radix_sort_pairs(at(cs.prim), prim_bytes, static_cast<unsigned long long*>(at(cs.hash)),
+                                       static_cast<unsigned long long*>(at(cs.hash_sorted)),
+                                       static_cast<uint32_t*>(at(cs.ids)), static_cast<uint32_t*>(at(cs.ids_sorted)),
+                                       size_t(n_seg), 0, 64, st) == hipSuccess;
+        if (ok) {
+            csr_offsets_leader_kernel<<<seg_grid, seg_block, 0, st>>>(
+                n_rows, n_seg, tab_c, mask_c, static_cast<const unsigned long long*>(at(cs.hash_sorted)),
+                static_cast<const uint32_t*>(at(cs.ids_sorted)), static_cast<uint32_t*>(at(cs.leader)),
+                static_cast<uint32_t*>(at(cs.is_new)));
+            prim_bytes = cs.prim_bytes;
+            ok = hipGetLastError() == hipSuccess &&
+                 rocprim::exclusive_scan(at(cs.prim), prim_bytes, static_cast<uint32_t*>(at(cs.is_new)),
+                                         static_cast<uint32_t*>(at(cs.class_at)), uint32_t(0), size_t(n_seg),
+                                         rocprim::plus<uint32_t>(), st) == hipSuccess;
+        }
+        if (ok) {
+            csr_offsets_class_count_kernel<<<dim3(1), dim3(1), 0, st>>>(
+                n_seg, static_cast<const uint32_t*>(at(cs.is_new)), static_cast<const uint32_t*>(at(cs.class_at)),
+                n_rows, row_ptrs, static_cast<unsigned long long*>(count_dev));
+            ok = hipGetLastError() == hipSuccess;
+        }
+        // (whatever was enqueued has run when the buffers are freed below, also after an error)
+        const bool copied = ok && hipMemcpyAsync(count, count_dev, 32, hipMemcpyDeviceToHost, st) == hipSuccess;
+        ok = hipStreamSynchronize(st) == hipSuccess && copied;
     }
     (void)hipGetLastError();
     if (count_dev) (void)arena_free(count_dev);
     pl.n_seg = n_seg;
     pl.eligible = ok ? int64_t(count[0]) : 0;
     pl.max_d = ok ? int(count[1]) : 0;
-    if (!ok || pl.eligible == 0 || pl.eligible * 100 < n_seg * offsets_min_share) {
-        if (tab) (void)arena_free(tab);
-        if (mask) (void)arena_free(mask);
-        if (skip) (void)arena_free(skip);
+    const int64_t n_classes = ok ? int64_t(count[2]) : 0;
+    const bool accepted = ok && pl.eligible > 0 && pl.eligible * 100 >= n_seg * offsets_min_share;
+    bool compacted = false;
+    if (accepted && n_classes >= 1 && n_classes <= n_seg &&
+        arena_malloc(&ctab, size_t(n_classes) * OFFS_TAB * 4, GKOC_MEM_INDICES) == GKOC_OK &&
+        arena_malloc(&cmask, size_t(n_classes) * 64 * 4, GKOC_MEM_INDICES) == GKOC_OK) {
+        csr_offsets_compact_kernel<<<seg_grid, seg_block, 0, st>>>(
+            n_rows, n_seg, static_cast<const int32_t*>(tab), static_cast<const uint32_t*>(mask),
+            static_cast<const uint32_t*>(at(cs.ids_sorted)), static_cast<const uint32_t*>(at(cs.leader)),
+            static_cast<const uint32_t*>(at(cs.is_new)), static_cast<const uint32_t*>(at(cs.class_at)),
+            static_cast<int32_t*>(ids), static_cast<int32_t*>(ctab), static_cast<uint32_t*>(cmask));
+        const bool launched = hipGetLastError() == hipSuccess;
+        compacted = hipStreamSynchronize(st) == hipSuccess && launched;
+        (void)hipGetLastError();
+    }
+    if (tab) (void)arena_free(tab);
+    if (mask) (void)arena_free(mask);
+    if (work) (void)arena_free(work);
+    if (!compacted) {
+        for (void* b : {skip, ids, ctab, cmask}) {
+            if (b) (void)arena_free(b);
+        }
         // too few eligible segments: rejected for good; an analysis that FAILED (no memory, a stream error) is
         // tried again by the next product
-        if (ok) pl.state = 2;
+        if (ok && !accepted) pl.state = 2;
         return GKOC_OK;
     }
     pl.state = 1;
-    pl.seg_tab = static_cast<int32_t*>(tab);
-    pl.row_mask = static_cast<uint32_t*>(mask);
-    pl.bytes = int64_t(tab_bytes + mask_bytes);
+    pl.n_classes = n_classes;
+    pl.nnz = int64_t(count[3]);
+    pl.seg_class = static_cast<int32_t*>(ids);
+    pl.cls_tab = static_cast<int32_t*>(ctab);
+    pl.cls_mask = static_cast<uint32_t*>(cmask);
+    pl.bytes = int64_t(ids_bytes) + n_classes * int64_t((OFFS_TAB + 64) * 4);
     if (pl.eligible == n_seg) {
         (void)arena_free(skip);        // every segment is this kernel's: the row-segment kernel is not launched
     } else {
@@ -533,9 +641,18 @@ void launch_offsets_kernel_nd(hipStream_t st, const offsets_plan& pl, const segm
                               const T* beta, T* c, T* dot_partial)
 {
     const dim3 grid(static_cast<unsigned>(p.n_waves)), block(64);
-    csr_spmv_pipe3_kernel_offsets<T, ADV, DOT, ND><<<grid, block, 0, st>>>(
-        int32_t(n_rows), int32_t(n_cols), p.n_seg, p.spw, row_ptrs, vals, b, c, alpha, beta, pl.seg_tab,
-        pl.row_mask, dot_partial);
+    // values, x, c and the row pointers: what a product streams.  Above the Infinity Cache's size the values and
+    // c go non-temporally (csr_offsets.hpp NT), below it repeated products are served from that cache
+    const int64_t product_bytes = pl.nnz * int64_t(sizeof(T)) + (n_rows + n_cols) * int64_t(sizeof(T)) + n_rows * 4;
+    if (product_bytes > offsets_nt_min_bytes) {
+        csr_spmv_pipe3_kernel_offsets<T, ADV, DOT, ND, true><<<grid, block, 0, st>>>(
+            int32_t(n_rows), int32_t(n_cols), p.n_seg, p.spw, row_ptrs, vals, b, c, alpha, beta, pl.seg_class,
+            pl.cls_tab, pl.cls_mask, dot_partial);
+    } else {
+        csr_spmv_pipe3_kernel_offsets<T, ADV, DOT, ND, false><<<grid, block, 0, st>>>(
+            int32_t(n_rows), int32_t(n_cols), p.n_seg, p.spw, row_ptrs, vals, b, c, alpha, beta, pl.seg_class,
+            pl.cls_tab, pl.cls_mask, dot_partial);
+    }
 }
 
 template <typename T, bool ADV, bool DOT>
@@ -1331,6 +1448,24 @@ extern "C" int gkoc_csr_plan_info(const void* row_ptrs, const void* col_idxs, in
     if (segments) *segments = ns;
     if (bytes) *bytes = by;
     if (products_by_plan) *products_by_plan = pr;
+    return GKOC_OK;
+}
+
+extern "C" int gkoc_csr_plan_classes(const void* row_ptrs, const void* col_idxs, uint64_t* classes)
+{
+    uint64_t nc = 0;
+    int dev = 0;
+    GKOC_HIP(hipGetDevice(&dev));
+    {
+        std::lock_guard<std::mutex> g(gkoc::g_off_mtx);
+        for (const auto& kv : gkoc::g_off_cache) {
+            if (std::get<0>(kv.first) == dev && std::get<1>(kv.first) == row_ptrs &&
+                std::get<2>(kv.first) == col_idxs) {
+                nc = uint64_t(kv.second.n_classes);
+            }
+        }
+    }
+    if (classes) *classes = nc;
     return GKOC_OK;
 }
 

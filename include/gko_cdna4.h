@@ -237,6 +237,11 @@ int gkoc_arena_probe(const void* x, size_t x_bytes, void* y, int read_kb_per_wav
                                       the second product on the same (row_ptrs, col_idxs), 1: by the first, 2: never
                                       (the row-segment kernel alone).  Only ever
                                       for index arrays that are live allocations of gkoc_malloc / gkoc_malloc_role. */
+#define GKOC_TUNE_CSR_OFFSETS_HASH_BITS 19 /* the column-offset plan's search for equal segments (csrc/csr_offsets.hpp):
+                                      the low bits of a segment's 64-bit hash that are kept.  64 (default) and above,
+                                      or negative: all of them; fewer make unequal segments collide - 0: every
+                                      segment with the first one - which costs classes, never a result: for the
+                                      tests of the collision path.  Read when a plan is built. */
 int gkoc_tune_set(int key, int64_t value);
 int gkoc_tune_get(int key, int64_t* value);
 /* HipHostAllocator (pinned host memory) and HipUnifiedAllocator (managed memory,
@@ -345,10 +350,15 @@ GKOC_DECL_CSR(float, f32, int64_t, i64)
  * and a graph that holds it must not be replayed after the plan was dropped).
  * gkoc_csr_plan_info: state -1 none, 0 arrays seen once, 1 plan in use, 2 analysed and rejected (fewer than half
  * of the segments eligible); eligible / all 64-row segments; bytes of device memory of the plan; products that
- * ran through it.  Any result pointer may be NULL. */
+ * ran through it.  Any result pointer may be NULL.
+ * The plan is kept by CLASS: segments whose offsets and row masks are equal bit for bit share one table, and a
+ * segment keeps a 4-byte class id, so bytes = 4 segments + 388 classes (+ a bit per segment where not every
+ * segment is eligible).  gkoc_csr_plan_classes: the number of classes of a plan in use (a host result), 0
+ * where there is none. */
 int gkoc_csr_structure_changed(const void* index_array);
 int gkoc_csr_plan_info(const void* row_ptrs, const void* col_idxs, int* state, int64_t* eligible_segments,
                        int64_t* segments, int64_t* bytes, int64_t* products_by_plan);
+int gkoc_csr_plan_classes(const void* row_ptrs, const void* col_idxs, uint64_t* classes);
 
 /* --------------------------------------------------------------- ELL SpMV
  * ell::spmv / advanced_spmv  core/matrix/ell_kernels.hpp:20-34
