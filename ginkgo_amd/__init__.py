@@ -2,7 +2,7 @@
 
 Thin host-side mirror of the gko::Executor / gko::LinOp / solver-factory
 interface over the C ABI of libgko_cdna4.so (include/gko_cdna4.h): CSR / ELL /
-SELL-P / Fbcsr SpMV, block-Jacobi, level-scheduled triangular solves with Sor / SSOR, ILU(0) / IC(0) with Ilu / Ic (exact, or by the fixed-point sweeps of factorization.ParIlu / ParIc), triangular ISAI (LowerIsai / UpperIsai), general and spd ISAI (GeneralIsai / SpdIsai), Pgm aggregation and a Multigrid solver / preconditioner, batched Cg / Bicgstab on batch Csr / Ell (ginkgo_amd.batch), BLAS-1 and the fused CG steps as hand-written HIP
+SELL-P / Fbcsr SpMV, block-Jacobi, level-scheduled triangular solves with Sor / SSOR, ILU(0) / IC(0) with Ilu / Ic (exact, by the fixed-point sweeps of factorization.ParIlu / ParIc, or with threshold fill-in by factorization.ParIlut / ParIct), triangular ISAI (LowerIsai / UpperIsai), general and spd ISAI (GeneralIsai / SpdIsai), Pgm aggregation and a Multigrid solver / preconditioner, batched Cg / Bicgstab on batch Csr / Ell (ginkgo_amd.batch), BLAS-1 and the fused CG steps as hand-written HIP
 kernels.  Importing the package does not need a GPU; creating a
 Cdna4Executor does, and there is no CPU fallback.
 """

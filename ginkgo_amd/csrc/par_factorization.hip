@@ -1,10 +1,12 @@
 // ILU(0) / IC(0) by fixed-point sweeps (factorization::ParIlu / ParIc; Chow, Patel, "Fine-grained parallel
 // incomplete LU factorization", SIAM J. Sci. Comput. 37, 2015), without a level schedule:
 //   par_ilu_sweeps / par_ic_sweeps                  `iterations` row-synchronous sweeps, one launch each
+//   par_ilu_sweeps_from / par_ic_sweeps_from        the same from a given iterate v^0 (ParIlut / ParIct)
 //
 // Contract (include/gko_cdna4.h; -ffp-contract=off keeps multiply and subtract apart), rows sorted: sweep t
 // computes EVERY row with the sequential row step of the exact contract (factorization.hip).  Values of other
-// rows, pivots included, are the ones of sweep t-1 (`prev`; sweep 1: the input a); the values of the row itself
+// rows, pivots included, are the ones of sweep t-1 (`prev`; sweep 1: v^0, which is the input a unless the _from
+// entry gives another); the values of the row itself
 // start from the input a and are the ones just computed in this sweep.
 //   ILU: w = a(row i); for every stored k < i ascending: w_ik = w_ik / prev_kk, then for every stored j > k of
 //        row k with (i, j) stored: w_ij = w_ij - w_ik * prev_kj.
@@ -147,7 +149,7 @@ __global__ __launch_bounds__(sweep_block) void par_sweep_kernel(int64_t n, const
 }
 
 template <bool IC, int W, typename T, typename I>
-int sweeps_launch(hipStream_t st, int64_t n, const I* rp, const I* ci, const I* diag, const T* a,
+int sweeps_launch(hipStream_t st, int64_t n, const I* rp, const I* ci, const I* diag, const T* a, const T* v0,
                   int64_t iterations, T* work, T* out, uint64_t* changed)
 {
     int64_t blocks = ceildiv(n, sweep_block / W);
@@ -156,7 +158,7 @@ int sweeps_launch(hipStream_t st, int64_t n, const I* rp, const I* ci, const I* 
         // sweep t writes out if iterations - t is even: the last one always does
         const bool to_out = (iterations - t) % 2 == 0;
         T* next = to_out ? out : work;
-        const T* prev = t == 1 ? a : (to_out ? work : out);
+        const T* prev = t == 1 ? v0 : (to_out ? work : out);
         par_sweep_kernel<IC, W, T, I><<<dim3(unsigned(blocks)), dim3(sweep_block), 0, st>>>(
             n, rp, ci, diag, a, prev, next,
             t == iterations ? reinterpret_cast<unsigned long long*>(changed) : nullptr);
@@ -173,7 +175,7 @@ inline bool overlap(const void* p, const void* q, size_t bytes)
 }
 
 template <bool IC, typename T, typename I>
-int par_sweeps(gkoc_stream_t s, int64_t n, int64_t nnz, const I* rp, const I* ci, const T* a,
+int par_sweeps(gkoc_stream_t s, int64_t n, int64_t nnz, const I* rp, const I* ci, const T* a, const T* v0,
                int64_t iterations, T* work, T* out, uint64_t* changed)
 {
     GKOC_REQUIRE(iterations >= 1, GKOC_E_INVALID, "fewer than one sweep");
@@ -184,11 +186,13 @@ int par_sweeps(gkoc_stream_t s, int64_t n, int64_t nnz, const I* rp, const I* ci
         return GKOC_OK;
     }
     GKOC_REQUIRE(nnz >= n, GKOC_E_INVALID, "fewer stored entries than rows: a row without a stored diagonal");
-    GKOC_REQUIRE(rp && ci && a && out, GKOC_E_INVALID, "null pointer");
+    GKOC_REQUIRE(rp && ci && a && v0 && out, GKOC_E_INVALID, "null pointer");
     GKOC_REQUIRE(work || iterations == 1, GKOC_E_INVALID, "more than one sweep needs the work buffer");
     const size_t bytes = sizeof(T) * size_t(nnz);
     GKOC_REQUIRE(!overlap(a, out, bytes) && (!work || (!overlap(a, work, bytes) && !overlap(work, out, bytes))),
                  GKOC_E_INVALID, "a_vals, work and out_vals must be three separate buffers");
+    GKOC_REQUIRE(v0 == a || (!overlap(v0, out, bytes) && (!work || !overlap(v0, work, bytes))), GKOC_E_INVALID,
+                 "v0_vals must not overlap work or out_vals");
     // scratch: 4 status words, then the diagonal positions
     void* raw = nullptr;
     GKOC_TRY(scratch_malloc(st, &raw, 16 + sizeof(I) * size_t(n)));
@@ -209,12 +213,12 @@ int par_sweeps(gkoc_stream_t s, int64_t n, int64_t nnz, const I* rp, const I* ci
     GKOC_REQUIRE(!IC || host[2] == 0, GKOC_E_INVALID, "a row whose last entry is not its diagonal");
     if (changed) GKOC_HIP(hipMemsetAsync(changed, 0, sizeof(uint64_t), st));
     if (host[3] <= fact_row_limits[0]) {
-        return sweeps_launch<IC, 16, T, I>(st, n, rp, ci, diag, a, iterations, work, out, changed);
+        return sweeps_launch<IC, 16, T, I>(st, n, rp, ci, diag, a, v0, iterations, work, out, changed);
     }
     if (host[3] <= fact_row_limits[1]) {
-        return sweeps_launch<IC, 32, T, I>(st, n, rp, ci, diag, a, iterations, work, out, changed);
+        return sweeps_launch<IC, 32, T, I>(st, n, rp, ci, diag, a, v0, iterations, work, out, changed);
     }
-    return sweeps_launch<IC, 64, T, I>(st, n, rp, ci, diag, a, iterations, work, out, changed);
+    return sweeps_launch<IC, 64, T, I>(st, n, rp, ci, diag, a, v0, iterations, work, out, changed);
 }
 
 }  // namespace
@@ -222,23 +226,26 @@ int par_sweeps(gkoc_stream_t s, int64_t n, int64_t nnz, const I* rp, const I* ci
 
 using namespace gkoc;
 
-#define GKOC_DEF_PAR_FACTORIZATION(T, TN, I, IN)                                                               \
-    extern "C" int gkoc_par_ilu_sweeps_##TN##_##IN(gkoc_stream_t s, int64_t n_rows, int64_t nnz,               \
-                                                   const I* row_ptrs, const I* col_idxs, const T* a_vals,      \
-                                                   int64_t iterations, T* work, T* out_vals,                   \
-                                                   uint64_t* changed_dev)                                      \
+// the plain entries are the _from ones with v^0 = a
+#define GKOC_DEF_PAR_SWEEPS(KIND, IC, T, TN, I, IN)                                                            \
+    extern "C" int gkoc_par_##KIND##_sweeps_##TN##_##IN(gkoc_stream_t s, int64_t n_rows, int64_t nnz,          \
+                                                        const I* row_ptrs, const I* col_idxs, const T* a_vals, \
+                                                        int64_t iterations, T* work, T* out_vals,              \
+                                                        uint64_t* changed_dev)                                 \
     {                                                                                                          \
-        return par_sweeps<false, T, I>(s, n_rows, nnz, row_ptrs, col_idxs, a_vals, iterations, work, out_vals, \
-                                       changed_dev);                                                           \
+        return par_sweeps<IC, T, I>(s, n_rows, nnz, row_ptrs, col_idxs, a_vals, a_vals, iterations, work,      \
+                                    out_vals, changed_dev);                                                    \
     }                                                                                                          \
-    extern "C" int gkoc_par_ic_sweeps_##TN##_##IN(gkoc_stream_t s, int64_t n_rows, int64_t nnz,                \
-                                                  const I* row_ptrs, const I* col_idxs, const T* a_vals,       \
-                                                  int64_t iterations, T* work, T* out_vals,                    \
-                                                  uint64_t* changed_dev)                                       \
+    extern "C" int gkoc_par_##KIND##_sweeps_from_##TN##_##IN(                                                  \
+        gkoc_stream_t s, int64_t n_rows, int64_t nnz, const I* row_ptrs, const I* col_idxs, const T* a_vals,   \
+        const T* v0_vals, int64_t iterations, T* work, T* out_vals, uint64_t* changed_dev)                     \
     {                                                                                                          \
-        return par_sweeps<true, T, I>(s, n_rows, nnz, row_ptrs, col_idxs, a_vals, iterations, work, out_vals,  \
-                                      changed_dev);                                                            \
+        return par_sweeps<IC, T, I>(s, n_rows, nnz, row_ptrs, col_idxs, a_vals, v0_vals, iterations, work,     \
+                                    out_vals, changed_dev);                                                    \
     }
+#define GKOC_DEF_PAR_FACTORIZATION(T, TN, I, IN)     \
+    GKOC_DEF_PAR_SWEEPS(ilu, false, T, TN, I, IN)    \
+    GKOC_DEF_PAR_SWEEPS(ic, true, T, TN, I, IN)
 GKOC_DEF_PAR_FACTORIZATION(double, f64, int32_t, i32)
 GKOC_DEF_PAR_FACTORIZATION(double, f64, int64_t, i64)
 GKOC_DEF_PAR_FACTORIZATION(float, f32, int32_t, i32)

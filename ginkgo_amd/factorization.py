@@ -24,14 +24,25 @@ many sweeps as the lower solve has levels the factors ARE the exact ones, before
 on the 27-point stencil to 4e-3 after 3 sweeps and 2e-4 after 5.  `with_iterations(0)`, Ginkgo's default
 value, stands for DEFAULT_SWEEPS.  A departure from Ginkgo: an entry that becomes inf / NaN is written like
 any other (Ginkgo keeps the old value), so that a value never depends on the history of the iteration.
+
+`ParIlut` / `ParIct` - mirror of include/ginkgo/core/factorization/{par_ilut,par_ict}.hpp - let the factors
+choose their own pattern by magnitude: `with_iterations(k)` (5) rounds of "add the pattern of L U (L L^T), give
+the candidates their residual-based values, sweep, keep the `with_fill_in_limit(f)` (2.0) times nnz largest
+entries of either triangle, sweep" (include/gko_cdna4.h, "ParIlut / ParIct"; gkoc_par_ilut_* / gkoc_par_ict_*,
+gkoc_par_ilu_sweeps_from_* / gkoc_par_ic_sweeps_from_*; every new pattern comes from the triplet pipeline).  Bit-identical to the
+restatement in tests/par_ilut_refs.py.  The selection is always exact: `with_approximate_select` and
+`with_deterministic_sample` are accepted without effect.  A limit below 1.0 is refused.  Pivots are not checked;
+ParIct in particular can break down where IC(0) does not (docs/KERNELS.md 43).
 """
 import ctypes as C
+import math
 
 import torch
 
 from ._lib import IT, VT, DimensionMismatch, GkoError, NotSupported, call, lib
 from .executor import MEM_INDICES, MEM_VALUES
-from .matrix import Csr, Fbcsr
+from .isai import _lower_pattern
+from .matrix import Csr, DeviceMatrixData, Fbcsr
 
 
 def row_limits():
@@ -95,6 +106,50 @@ class _ParFactory(_SweepsMixin, _Factory):
 
 class _ParIcFactory(_SweepsMixin, _IcFactory):
     pass
+
+
+class _ThresholdMixin:
+    """the parameters of the two threshold factories (par_ilut.hpp / par_ict.hpp), Ginkgo's defaults"""
+    iterations = 5
+    fill_in_limit = 2.0
+    approximate_select = True
+    deterministic_sample = False
+
+    def with_iterations(self, v):
+        if int(v) < 1:
+            raise GkoError("with_iterations needs at least one iteration")
+        self.iterations = int(v)
+        return self
+
+    def with_fill_in_limit(self, v):
+        if not float(v) >= 1.0:
+            raise GkoError(f"with_fill_in_limit needs a limit >= 1.0, got {v}: the factors hold at least the "
+                           "entries of the system matrix")
+        self.fill_in_limit = float(v)
+        return self
+
+    def with_approximate_select(self, v):
+        """accepted for API compatibility: the selection is always exact"""
+        self.approximate_select = bool(v)
+        return self
+
+    def with_deterministic_sample(self, v):
+        """accepted for API compatibility: nothing is sampled"""
+        self.deterministic_sample = bool(v)
+        return self
+
+
+class _ParIlutFactory(_ThresholdMixin, _Factory):
+    pass
+
+
+class _ParIctFactory(_ThresholdMixin, _IcFactory):
+    pass
+
+
+def keep_counts(fill_in_limit, n_lower, n_upper):
+    """(keep_L, keep_U): the entries a triangle of the threshold factors may hold beside ties"""
+    return tuple(max(1, int(math.floor(fill_in_limit * count))) for count in (n_lower, n_upper))
 
 
 class _Factorization:
@@ -183,6 +238,89 @@ class _Factorization:
         call(entry + self._suf, ex.stream, n, nnz, m.row_ptrs, m.col_idxs, m.values, self.iterations, work, out,
              self._changed_dev)
         return Csr(ex, m.size, out, m.col_idxs, m.row_ptrs, m.strategy)
+
+    # ---- ParIlut / ParIct: one iteration of the threshold loop (include/gko_cdna4.h, steps 1-6)
+    def _product_pattern(self, left, right, a):
+        """(row_ptrs, col_idxs) of pattern(left * right) + pattern(a), rows sorted: the product's triplets with
+        D = a through the triplet pipeline, all values 1 (nothing cancels, the pipeline drops no zero)"""
+        ex, n, dt = self.exec, self.size[0], a.dtype
+        ones = [ex.alloc((m.values.numel(),), dt).fill_(1) for m in (left, right, a)]
+        offsets, total = ex.alloc((n + 1,), torch.int64), C.c_int64(0)
+        call("gkoc_csr_spgemm_count_" + self._it, ex.stream, n, left.row_ptrs, left.col_idxs, right.row_ptrs,
+             a.row_ptrs, offsets, C.byref(total))
+        t = max(total.value, 1)
+        rows, cols = ex.alloc((t,), a.col_idxs.dtype), ex.alloc((t,), a.col_idxs.dtype)
+        vals = ex.alloc((t,), dt)
+        call("gkoc_csr_spgemm_expand_" + self._suf, ex.stream, n, None, left.row_ptrs, left.col_idxs, ones[0],
+             right.row_ptrs, right.col_idxs, ones[1], None, a.row_ptrs, a.col_idxs, ones[2], offsets, rows, cols,
+             vals)
+        data = DeviceMatrixData(ex, a.size, rows[:total.value], cols[:total.value], vals[:total.value])
+        data.sum_duplicates()
+        rp = Csr.read(data).row_ptrs
+        ex.synchronize()                # the triplets and the ones are released on return
+        return rp, data.col_idxs
+
+    def _gather(self, rp, ci, src):
+        """the values of the sorted Csr `src` at the positions of the pattern, +0 where it stores none"""
+        ex = self.exec
+        out = ex.alloc((ci.numel(),), src.dtype)
+        call("gkoc_par_ilut_gather_" + self._suf, ex.stream, self.size[0], ci.numel(), rp, ci,
+             src.values.numel(), src.row_ptrs, src.col_idxs, src.values, out)
+        return out
+
+    def _sweep_from(self, entry, rp, ci, a_vals, v0):
+        out = self.exec.alloc((ci.numel(),), v0.dtype)
+        call(entry + self._suf, self.exec.stream, self.size[0], ci.numel(), rp, ci, a_vals, v0, 1, None, out, None)
+        return out
+
+    def _threshold_iteration(self, lower_only, a, src, m, keep):
+        """M_t from M_{t-1} = m.  a: the prepared matrix; src: what the sweeps take as their input values (a,
+        or its lower triangle for ict); keep: (keep_L, keep_U)"""
+        ex, n, suf = self.exec, self.size[0], self._suf
+        if lower_only:
+            rp, ci = self._product_pattern(m, m.transpose(), a)
+            rp, ci = _lower_pattern(ex, self.size, rp, ci, a.dtype)
+            candidates, sweeps = "gkoc_par_ict_candidate_values_", "gkoc_par_ic_sweeps_from_"
+        else:
+            l, u = self._split(m, True)
+            rp, ci = self._product_pattern(l, u, a)
+            candidates, sweeps = "gkoc_par_ilut_candidate_values_", "gkoc_par_ilu_sweeps_from_"
+        nnz = ci.numel()
+        v0 = ex.alloc((nnz,), a.dtype)
+        call(candidates + suf, ex.stream, n, nnz, rp, ci, a.values.numel(), a.row_ptrs, a.col_idxs, a.values,
+             m.values.numel(), m.row_ptrs, m.col_idxs, m.values, v0)
+        v = self._sweep_from(sweeps, rp, ci, self._gather(rp, ci, src), v0)
+        # the thresholds stay on the device: the select reads nothing back
+        f = lib().gkoc_par_ilut_select_workspace_bytes
+        f.restype = C.c_size_t
+        work = ex.alloc((int(f()),), torch.uint8)
+        thr = ex.alloc((2,), a.dtype)
+        for part in (0,) if lower_only else (0, 1):
+            call("gkoc_par_ilut_threshold_select_" + suf, ex.stream, n, rp, ci, v, C.c_int(part), keep[part],
+                 work, C.c_size_t(work.numel()), thr[part:part + 1])
+        mask = ex.alloc((nnz,), a.dtype)
+        call("gkoc_par_ilut_keep_mask_" + suf, ex.stream, n, nnz, rp, ci, v, thr[0:1],
+             None if lower_only else thr[1:2], mask)
+        rows = ex.alloc((nnz,), ci.dtype)
+        call("gkoc_convert_ptrs_to_idxs_" + self._it, ex.stream, rp, n, rows)
+        data = DeviceMatrixData(ex, self.size, rows, ci, mask).remove_zeros()
+        kept_rp, kept_ci = Csr.read(data).row_ptrs, data.col_idxs
+        out = self._sweep_from(sweeps, kept_rp, kept_ci, self._gather(kept_rp, kept_ci, src),
+                               self._gather(kept_rp, kept_ci, Csr(ex, self.size, v, ci, rp)))
+        ex.synchronize()                # the iteration's buffers are released on return
+        return Csr(ex, self.size, out, kept_ci, kept_rp)
+
+    def _threshold_loop(self, factory, lower_only, a, src, m):
+        self.iterations, self.fill_in_limit = factory.iterations, factory.fill_in_limit
+        # the sizes of A's triangles from the row pointers of its split: each ends at the triangle + a diagonal
+        ex, n = self.exec, self.size[0]
+        l_rp, u_rp = ex.alloc((n + 1,), a.row_ptrs.dtype), ex.alloc((n + 1,), a.row_ptrs.dtype)
+        call("gkoc_factorization_initialize_row_ptrs_l_u_" + self._it, ex.stream, n, a.row_ptrs, a.col_idxs,
+             l_rp, u_rp)
+        self.keep = keep_counts(self.fill_in_limit, int(l_rp[-1].item()) - n, int(u_rp[-1].item()) - n)
+        for _ in range(self.iterations):
+            m = self._threshold_iteration(lower_only, a, src, m, self.keep)
+        return m
 
     def last_sweep_changes(self):
         """the number of entries whose bits the last sweep changed; 0: the factors are a fixed point of the
@@ -283,6 +421,61 @@ class ParIc(_Factorization):
         self.both_factors = factory.both_factors
         self.lt = self.l.transpose() if self.both_factors else None
         ex.synchronize()                # the prepared copy and the sweeps' buffers are released on return
+
+    def get_l_factor(self):
+        return self.l
+
+    def get_lt_factor(self):
+        return self.lt
+
+
+class ParIlut(_Factorization):
+    """A ~ L U on a pattern the factorization chooses by magnitude: `iterations` rounds of "add the pattern of
+    L U, sweep, keep the fill_in_limit * nnz largest entries of either triangle, sweep" (steps 1-6 of
+    include/gko_cdna4.h).  `keep` holds the two limits."""
+
+    @staticmethod
+    def build():
+        return _ParIlutFactory(ParIlut)
+
+    def __init__(self, factory, a):
+        super().__init__(factory, a)
+        ex = self.exec
+        m = self._prepared(factory, a)
+        self.l, self.u = self._split(self._threshold_loop(factory, False, m, m, m), True)
+        ex.synchronize()                # the prepared copy and the last iterate are released on return
+
+    def get_l_factor(self):
+        return self.l
+
+    def get_u_factor(self):
+        return self.u
+
+
+class ParIct(_Factorization):
+    """A ~ L L^T on a pattern the factorization chooses by magnitude: the loop of ParIlut on the lower
+    triangle, with one limit."""
+
+    @staticmethod
+    def build():
+        return _ParIctFactory(ParIct)
+
+    def __init__(self, factory, a):
+        super().__init__(factory, a)
+        ex = self.exec
+        m = self._prepared(factory, a)
+        last = self._threshold_loop(factory, True, m, self._split(m, False), self._split(m, False, diag_sqrt=True))
+        # the iterate's arrays live with the vectors; the factor's go where a matrix' read-only arrays belong
+        nnz, idx = last.values.numel(), last.col_idxs.dtype
+        rp, ci = ex.alloc((self.size[0] + 1,), idx, MEM_INDICES), ex.alloc((nnz,), idx, MEM_INDICES)
+        v = ex.alloc((nnz,), last.dtype, MEM_VALUES)
+        rp.copy_(last.row_ptrs)
+        ci.copy_(last.col_idxs)
+        v.copy_(last.values)
+        self.l = Csr(ex, self.size, v, ci, rp)
+        self.both_factors = factory.both_factors
+        self.lt = self.l.transpose() if self.both_factors else None
+        ex.synchronize()                # the prepared copy and the last iterate are released on return
 
     def get_l_factor(self):
         return self.l

@@ -2722,6 +2722,110 @@ GKOC_DECL_PAR_FACTORIZATION(double, f64, int64_t, i64)
 GKOC_DECL_PAR_FACTORIZATION(float, f32, int32_t, i32)
 GKOC_DECL_PAR_FACTORIZATION(float, f32, int64_t, i64)
 
+/* ------------------------------------- ParIlut / ParIct (factorization::ParIlut / ParIct)
+ * Threshold ILU / IC by fixed-point sweeps (Anzt, Chow, Dongarra 2018): a factor that chooses its own pattern by
+ * magnitude with a bounded amount of fill.  Specified bit for bit, like ParIlu / ParIc; every multiply, subtract
+ * and divide is a separate operation in T.  Rows sorted by column everywhere.
+ * ParIlut.  The factor is ONE combined matrix M: strictly-lower entries are L without its unit diagonal, the
+ *   diagonal and the upper entries are U, every diagonal is stored - the form of par_ilu_sweeps and of the split.
+ *   A' = the prepared matrix (sorted, every diagonal stored), M_0 = A', keep_L = max(1, floor(fill_in_limit *
+ *   number of strictly-lower entries of A')), keep_U likewise for the strictly-upper ones.  For t = 1 ..
+ *   iterations:
+ *   1. pattern: P = pattern(L U) + pattern(A'), L with its unit diagonal; P contains the pattern of M.  Made by
+ *      gkoc_csr_spgemm_count / _expand with D = A', gkoc_sort_row_major, gkoc_sum_duplicates_*,
+ *      gkoc_convert_idxs_to_ptrs; only the pattern is kept.
+ *   2. candidate values (candidate_values), for every (i, j) of P: m_ij if M stores (i, j); otherwise s = a'_ij,
+ *      or +0 where A' stores none; for every column k stored in row i of M, ascending, with k < min(i, j) and
+ *      (k, j) stored in M: s = s - m_ik * m_kj; the value is s / m_jj for j < i and s otherwise.
+ *      a_P = A' gathered onto P (gather), +0 where A' has no entry.
+ *   3. one sweep on P (par_ilu_sweeps_from, iterations = 1) with v^0 = the values of step 2 and a = a_P.
+ *   4. thresholds (threshold_select).  Values are ordered by u(v) = the bit pattern of |v| (sign bit cleared)
+ *      read as an unsigned integer: -0 is 0, NaN ranks above inf.  For the c strictly-lower entries of P the
+ *      threshold is +0 if c <= keep_L, otherwise the non-negative value whose u has rank c - keep_L, 0-based and
+ *      ascending, among them.  The strictly-upper entries likewise with keep_U.
+ *   5. filter (keep_mask): the diagonal is kept, an off-diagonal entry iff u(v) >= u(threshold of its part).
+ *      Ties at the threshold are all kept, so a part may end with more than `keep` entries.  P' = the kept
+ *      pattern, made from the mask by gkoc_convert_ptrs_to_idxs, gkoc_remove_zeros_* and
+ *      gkoc_convert_idxs_to_ptrs; v' = v gathered onto P', a' = A' gathered onto P'.
+ *   6. one sweep on P' with v^0 = v' and a = a'.  The result is M_t.
+ *   L and U are the split of the last M (gkoc_factorization_initialize_l_u_*).
+ * ParIct.  The same loop on the lower triangle.  L_0 = the lower triangle of A' with the square root taken on the
+ *   diagonal (gkoc_factorization_initialize_l_* with diag_sqrt), the diagonal LAST in every row.  P = the lower
+ *   triangle of pattern(L L^T) + the lower pattern of A'.  Candidate (i, j), j < i, not stored in L: s = a'_ij or
+ *   +0; for k ascending, k < j, with (i, k) and (j, k) stored in L: s = s - l_ik * l_jk; the value is s / l_jj.
+ *   The sweeps are par_ic_sweeps_from with a = the lower triangle of A' (diagonal as it is) gathered onto the
+ *   pattern.  One threshold, over the strictly-lower entries, with keep_L; the diagonal is always kept.
+ * Selection is always exact (DEPARTURE from Ginkgo, whose default samples: approximate_select and
+ * deterministic_sample of the classes are accepted without effect).  Consequences pinned by the tests: with
+ * fill_in_limit 1 and values without ties the pattern falls back onto that of A'; on an arrow matrix with its hub
+ * first and a limit that drops nothing, the pattern is full after one iteration and the factors are the exact ILU
+ * (IC) factors on the full pattern, bit for bit, from the 4th iteration on (8 x 8, the case of the tests).  Pivots
+ * are not checked, and ParIct can break down where IC(0) does not (27-point stencil from 5^3 points on: L_0 keeps
+ * the unscaled off-diagonals of A', and the second sweep takes roots of negative numbers; docs/KERNELS.md 43).
+ *
+ * par_ilu_sweeps_from / par_ic_sweeps_from: par_ilu_sweeps / par_ic_sweeps (above) with the iterate v^0 that
+ *   sweep 1 reads for OTHER rows given apart from a_vals, from which every row starts.  The same checks, ping-pong
+ *   and changed_dev; v0_vals may be a_vals (then it IS the plain entry, bit for bit) and otherwise overlaps
+ *   neither work nor out_vals.
+ * gather: out[p] = src(i, j) for every position p = (i, j) of the sorted pattern (p_row_ptrs, p_col_idxs), +0
+ *   where the sorted src stores none.  Rows may be empty and need no diagonal.
+ * candidate_values (ilut: combined M; ict: lower-triangular L): step 2.  Pattern, A' and the factor are const;
+ *   out_vals (p_nnz values) is the one output.
+ * threshold_select: step 4 for part 0 (strictly lower) or 1 (strictly upper) of (row_ptrs, col_idxs, vals) with
+ *   keep >= 1.  *threshold_dev is written on the device and the entry does NOT synchronise: nothing is read back.
+ *   work: gkoc_par_ilut_select_workspace_bytes() bytes, 8-byte aligned, opaque, zeroed by the call.  Because it
+ *   reads nothing back, this entry checks its host arguments only; the structure is the caller's, who has had it
+ *   checked by candidate_values, gather or keep_mask.
+ * keep_mask: step 5.  mask[p] = 1 for a kept entry and +0 for a dropped one, as values of T, so that
+ *   gkoc_remove_zeros_* compacts the triplets.  Both thresholds are read from device memory.  thr_upper_dev NULL
+ *   means a lower-triangular factor: an entry right of the diagonal gets 0.  The diagonal gets 1 whatever its
+ *   value.
+ * GKOC_E_INVALID before any kernel touches a value buffer: negative sizes, null pointers, row pointers that do
+ * not ascend from 0 to nnz, a column outside the matrix (all entries but threshold_select, see there);
+ * candidate_values also: a row of the pattern or of the factor without a stored diagonal, a pattern that does not
+ * contain the factor's, for ict a row (of either) whose last entry is not its diagonal; threshold_select: keep < 1,
+ * part other than 0 / 1, a work buffer that is too small.  n_rows == 0 is GKOC_OK (threshold_select writes +0).
+ * Set-up calls: gather, candidate_values and keep_mask take scratch from the arena and synchronise the stream
+ * for their checks.  No entry writes an index array; integer counters and the select's tables live in `work`.
+ * Kernels: one group of lanes per row, lane = position, rows spread over the grid, longer rows streamed in
+ * rounds; candidate_values picks 16 / 32 / 64 lanes from the longest row at gkoc_factorization_row_limits.  No
+ * length cap, no serial path, every output written by one lane, no atomics on values.  threshold_select is a
+ * radix select over u(v), most significant 8 bits first (8 passes for f64, 4 for f32): per pass one streaming
+ * read with a 256-bin table per workgroup in LDS merged by integer atomics, and a single-workgroup kernel that
+ * narrows prefix and rank; passes are separated by kernel boundaries, no kernel waits for another workgroup. */
+size_t gkoc_par_ilut_select_workspace_bytes(void);
+#define GKOC_DECL_PAR_ILUT(T, TN, I, IN)                                                                     \
+    int gkoc_par_ilu_sweeps_from_##TN##_##IN(gkoc_stream_t s, int64_t n_rows, int64_t nnz,                   \
+                                             const I* row_ptrs, const I* col_idxs, const T* a_vals,          \
+                                             const T* v0_vals, int64_t iterations, T* work, T* out_vals,     \
+                                             uint64_t* changed_dev);                                         \
+    int gkoc_par_ic_sweeps_from_##TN##_##IN(gkoc_stream_t s, int64_t n_rows, int64_t nnz,                    \
+                                            const I* row_ptrs, const I* col_idxs, const T* a_vals,           \
+                                            const T* v0_vals, int64_t iterations, T* work, T* out_vals,      \
+                                            uint64_t* changed_dev);                                          \
+    int gkoc_par_ilut_gather_##TN##_##IN(gkoc_stream_t s, int64_t n_rows, int64_t p_nnz,                     \
+                                         const I* p_row_ptrs, const I* p_col_idxs, int64_t src_nnz,          \
+                                         const I* src_row_ptrs, const I* src_col_idxs, const T* src_vals,    \
+                                         T* out_vals);                                                       \
+    int gkoc_par_ilut_candidate_values_##TN##_##IN(                                                          \
+        gkoc_stream_t s, int64_t n_rows, int64_t p_nnz, const I* p_row_ptrs, const I* p_col_idxs,            \
+        int64_t a_nnz, const I* a_row_ptrs, const I* a_col_idxs, const T* a_vals, int64_t m_nnz,             \
+        const I* m_row_ptrs, const I* m_col_idxs, const T* m_vals, T* out_vals);                             \
+    int gkoc_par_ict_candidate_values_##TN##_##IN(                                                           \
+        gkoc_stream_t s, int64_t n_rows, int64_t p_nnz, const I* p_row_ptrs, const I* p_col_idxs,            \
+        int64_t a_nnz, const I* a_row_ptrs, const I* a_col_idxs, const T* a_vals, int64_t l_nnz,             \
+        const I* l_row_ptrs, const I* l_col_idxs, const T* l_vals, T* out_vals);                             \
+    int gkoc_par_ilut_threshold_select_##TN##_##IN(gkoc_stream_t s, int64_t n_rows, const I* row_ptrs,       \
+                                                   const I* col_idxs, const T* vals, int part, int64_t keep, \
+                                                   void* work, size_t work_bytes, T* threshold_dev);         \
+    int gkoc_par_ilut_keep_mask_##TN##_##IN(gkoc_stream_t s, int64_t n_rows, int64_t nnz,                    \
+                                            const I* row_ptrs, const I* col_idxs, const T* vals,             \
+                                            const T* thr_lower_dev, const T* thr_upper_dev, T* mask);
+GKOC_DECL_PAR_ILUT(double, f64, int32_t, i32)
+GKOC_DECL_PAR_ILUT(double, f64, int64_t, i64)
+GKOC_DECL_PAR_ILUT(float, f32, int32_t, i32)
+GKOC_DECL_PAR_ILUT(float, f32, int64_t, i64)
+
 /* ------------------------------------- triangular ISAI (preconditioner::LowerIsai / UpperIsai)
  * isai::generate_tri_inverse (reference/preconditioner/isai_kernels.cpp): the incomplete sparse approximate
  * inverse W of a triangular matrix A on a given pattern, (W A)(i, S_i) = e_i(S_i) for every row i, S_i = the

@@ -4,6 +4,12 @@ time of ParIc / ParIlu at 1, 3 and 5 sweeps, one sweep next to one CSR SpMV of t
 iterations to 1e-10 with LowerIsai on each IC factor.  f64 / int32.  (development / measurement tool)
 
     python tools/par_factorization_bench.py [grid ...]       default: 64 128
+    python tools/par_factorization_bench.py --threshold [grid ...]      default: 64
+
+--threshold prints four rows instead: ParIc / ParIlu (5 sweeps) and ParIct / ParIlut (5 iterations,
+fill_in_limit 2.0) with the generate time, the stored entries of the factors, and the iterations to 1e-10 of
+CG with Ic + LowerIsai resp. Gmres with Ilu + LowerIsai / UpperIsai ("no convergence" where the solver does not
+get there, e.g. with a factor that holds NaN).
 
 generate() is timed as a whole with a host clock around a second, synchronised call: preparation (copy,
 diagonal check), factorization and split.  One sweep is the difference of the raw entry at 11 sweeps and at 1
@@ -21,7 +27,8 @@ import torch
 import ginkgo_amd as g
 from ginkgo_amd._lib import call
 
-grids = [int(a) for a in sys.argv[1:] if not a.startswith("--")] or [64, 128]
+THRESHOLD = "--threshold" in sys.argv
+grids = [int(a) for a in sys.argv[1:] if not a.startswith("--")] or ([64] if THRESHOLD else [64, 128])
 ex = g.Cdna4Executor.create(0)
 REPS = 5
 
@@ -90,8 +97,60 @@ def sweep_bytes(m, lower_only):
     return 3 * 8 * nnz + 4 * nnz + 4 * (n + 1) + (0 if lower_only else 4 * n)
 
 
+def solver_iterations(solver_cls, a, m):
+    """iterations to 1e-10 with the generated preconditioner m, or None"""
+    s = (solver_cls.build()
+         .with_criteria(g.stop.Iteration.build().with_max_iters(2000),
+                        g.stop.ResidualNorm.build().with_reduction_factor(1e-10))
+         .with_generated_preconditioner(m).on(ex).generate(a))
+    x = g.Dense.from_numpy(ex, np.zeros(a.size[0]))
+    s.apply(g.Dense.from_numpy(ex, np.ones(a.size[0])), x)
+    return s.num_iterations if s.has_converged else None
+
+
+def threshold_rows(a):
+    """ParIc / ParIct and ParIlu / ParIlut side by side"""
+    fz = g.factorization
+    rows = (("ParIc  (5 sweeps)", lambda: fz.ParIc.build().with_iterations(5), True),
+            ("ParIct (5 iterations, limit 2.0)", lambda: fz.ParIct.build().with_iterations(5).with_fill_in_limit(2.0),
+             True),
+            ("ParIlu (5 sweeps)", lambda: fz.ParIlu.build().with_iterations(5), False),
+            ("ParIlut (5 iterations, limit 2.0)",
+             lambda: fz.ParIlut.build().with_iterations(5).with_fill_in_limit(2.0), False))
+    for label, factory, lower_only in rows:
+        try:
+            fact, t = best(lambda: factory().on(ex).generate(a), reps=2)
+        except g.GkoError as err:
+            # ParIct on this stencil: NaN pivots rank above every number, are all kept as ties, and the pattern
+            # of L L^T outgrows the device
+            print(f"  factorization.{label}: generate FAILED ({str(err).splitlines()[-1][-90:]})", flush=True)
+            continue
+        if lower_only:
+            stored = fact.get_l_factor().get_num_stored_elements()
+            finite = bool(torch.isfinite(fact.get_l_factor().values).all().item())
+            m = g.Ic.build().with_l_solver(g.LowerIsai.build()).on(ex).generate(fact)
+            its, solver = solver_iterations(g.Cg, a, m), "CG + Ic + LowerIsai"
+        else:
+            stored = fact.get_l_factor().get_num_stored_elements() + fact.get_u_factor().get_num_stored_elements()
+            finite = bool(torch.isfinite(fact.get_l_factor().values).all().item()
+                          and torch.isfinite(fact.get_u_factor().values).all().item())
+            m = (g.Ilu.build().with_l_solver(g.LowerIsai.build()).with_u_solver(g.UpperIsai.build())
+                 .on(ex).generate(fact))
+            its, solver = solver_iterations(g.Gmres, a, m), "Gmres + Ilu + ISAI"
+        print(f"  factorization.{label}: generate {t*1e3:9.2f} ms, {stored} stored entries"
+              f"{'' if finite else ' (NOT finite)'};  {solver} "
+              f"{'no convergence' if its is None else '%d iterations' % its}", flush=True)
+        del fact, m
+
+
 for grid in grids:
     a = g.stencil_csr(ex, 3, grid)
+    if THRESHOLD:
+        print(f"L27({grid}^3): n={a.size[0]} nnz={a.get_num_stored_elements()}", flush=True)
+        threshold_rows(a)
+        del a
+        torch.cuda.synchronize()
+        continue
     n, nnz = a.size[0], a.get_num_stored_elements()
     t_spmv = apply_us(a, 50)
     print(f"L27({grid}^3): n={n} nnz={nnz}  CSR SpMV {t_spmv:.1f} us", flush=True)
