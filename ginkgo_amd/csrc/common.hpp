@@ -77,10 +77,10 @@ int scratch_free(hipStream_t st, void* ptr);
 // reduction (the word is 0 again when such a kernel ends; launches of one stream do not overlap).
 int stream_ticket(hipStream_t st, unsigned** word);
 
-// csr::spmv's memory of which segments of a matrix hold very long rows (csr_spmv.hip): forgotten when the
+// csr::spmv's memory of which segments of a matrix hold very long rows (csr_structure.hip): forgotten when the
 // row-pointer array is freed
 void csr_long_rows_forget(const void* ptr);
-// csr::spmv's cached column-offset plans (csr_offsets.hpp, csr_spmv.hip), keyed by a matrix' two index arrays:
+// csr::spmv's cached column-offset plans (csr_offsets.hpp, csr_structure.hip), keyed by a matrix' two index arrays:
 // every entry of the library that frees or WRITES an index array of a CSR matrix says so.  An atomic load
 // while no plan exists.
 extern std::atomic<int> g_csr_offsets_cached;

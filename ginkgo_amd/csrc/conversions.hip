@@ -311,7 +311,7 @@ __global__ __launch_bounds__(256) void sellp_fill_in_dense_kernel(int64_t n_rows
 
 // ------------------------------------------------------------ diagonals
 // extract_diagonal: the first entry of row r with column r (ell / sellp: the reference breaks at
-// the first match; csr: csr_spmv.hip); coo: every entry with row == column (one per row in a valid
+// the first match; csr: csr_rows.hip); coo: every entry with row == column (one per row in a valid
 // matrix)
 template <typename T, typename I>
 __global__ __launch_bounds__(256) void ell_extract_diagonal_kernel(int64_t n, int64_t ell_k, int64_t stride,

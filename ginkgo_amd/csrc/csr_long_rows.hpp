@@ -12,7 +12,7 @@
 //   * the segments that contain a row longer than GKOC_CSR_LONG_ROW are FLAGGED (one bit per 64-row segment
 //     + a list), once per matrix: csr_long_row_scan_kernel reads the row pointers (n x 4 bytes, 15 us at
 //     256^3) the first time a (row_ptrs, n_rows) pair is seen; the answer - usually "none" - is cached by
-//     the launcher (csr_spmv.hip), so a regular matrix pays one scan in its first product and nothing after;
+//     csr_structure.hip (csr_long_info), so a regular matrix pays one scan in its first product and nothing after;
 //   * the row-segment kernel leaves flagged segments out (a wave owns one or two segments: it shortens
 //     its range at its start - the only change to that kernel);
 //   * csr_flagged_segments_kernel does them: PARTS = 64 workgroups per flagged segment.  Workgroup p takes the
@@ -188,15 +188,5 @@ __global__ __launch_bounds__(64) void csr_long_rows_fold_kernel(
 }
 
 #endif  // __HIPCC__
-
-// what the launcher remembers about a matrix (csr_spmv.hip)
-struct csr_long_info {
-    int64_t count = 0;                   // flagged segments (0: none - the common case)
-    uint32_t* bits = nullptr;            // device: one bit per segment
-    unsigned long long* list = nullptr;  // device: [count, segment indices ...]
-    int64_t nnz = -1;                    // row_ptrs[n_rows] when the matrix was looked at (-1: unknown)
-    uint64_t seq = 0;                    // order of arrival in the launcher's cache (the oldest entry makes room)
-    void* partial = nullptr;             // device: chunk sums, THE CALLING STREAM's buffer (filled in per call)
-};
 
 }  // namespace gkoc

@@ -20,195 +20,21 @@
 //
 // Algorithmic HBM bytes: nnz*(sizeof(T)+sizeof(I)) + (n+1)*sizeof(I)
 //                        + n_cols*sizeof(T) (b once) + n*sizeof(T) (c).
+//
+// What the launchers know about a matrix from earlier products - its long rows, its column-offset plan - is kept
+// by csr_structure.hip; a product holds a csr_structure_lease while it enqueues kernels that read it.
 #include <algorithm>
-#include <atomic>
-#include <cstring>
-#include <map>
-#include <mutex>
-#include <tuple>
 #include <type_traits>
-#include <vector>
-
-#include <rocprim/rocprim.hpp>
 
 #include "common.hpp"
 #include "csr_long_rows.hpp"
 #include "csr_offsets.hpp"
 #include "csr_spmv_multi.hpp"
 #include "csr_spmv_pipe.hpp"
+#include "csr_structure.hpp"
 #include "fused.hpp"
 
 namespace gkoc {
-namespace {
-
-// ---- which 64-row segments of a matrix hold a row beyond GKOC_CSR_LONG_ROW (csr_long_rows.hpp) --------
-// Found by one scan of the row pointers the first time a (device, row_ptrs, n_rows) is multiplied, kept
-// here (flags and list read-only from then on; the chunk sums of a product go to a buffer per (matrix, stream),
-// so products of one matrix on several streams share nothing that is written); gkoc_free forgets the entries of
-// a pointer that goes away (csr_long_rows_forget).  A few dozen matrices at most: the OLDEST entry makes room,
-// after a device synchronisation (a product on any stream may still read its flags).  The first product of a
-// matrix therefore synchronises its stream once (the scan's answer is needed on the host) - documented in
-// gko_cdna4.h; inside a stream capture the matrix is multiplied by the row-segment kernel alone.
-std::mutex g_long_mtx;
-struct long_entry {
-    csr_long_info info;
-    // one buffer of chunk sums per stream that has multiplied this matrix (count x 8 x 64 values of 8 bytes)
-    std::vector<std::pair<hipStream_t, void*>> partials;
-};
-std::map<std::tuple<int, const void*, int64_t>, long_entry> g_long_cache;
-std::atomic<int> g_long_cached{0};
-constexpr size_t long_cache_cap = 128;
-constexpr int64_t long_list_cap = 4096;      // more flagged segments than this: the matrix has no "few long rows"
-
-thread_local bool t_long_releasing = false;      // gkoc_free below comes back through csr_long_rows_forget
-
-void long_info_release(long_entry& en)
-{
-    csr_long_info& f = en.info;
-    t_long_releasing = true;
-    if (f.bits) (void)gkoc_free(f.bits);
-    if (f.list) (void)gkoc_free(f.list);
-    for (auto& sp : en.partials) (void)gkoc_free(sp.second);
-    en.partials.clear();
-    f = csr_long_info{};
-    t_long_releasing = false;
-}
-
-bool stream_is_capturing(hipStream_t st)
-{
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
-        (void)hipGetLastError();
-        return true;
-    }
-    return false;
-}
-
-// the calling stream's buffer of chunk sums (allocated the first time the stream multiplies the matrix; not
-// inside a stream capture: the product is then left to the row-segment kernel alone, which handles any row)
-void long_partial_for(long_entry& en, hipStream_t st, csr_long_info* out)
-{
-    *out = en.info;
-    if (en.info.count <= 0) return;
-    for (auto& sp : en.partials) {
-        if (sp.first == st) {
-            out->partial = sp.second;
-            return;
-        }
-    }
-    void* p = nullptr;
-    if (stream_is_capturing(st) ||
-        gkoc_malloc(&p, size_t(en.info.count) * LONG_MAX_PER_SEG * LONG_PARTS * 8) != GKOC_OK) {
-        (void)hipGetLastError();
-        *out = csr_long_info{};
-        out->nnz = en.info.nnz;
-        return;
-    }
-    en.partials.emplace_back(st, p);
-    out->partial = p;
-}
-
-template <typename T, typename I>
-int long_info_of(gkoc_stream_t s, int64_t n_rows, const I* row_ptrs, csr_long_info* out)
-{
-    int dev = 0;
-    GKOC_HIP(hipGetDevice(&dev));
-    const auto key = std::make_tuple(dev, static_cast<const void*>(row_ptrs), n_rows);
-    std::lock_guard<std::mutex> g(g_long_mtx);
-    auto it = g_long_cache.find(key);
-    if (it != g_long_cache.end()) {
-        long_partial_for(it->second, as_stream(s), out);
-        return GKOC_OK;
-    }
-    // a stream that is being captured into a hipGraph cannot be synchronised: a matrix first seen there is
-    // multiplied by the row-segment kernel alone (correct for any row), and looked at on its next product
-    if (stream_is_capturing(as_stream(s))) {
-        *out = csr_long_info{};
-        return GKOC_OK;
-    }
-    if (g_long_cache.size() >= long_cache_cap) {
-        auto oldest = g_long_cache.begin();
-        for (auto jt = g_long_cache.begin(); jt != g_long_cache.end(); ++jt) {
-            if (jt->second.info.seq < oldest->second.info.seq) oldest = jt;
-        }
-        if (oldest->second.info.count > 0) GKOC_HIP(hipDeviceSynchronize());   // (a product in flight may use it)
-        long_info_release(oldest->second);
-        g_long_cache.erase(oldest);
-    }
-    csr_long_info f;
-    static uint64_t arrivals = 0;
-    f.seq = ++arrivals;
-    const int64_t n_seg = ceildiv(n_rows, int64_t(64));
-    const size_t bit_bytes = size_t(ceildiv(n_seg, int64_t(32))) * 4;
-    const size_t list_bytes = size_t(1 + long_list_cap) * 8;
-    void *bits = nullptr, *list = nullptr;
-    GKOC_TRY(gkoc_malloc(&bits, bit_bytes));
-    if (gkoc_malloc(&list, list_bytes) != GKOC_OK) {
-        t_long_releasing = true;
-        (void)gkoc_free(bits);
-        t_long_releasing = false;
-        return GKOC_E_INVALID;
-    }
-    hipStream_t st = as_stream(s);
-    unsigned long long count = 0;
-    I nnz_dev = I(0);
-    bool ok = hipMemsetAsync(bits, 0, bit_bytes, st) == hipSuccess && hipMemsetAsync(list, 0, 8, st) == hipSuccess;
-    if (ok) {
-        csr_long_row_scan_kernel<I><<<dim3(unsigned(ceildiv(n_seg, int64_t(4)))), dim3(256), 0, st>>>(
-            n_rows, row_ptrs, static_cast<uint32_t*>(bits), static_cast<unsigned long long*>(list), long_list_cap);
-        // (the number of stored entries comes with the same wait: the launcher sizes a wave's share by it)
-        ok = hipGetLastError() == hipSuccess &&
-             hipMemcpyAsync(&count, list, 8, hipMemcpyDeviceToHost, st) == hipSuccess &&
-             hipMemcpyAsync(&nnz_dev, row_ptrs + n_rows, sizeof(I), hipMemcpyDeviceToHost, st) == hipSuccess &&
-             hipStreamSynchronize(st) == hipSuccess;
-    }
-    if (ok) f.nnz = int64_t(nnz_dev);
-    if (!ok || count == 0 || int64_t(count) > long_list_cap) {
-        // none (the common case), or so many that "a few long rows" is not what this matrix has: the
-        // row-segment kernel does everything, as before
-        (void)hipGetLastError();
-        t_long_releasing = true;
-        (void)gkoc_free(bits);
-        (void)gkoc_free(list);
-        t_long_releasing = false;
-    } else {
-        f.count = int64_t(count);
-        f.bits = static_cast<uint32_t*>(bits);
-        f.list = static_cast<unsigned long long*>(list);
-    }
-    long_entry& en = g_long_cache[key];
-    en.info = f;
-    g_long_cached.store(int(g_long_cache.size()));
-    long_partial_for(en, st, out);
-    return GKOC_OK;
-}
-
-}  // namespace
-
-void csr_long_rows_forget(const void* ptr)
-{
-    if (ptr == nullptr || t_long_releasing || g_long_cached.load(std::memory_order_relaxed) == 0) return;
-    std::vector<long_entry> gone;
-    {
-        std::lock_guard<std::mutex> g(g_long_mtx);
-        for (auto it = g_long_cache.begin(); it != g_long_cache.end();) {
-            if (std::get<1>(it->first) == ptr) {
-                gone.push_back(it->second);
-                it = g_long_cache.erase(it);
-            } else {
-                ++it;
-            }
-        }
-        g_long_cached.store(int(g_long_cache.size()));
-    }
-    for (auto& en : gone) {
-        if (en.info.count > 0) (void)hipDeviceSynchronize();      // a product in flight may still use its buffers
-        long_info_release(en);
-    }
-}
-
-std::atomic<int> g_csr_offsets_cached{0};
-
 namespace {
 
 // ---- the launch plan of the row-segment kernels (csr_spmv_pipe3_kernel, csr_spmv_multi_kernel) -------------
@@ -366,268 +192,25 @@ int launch_csr_pair(gkoc_stream_t s, int64_t n_rows, const T* alpha, const I* ro
     return GKOC_OK;
 }
 
-// ---- cached per-segment column offsets (csr_offsets.hpp) ---------------------------------------------------
-// A derived, read-only description of (row_ptrs, col_idxs), keyed by (device, row_ptrs, col_idxs, n_rows), in
-// the style of the long-row cache above.  Only for index arrays that are live allocations of the library's own
-// allocator: their addresses cannot be reused without gkoc_free seeing them.  Built by the SECOND product on the
-// same arrays (a one-shot product never pays; GKOC_TUNE_CSR_OFFSETS = 1: by the first, 2: never), never inside a
-// stream capture (the product takes the row-segment kernel and the next one tries again).  Dropped by
-// csr_offsets_forget: gkoc_free, every C-ABI entry that writes an index array of a CSR matrix, gkoc_memcpy_h2d /
-// _d2d into one, gkoc_csr_structure_changed.  Lookup and launch happen under the mutex, so a plan cannot be
-// released between the two; its buffers are released after a device synchronisation.
-std::mutex g_off_mtx;
-struct offsets_plan {
-    int state = 0;                  // 0: seen once, 1: in use, 2: rejected (fewer than half of the segments eligible)
-    int64_t n_seg = 0, eligible = 0;
-    int max_d = 0;                  // the largest D of a segment: picks the product kernel's diagonal slots
-    int64_t n_classes = 0;          // distinct (table, masks) among the segments (csr_offsets.hpp)
-    int64_t nnz = 0;                // stored entries when the plan was built: sizes the product (offsets_nt_min_bytes)
-    int32_t* seg_class = nullptr;   // device: the class id of every segment
-    int32_t* cls_tab = nullptr;     // device: OFFS_TAB int32 per class
-    uint32_t* cls_mask = nullptr;   // device: 64 words per class, one per row of a segment
-    uint32_t* skip = nullptr;       // device: bit per segment the row-segment kernel leaves out (eligible | long-flagged)
-    bool with_long = false;         // skip holds the long-row flags too
-    int64_t bytes = 0, products = 0;
-    uint64_t seq = 0;
-    size_t rp_bytes = 0, ci_bytes = 0;      // the two allocations the plan describes (csr_offsets_forget)
-};
-using offsets_key = std::tuple<int, const void*, const void*, int64_t>;
-std::map<offsets_key, offsets_plan> g_off_cache;
-constexpr size_t offsets_cache_cap = 128;
-// at least this share of the segments must be eligible, in per cent (docs/KERNELS.md: measured on a stencil
-// whose every other segment is not)
-constexpr int64_t offsets_min_share = 50;
+// ---- the product through a column-offset plan (csr_offsets.hpp; the plan is csr_structure.hip's) -------------
+// The plan a one-column, unit-stride product of these arrays may use, or nullptr: double / float values aligned
+// for 16-byte loads and 32-bit indices.  Valid while the lease is held - to the last kernel that reads it.
+template <typename T, typename I>
+offsets_plan* offsets_plan_of(csr_structure_lease& lease, hipStream_t st, int64_t n_rows, int64_t n_cols,
+                              const I* row_ptrs, const I* col_idxs, const T* vals, const T* b,
+                              const csr_long_info& lng)
+{
+    if constexpr (std::is_same<I, int32_t>::value && (sizeof(T) == 8 || sizeof(T) == 4)) {
+        if (vals != nullptr && b != nullptr && reinterpret_cast<uintptr_t>(vals) % 16 == 0) {
+            return csr_offsets_plan_for(lease, st, n_rows, n_cols, row_ptrs, col_idxs, lng);
+        }
+    }
+    return nullptr;
+}
+
 // the MI355X's Infinity Cache, 256 MiB: a product that streams more than this per call cannot live in it, and its
 // value stream and result bypass it (measured on both sides of it: docs/KERNELS.md 36)
 constexpr int64_t offsets_nt_min_bytes = int64_t(256) << 20;
-
-// buffers of dropped plans that could not be released at once (inside a stream capture the device cannot be
-// synchronised): released with the next plan that goes.  Guarded by g_off_mtx.
-std::vector<void*> g_off_graveyard;
-
-// Only plans that HAVE buffers pay the synchronisation (a product in flight on any stream may still read them):
-// matrices that were multiplied through a plan, as with the long-row cache above.
-void offsets_release(std::vector<offsets_plan>& gone)
-{
-    std::vector<void*> bufs;
-    for (auto& pl : gone) {
-        for (void* b : {static_cast<void*>(pl.seg_class), static_cast<void*>(pl.cls_tab),
-                        static_cast<void*>(pl.cls_mask), static_cast<void*>(pl.skip)}) {
-            if (b) bufs.push_back(b);
-        }
-    }
-    if (bufs.empty()) return;
-    std::lock_guard<std::mutex> g(g_off_mtx);
-    g_off_graveyard.insert(g_off_graveyard.end(), bufs.begin(), bufs.end());
-    if (hipDeviceSynchronize() != hipSuccess) {
-        (void)hipGetLastError();      // (a capture is under way: they wait in the graveyard)
-        return;
-    }
-    for (void* b : g_off_graveyard) (void)arena_free(b);
-    g_off_graveyard.clear();
-}
-
-// scratch of the class search for n segments, in bytes, and where its parts lie
-struct class_scratch {
-    size_t hash, hash_sorted, ids, ids_sorted, leader, is_new, class_at, prim, prim_bytes, total;
-};
-class_scratch class_scratch_of(int64_t n)
-{
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    size_t sort_bytes = 0, scan_bytes = 0;
-    unsigned long long* k = nullptr;
-    uint32_t* v = nullptr;
-    (void)rocprim::radix_sort_pairs(nullptr, sort_bytes, k, k, v, v, size_t(n), 0, 64, hipStream_t(nullptr));
-    (void)rocprim::exclusive_scan(nullptr, scan_bytes, v, v, uint32_t(0), size_t(n), rocprim::plus<uint32_t>(),
-                                  hipStream_t(nullptr));
-    class_scratch c;
-    size_t at = 0;
-    auto part = [&](size_t bytes) {
-        const size_t here = at;
-        at += up(bytes);
-        return here;
-    };
-    c.hash = part(size_t(n) * 8);
-    c.hash_sorted = part(size_t(n) * 8);
-    c.ids = part(size_t(n) * 4);
-    c.ids_sorted = part(size_t(n) * 4);
-    c.leader = part(size_t(n) * 4);
-    c.is_new = part(size_t(n) * 4);
-    c.class_at = part(size_t(n) * 4);
-    c.prim_bytes = sort_bytes > scan_bytes ? sort_bytes : scan_bytes;
-    c.prim = part(c.prim_bytes);
-    c.total = at;
-    return c;
-}
-
-// The analysis.  One pass over the column indices gives the per-segment tables and the per-row masks; behind it,
-// on the same stream, the class search of csr_offsets.hpp (hash, stable sort of (hash, segment), compare with the
-// run's leader, scan).  The eligible count, the largest D and the number of classes come back with ONE stream
-// synchronisation.  An accepted plan is then compacted - a class id per segment, a table and 64 masks per class,
-// sized by the count - and the per-segment tables, the per-row masks and the scratch are freed behind a second,
-// short synchronisation (the compaction reads them): what a plan keeps is 4 n_seg + 388 n_classes bytes
-// (+ the skip bits), 1 MiB for the 27-point stencil 256^3 where tables and masks were 97 MiB.
-int offsets_build(hipStream_t st, int64_t n_rows, const int32_t* row_ptrs, const int32_t* col_idxs,
-                  const csr_long_info& lng, offsets_plan& pl)
-{
-    const int64_t n_seg = ceildiv(n_rows, int64_t(64));
-    const size_t tab_bytes = size_t(n_seg) * OFFS_TAB * 4, mask_bytes = size_t(n_rows) * 4;
-    const size_t skip_bytes = size_t(ceildiv(n_seg, int64_t(32))) * 4;
-    const size_t ids_bytes = size_t(n_seg) * 4;
-    const class_scratch cs = class_scratch_of(n_seg);
-    // (cut to its low bits only to provoke collisions: the tests of the compare-with-the-leader path)
-    const int64_t hash_bits = tune_value(GKOC_TUNE_CSR_OFFSETS_HASH_BITS);
-    const unsigned long long keep = (hash_bits < 0 || hash_bits >= 64) ? ~0ull : ((1ull << hash_bits) - 1ull);
-    void *tab = nullptr, *mask = nullptr, *skip = nullptr, *count_dev = nullptr, *ids = nullptr, *work = nullptr;
-    void *ctab = nullptr, *cmask = nullptr;
-    bool ok = n_seg > 0 && arena_malloc(&tab, tab_bytes, GKOC_MEM_INDICES) == GKOC_OK &&
-              arena_malloc(&mask, mask_bytes, GKOC_MEM_INDICES) == GKOC_OK &&
-              arena_malloc(&skip, skip_bytes, GKOC_MEM_INDICES) == GKOC_OK &&
-              arena_malloc(&ids, ids_bytes, GKOC_MEM_INDICES) == GKOC_OK &&
-              arena_malloc(&work, cs.total, GKOC_MEM_INDICES) == GKOC_OK &&
-              arena_malloc(&count_dev, 32, GKOC_MEM_VECTOR) == GKOC_OK;
-    char* w = static_cast<char*>(work);
-    auto at = [&](size_t off) { return static_cast<void*>(w + off); };
-    const dim3 seg_grid(unsigned(ceildiv(n_seg, int64_t(4)))), seg_block(256);
-    unsigned long long count[4] = {0, 0, 0, 0};
-    if (ok) {
-        const int32_t* tab_c = static_cast<const int32_t*>(tab);
-        const uint32_t* mask_c = static_cast<const uint32_t*>(mask);
-        csr_offsets_build_kernel<int32_t><<<seg_grid, seg_block, 0, st>>>(
-            n_rows, row_ptrs, col_idxs, static_cast<int32_t*>(tab), static_cast<uint32_t*>(mask));
-        csr_offsets_finish_kernel<<<dim3(1), dim3(1024), 0, st>>>(
-            n_seg, tab_c, lng.count > 0 ? lng.bits : nullptr, static_cast<uint32_t*>(skip),
-            static_cast<unsigned long long*>(count_dev));
-        csr_offsets_hash_kernel<<<seg_grid, seg_block, 0, st>>>(
-            n_rows, n_seg, tab_c, mask_c, keep, static_cast<unsigned long long*>(at(cs.hash)),
-            static_cast<uint32_t*>(at(cs.ids)));
-        size_t prim_bytes = cs.prim_bytes;
-        ok = hipGetLastError() == hipSuccess &&
-             rocprim::radix_sort_pairs(at(cs.prim), prim_bytes, static_cast<unsigned long long*>(at(cs.hash)),
-                                       static_cast<unsigned long long*>(at(cs.hash_sorted)),
-                                       static_cast<uint32_t*>(at(cs.ids)), static_cast<uint32_t*>(at(cs.ids_sorted)),
-                                       size_t(n_seg), 0, 64, st) == hipSuccess;
-        if (ok) {
-            csr_offsets_leader_kernel<<<seg_grid, seg_block, 0, st>>>(
-                n_rows, n_seg, tab_c, mask_c, static_cast<const unsigned long long*>(at(cs.hash_sorted)),
-                static_cast<const uint32_t*>(at(cs.ids_sorted)), static_cast<uint32_t*>(at(cs.leader)),
-                static_cast<uint32_t*>(at(cs.is_new)));
-            prim_bytes = cs.prim_bytes;
-            ok = hipGetLastError() == hipSuccess &&
-                 rocprim::exclusive_scan(at(cs.prim), prim_bytes, static_cast<uint32_t*>(at(cs.is_new)),
-                                         static_cast<uint32_t*>(at(cs.class_at)), uint32_t(0), size_t(n_seg),
-                                         rocprim::plus<uint32_t>(), st) == hipSuccess;
-        }
-        if (ok) {
-            csr_offsets_class_count_kernel<<<dim3(1), dim3(1), 0, st>>>(
-                n_seg, static_cast<const uint32_t*>(at(cs.is_new)), static_cast<const uint32_t*>(at(cs.class_at)),
-                n_rows, row_ptrs, static_cast<unsigned long long*>(count_dev));
-            ok = hipGetLastError() == hipSuccess;
-        }
-        // (whatever was enqueued has run when the buffers are freed below, also after an error)
-        const bool copied = ok && hipMemcpyAsync(count, count_dev, 32, hipMemcpyDeviceToHost, st) == hipSuccess;
-        ok = hipStreamSynchronize(st) == hipSuccess && copied;
-    }
-    (void)hipGetLastError();
-    if (count_dev) (void)arena_free(count_dev);
-    pl.n_seg = n_seg;
-    pl.eligible = ok ? int64_t(count[0]) : 0;
-    pl.max_d = ok ? int(count[1]) : 0;
-    const int64_t n_classes = ok ? int64_t(count[2]) : 0;
-    const bool accepted = ok && pl.eligible > 0 && pl.eligible * 100 >= n_seg * offsets_min_share;
-    bool compacted = false;
-    if (accepted && n_classes >= 1 && n_classes <= n_seg &&
-        arena_malloc(&ctab, size_t(n_classes) * OFFS_TAB * 4, GKOC_MEM_INDICES) == GKOC_OK &&
-        arena_malloc(&cmask, size_t(n_classes) * 64 * 4, GKOC_MEM_INDICES) == GKOC_OK) {
-        csr_offsets_compact_kernel<<<seg_grid, seg_block, 0, st>>>(
-            n_rows, n_seg, static_cast<const int32_t*>(tab), static_cast<const uint32_t*>(mask),
-            static_cast<const uint32_t*>(at(cs.ids_sorted)), static_cast<const uint32_t*>(at(cs.leader)),
-            static_cast<const uint32_t*>(at(cs.is_new)), static_cast<const uint32_t*>(at(cs.class_at)),
-            static_cast<int32_t*>(ids), static_cast<int32_t*>(ctab), static_cast<uint32_t*>(cmask));
-        const bool launched = hipGetLastError() == hipSuccess;
-        compacted = hipStreamSynchronize(st) == hipSuccess && launched;
-        (void)hipGetLastError();
-    }
-    if (tab) (void)arena_free(tab);
-    if (mask) (void)arena_free(mask);
-    if (work) (void)arena_free(work);
-    if (!compacted) {
-        for (void* b : {skip, ids, ctab, cmask}) {
-            if (b) (void)arena_free(b);
-        }
-        // too few eligible segments: rejected for good; an analysis that FAILED (no memory, a stream error) is
-        // tried again by the next product
-        if (ok && !accepted) pl.state = 2;
-        return GKOC_OK;
-    }
-    pl.state = 1;
-    pl.n_classes = n_classes;
-    pl.nnz = int64_t(count[3]);
-    pl.seg_class = static_cast<int32_t*>(ids);
-    pl.cls_tab = static_cast<int32_t*>(ctab);
-    pl.cls_mask = static_cast<uint32_t*>(cmask);
-    pl.bytes = int64_t(ids_bytes) + n_classes * int64_t((OFFS_TAB + 64) * 4);
-    if (pl.eligible == n_seg) {
-        (void)arena_free(skip);        // every segment is this kernel's: the row-segment kernel is not launched
-    } else {
-        pl.skip = static_cast<uint32_t*>(skip);
-        pl.with_long = lng.count > 0;
-        pl.bytes += int64_t(skip_bytes);
-    }
-    return GKOC_OK;
-}
-
-// plans that made room in the cache while the mutex was held: released when the holder is destroyed, which the
-// callers arrange to happen AFTER their lock is gone (declared in front of it)
-struct evicted_plans {
-    std::vector<offsets_plan> v;
-    ~evicted_plans() { offsets_release(v); }
-};
-
-// The plan this product may use, or nullptr.  The caller holds g_off_mtx.
-offsets_plan* offsets_plan_for(hipStream_t st, int64_t n_rows, int64_t n_cols, const int32_t* row_ptrs,
-                               const int32_t* col_idxs, const csr_long_info& lng, std::vector<offsets_plan>* evicted)
-{
-    const int64_t mode = tune_value(GKOC_TUNE_CSR_OFFSETS);
-    if (mode == 2 || row_ptrs == nullptr || col_idxs == nullptr || n_cols < 1 ||
-        n_rows >= (int64_t(1) << 31) - 64 || n_cols >= (int64_t(1) << 31)) {
-        return nullptr;
-    }
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    const offsets_key key{dev, row_ptrs, col_idxs, n_rows};
-    auto it = g_off_cache.find(key);
-    if (it == g_off_cache.end()) {
-        const size_t rp_bytes = arena_allocation_bytes(row_ptrs), ci_bytes = arena_allocation_bytes(col_idxs);
-        if (rp_bytes == 0 || ci_bytes == 0) return nullptr;
-        if (g_off_cache.size() >= offsets_cache_cap) {
-            auto oldest = g_off_cache.begin();
-            for (auto jt = g_off_cache.begin(); jt != g_off_cache.end(); ++jt) {
-                if (jt->second.seq < oldest->second.seq) oldest = jt;
-            }
-            evicted->push_back(oldest->second);      // (released by the caller once the mutex is free)
-            g_off_cache.erase(oldest);
-        }
-        static uint64_t arrivals = 0;
-        offsets_plan fresh;
-        fresh.seq = ++arrivals;
-        fresh.rp_bytes = rp_bytes;
-        fresh.ci_bytes = ci_bytes;
-        it = g_off_cache.emplace(key, fresh).first;
-        g_csr_offsets_cached.store(int(g_off_cache.size()));
-        if (mode != 1) return nullptr;      // the first product of these arrays
-    }
-    offsets_plan& pl = it->second;
-    if (pl.state == 0) {
-        if (stream_is_capturing(st)) return nullptr;
-        (void)offsets_build(st, n_rows, row_ptrs, col_idxs, lng, pl);
-    }
-    if (pl.state != 1) return nullptr;
-    // the row-segment kernel beside this one must leave out what the plan's skip bits say, and somebody must
-    // do the long-flagged segments: only with the flags the plan was built with
-    if (pl.skip != nullptr && pl.with_long != (lng.count > 0)) return nullptr;
-    return &pl;
-}
 
 // the product of the plan's segments: the kernel with the fewest diagonal slots (8, 16, 28 or 32) that holds the
 // plan's largest D - its value stream, its stage and its x loads are sized by the slot count (one straight-line
@@ -635,34 +218,27 @@ offsets_plan* offsets_plan_for(hipStream_t st, int64_t n_rows, int64_t n_cols, c
 // stencil's.
 // The price: in a plan that has wide segments the narrow ones issue dead x loads - 5 % on a matrix with one
 // segment of 9 offsets in eight of 3 under the 32-slot kernel, nothing with one in two (docs/KERNELS.md 36).
-template <typename T, bool ADV, bool DOT, int ND>
-void launch_offsets_kernel_nd(hipStream_t st, const offsets_plan& pl, const segment_plan& p, int64_t n_rows,
-                              int64_t n_cols, const T* alpha, const int32_t* row_ptrs, const T* vals, const T* b,
-                              const T* beta, T* c, T* dot_partial)
-{
-    const dim3 grid(static_cast<unsigned>(p.n_waves)), block(64);
-    // values, x, c and the row pointers: what a product streams.  Above the Infinity Cache's size the values and
-    // c go non-temporally (csr_offsets.hpp NT), below it repeated products are served from that cache
-    const int64_t product_bytes = pl.nnz * int64_t(sizeof(T)) + (n_rows + n_cols) * int64_t(sizeof(T)) + n_rows * 4;
-    if (product_bytes > offsets_nt_min_bytes) {
-        csr_spmv_pipe3_kernel_offsets<T, ADV, DOT, ND, true><<<grid, block, 0, st>>>(
-            int32_t(n_rows), int32_t(n_cols), p.n_seg, p.spw, row_ptrs, vals, b, c, alpha, beta, pl.seg_class,
-            pl.cls_tab, pl.cls_mask, dot_partial);
-    } else {
-        csr_spmv_pipe3_kernel_offsets<T, ADV, DOT, ND, false><<<grid, block, 0, st>>>(
-            int32_t(n_rows), int32_t(n_cols), p.n_seg, p.spw, row_ptrs, vals, b, c, alpha, beta, pl.seg_class,
-            pl.cls_tab, pl.cls_mask, dot_partial);
-    }
-}
-
 template <typename T, bool ADV, bool DOT>
 void launch_offsets_kernel(hipStream_t st, const offsets_plan& pl, const segment_plan& p, int64_t n_rows,
                            int64_t n_cols, const T* alpha, const int32_t* row_ptrs, const T* vals, const T* b,
                            const T* beta, T* c, T* dot_partial)
 {
+    const dim3 grid(static_cast<unsigned>(p.n_waves)), block(64);
+    // values, x, c and the row pointers: what a product streams.  Above the Infinity Cache's size the values and
+    // c go non-temporally (csr_offsets.hpp NT), below it repeated products are served from that cache
+    const int64_t product_bytes = pl.nnz * int64_t(sizeof(T)) + (n_rows + n_cols) * int64_t(sizeof(T)) + n_rows * 4;
+    auto launch = [&](auto nd, auto nt) {
+        constexpr int ND = decltype(nd)::value;
+        csr_spmv_pipe3_kernel_offsets<T, ADV, DOT, ND, decltype(nt)::value><<<grid, block, 0, st>>>(
+            int32_t(n_rows), int32_t(n_cols), p.n_seg, p.spw, row_ptrs, vals, b, c, alpha, beta, pl.seg_class,
+            pl.cls_tab, pl.cls_mask, dot_partial);
+    };
     auto go = [&](auto nd) {
-        launch_offsets_kernel_nd<T, ADV, DOT, decltype(nd)::value>(st, pl, p, n_rows, n_cols, alpha, row_ptrs, vals,
-                                                                   b, beta, c, dot_partial);
+        if (product_bytes > offsets_nt_min_bytes) {
+            launch(nd, std::true_type{});
+        } else {
+            launch(nd, std::false_type{});
+        }
     };
     if (pl.max_d <= 8) {
         go(std::integral_constant<int, 8>{});
@@ -700,28 +276,24 @@ int launch_csr_single(gkoc_stream_t s, int64_t n_rows, int64_t n_cols, const T* 
                       const T* vals, const T* b, int64_t ldb, const T* beta, T* c, int64_t ldc, int64_t nrhs)
 {
     using lay = pipe_layout<T>;
+    // What is cached about the matrix is leased to the end of this function: neither the flags nor a plan can be
+    // released while their product is being enqueued.
+    csr_structure_lease lease;
     // rows far longer than the rest: their segments are left out here and done by many workgroups
     // (csr_long_rows.hpp); one right-hand side
     csr_long_info lng;
     if (nrhs == 1 && tune_value(GKOC_TUNE_CSR_LONG_ROWS) != 0) {
-        GKOC_TRY((long_info_of<T, I>(s, n_rows, row_ptrs, &lng)));
+        GKOC_TRY(csr_long_info_for(lease, as_stream(s), n_rows, row_ptrs, &lng));
     }
     const uint32_t* seg_skip = lng.count > 0 ? lng.bits : nullptr;
     // stencil-like structure seen before: the column-offset plan (csr_offsets.hpp) takes its eligible
-    // segments, the row-segment kernel below the others.  Held to the end: a plan is not released while its
-    // product is being enqueued.
+    // segments, the row-segment kernel below the others
     constexpr bool offsets_type = std::is_same<I, int32_t>::value && (sizeof(T) == 8 || sizeof(T) == 4);
-    evicted_plans evicted;
-    std::unique_lock<std::mutex> plan_lock(g_off_mtx, std::defer_lock);
     offsets_plan* plan = nullptr;
-    if constexpr (offsets_type) {
-        if (nrhs == 1 && ldb == 1 && ldc == 1 && vals != nullptr && b != nullptr &&
-            reinterpret_cast<uintptr_t>(vals) % 16 == 0 && tune_value(GKOC_TUNE_CSR_OFFSETS) != 2) {
-            plan_lock.lock();
-            plan = offsets_plan_for(as_stream(s), n_rows, n_cols, row_ptrs, col_idxs, lng, &evicted.v);
-            if (plan == nullptr) plan_lock.unlock();
-        }
+    if (nrhs == 1 && ldb == 1 && ldc == 1) {
+        plan = offsets_plan_of(lease, as_stream(s), n_rows, n_cols, row_ptrs, col_idxs, vals, b, lng);
     }
+    if (lng.count <= 0 && plan == nullptr) lease.give_back();      // (nothing cached is read below)
     // GKOC_TUNE_CSR_SEGS_PER_WAVE forces 1 or 2 segments per wave (round 6 tried "up to eight for matrices
     // with short rows" - the heavy-tailed stand-in 256 us with one, 261 with two, 276 with four, 320 with eight
     // segments; 5-pt 4096^2 325 / 289 / 325 / 315; profiles/r06/r06_segments_per_wave.txt: the size rule
@@ -802,16 +374,13 @@ int launch_csr_single(gkoc_stream_t s, int64_t n_rows, int64_t n_cols, const T* 
 }
 
 template <typename T, typename I, bool ADV>
-int launch_csr(gkoc_stream_t s, int64_t n_rows, int64_t n_cols, const T* alpha,
-               const I* row_ptrs, const I* col_idxs, const T* vals, const T* b,
-               int64_t ldb, const T* beta, T* c, int64_t ldc, int64_t nrhs)
+int launch_csr(gkoc_stream_t s, int64_t n_rows, int64_t n_cols, const T* alpha, const I* row_ptrs, const I* col_idxs,
+               const T* vals, const T* b, int64_t ldb, const T* beta, T* c, int64_t ldc, int64_t nrhs)
 {
-    GKOC_REQUIRE(n_rows >= 0 && n_cols >= 0 && nrhs >= 0, GKOC_E_INVALID,
-                 "negative dimension");
+    GKOC_REQUIRE(n_rows >= 0 && n_cols >= 0 && nrhs >= 0, GKOC_E_INVALID, "negative dimension");
     if (n_rows == 0 || nrhs == 0) return GKOC_OK;
     GKOC_REQUIRE(row_ptrs && c, GKOC_E_INVALID, "null pointer");
-    GKOC_REQUIRE(ldc >= nrhs && (n_cols == 0 || ldb >= nrhs), GKOC_E_INVALID,
-                 "stride smaller than nrhs");
+    GKOC_REQUIRE(ldc >= nrhs && (n_cols == 0 || ldb >= nrhs), GKOC_E_INVALID, "stride smaller than nrhs");
     if (ADV) GKOC_REQUIRE(alpha && beta, GKOC_E_INVALID, "null alpha/beta");
     if (nrhs >= 3) {
         return launch_csr_columns<T, I, ADV>(s, n_rows, n_cols, alpha, row_ptrs, col_idxs, vals, b, ldb, beta, c,
@@ -945,15 +514,14 @@ __global__ void delay_kernel(long long ticks)
 // 12 bytes per stored entry; the result has the bits of the T kernel on the widened values.
 // Columns one after the other (the matrix is streamed once per column).
 template <typename T, typename V, typename I, bool ADV>
-int launch_csr_mixed(gkoc_stream_t s, int64_t n_rows, int64_t n_cols, const T* alpha,
-                     const I* row_ptrs, const I* col_idxs, const V* vals, const T* b, int64_t ldb,
-                     const T* beta, T* c, int64_t ldc, int64_t nrhs)
+int launch_csr_mixed(gkoc_stream_t s, int64_t n_rows, int64_t n_cols, const T* alpha, const I* row_ptrs,
+                     const I* col_idxs, const V* vals, const T* b, int64_t ldb, const T* beta, T* c, int64_t ldc,
+                     int64_t nrhs)
 {
     GKOC_REQUIRE(n_rows >= 0 && n_cols >= 0 && nrhs >= 0, GKOC_E_INVALID, "negative dimension");
     if (n_rows == 0 || nrhs == 0) return GKOC_OK;
     GKOC_REQUIRE(row_ptrs && c, GKOC_E_INVALID, "null pointer");
-    GKOC_REQUIRE(ldc >= nrhs && (n_cols == 0 || ldb >= nrhs), GKOC_E_INVALID,
-                 "stride smaller than nrhs");
+    GKOC_REQUIRE(ldc >= nrhs && (n_cols == 0 || ldb >= nrhs), GKOC_E_INVALID, "stride smaller than nrhs");
     if (ADV) GKOC_REQUIRE(alpha && beta, GKOC_E_INVALID, "null alpha/beta");
     using lay = pipe_layout<T>;
     segment_plan p;
@@ -985,8 +553,7 @@ int launch_csr_mixed(gkoc_stream_t s, int64_t n_rows, int64_t n_cols, const T* a
 // right-hand side, unit strides): every wave also emits its part of the dot
 // product, a fixed two-level fold adds them up
 template <typename T, typename I>
-int launch_csr_dot(gkoc_stream_t s, int64_t n, const I* row_ptrs,
-                   const I* col_idxs, const T* vals, const T* b, T* c,
+int launch_csr_dot(gkoc_stream_t s, int64_t n, const I* row_ptrs, const I* col_idxs, const T* vals, const T* b, T* c,
                    T* dot_out, void* work, size_t work_bytes)
 {
     GKOC_REQUIRE(n >= 0, GKOC_E_INVALID, "negative dimension");
@@ -1001,19 +568,17 @@ int launch_csr_dot(gkoc_stream_t s, int64_t n, const I* row_ptrs,
     // a matrix with rows far beyond the rest: the product with its long rows spread over many workgroups
     // (csr_long_rows.hpp), then the dot product as a pass of its own - the fusion saves one pass over two
     // vectors, a hub row summed by one wave costs milliseconds
+    csr_structure_lease lease;
+    csr_long_info lng;
     if (tune_value(GKOC_TUNE_CSR_LONG_ROWS) != 0) {
-        csr_long_info lng;
-        GKOC_TRY((long_info_of<T, I>(s, n, row_ptrs, &lng)));
+        GKOC_TRY(csr_long_info_for(lease, as_stream(s), n, row_ptrs, &lng));
         if (lng.count > 0) {
+            lease.give_back();      // (launch_csr takes its own, and the mutex is not recursive)
             GKOC_TRY((launch_csr<T, I, false>(s, n, n, nullptr, row_ptrs, col_idxs, vals, b, 1, nullptr, c, 1, 1)));
-            if constexpr (sizeof(T) == 8) {
-                return gkoc_dense_compute_dot_f64(s, n, 1, reinterpret_cast<const double*>(b), 1,
-                                                  reinterpret_cast<const double*>(c), 1,
-                                                  reinterpret_cast<double*>(dot_out), work, work_bytes);
+            if constexpr (std::is_same<T, double>::value) {
+                return gkoc_dense_compute_dot_f64(s, n, 1, b, 1, c, 1, dot_out, work, work_bytes);
             } else {
-                return gkoc_dense_compute_dot_f32(s, n, 1, reinterpret_cast<const float*>(b), 1,
-                                                  reinterpret_cast<const float*>(c), 1,
-                                                  reinterpret_cast<float*>(dot_out), work, work_bytes);
+                return gkoc_dense_compute_dot_f32(s, n, 1, b, 1, c, 1, dot_out, work, work_bytes);
             }
         }
     }
@@ -1030,20 +595,18 @@ int launch_csr_dot(gkoc_stream_t s, int64_t n, const I* row_ptrs,
     const bool vec_ok = streams_aligned(vals, col_idxs, 4);      // (for four entries whatever the type)
     const int xcd_map = (tune_value(GKOC_TUNE_CSR_XCD_MAP) == 1 && p.n_waves >= 8 * 1024) ? 1 : 0;
     // the column-offset plan, where EVERY segment is eligible (a wave's part of <b, c> comes from one kernel)
+    // (no hub rows here: lng.count is 0)
+    offsets_plan* plan = offsets_plan_of(lease, as_stream(s), n, n, row_ptrs, col_idxs, vals, b, lng);
     if constexpr (std::is_same<I, int32_t>::value) {
-        if (vals != nullptr && reinterpret_cast<uintptr_t>(vals) % 16 == 0 && tune_value(GKOC_TUNE_CSR_OFFSETS) != 2) {
-            evicted_plans evicted;
-            std::lock_guard<std::mutex> plan_lock(g_off_mtx);
-            offsets_plan* plan = offsets_plan_for(as_stream(s), n, n, row_ptrs, col_idxs, csr_long_info{}, &evicted.v);
-            if (plan != nullptr && plan->skip == nullptr) {
-                launch_offsets_kernel<T, false, true>(as_stream(s), *plan, p, n, n, static_cast<const T*>(nullptr),
-                                                      row_ptrs, vals, b, static_cast<const T*>(nullptr), c, partial);
-                GKOC_LAUNCH_OK();
-                ++plan->products;
-                return fold_partials<T>(s, p.n_waves, partial, scratch, dot_out, false);
-            }
+        if (plan != nullptr && plan->skip == nullptr) {
+            launch_offsets_kernel<T, false, true>(as_stream(s), *plan, p, n, n, static_cast<const T*>(nullptr),
+                                                  row_ptrs, vals, b, static_cast<const T*>(nullptr), c, partial);
+            GKOC_LAUNCH_OK();
+            ++plan->products;
+            return fold_partials<T>(s, p.n_waves, partial, scratch, dot_out, false);
         }
     }
+    lease.give_back();      // (nothing cached is read below)
     // four waves per SIMD, like the plain product: the dot's registers (and, since round 6, the loop over runs
     // of unflagged segments) had taken the double / int32 kernel to 133 VGPRs = three waves - 985 -> 1107 us on
     // L256 (profiles/r06/r06_bench_kernel_stats_regression.csv); with the bound the compiler stays at 128
@@ -1065,165 +628,7 @@ int launch_csr_dot(gkoc_stream_t s, int64_t n, const I* row_ptrs,
     return fold_partials<T>(s, p.n_waves, partial, scratch, dot_out, false);
 }
 
-// ---- diagonal extraction / sortedness / per-row sort ---------------------
-
-// One wave per 64 rows: the rows' contiguous column-index (and value) range is
-// staged in LDS with coalesced loads, lane = row then works on its row there.
-// Segments longer than the stage fall back to walking global memory per lane.
-constexpr int row_stage_cap = 2048;
-
-template <typename I>
-struct row_segment {
-    int64_t row, rs, re, K0, K1;
-    bool valid;
-};
-
-template <typename I>
-__device__ __forceinline__ row_segment<I> load_row_segment(int64_t n_rows,
-                                                           const I* row_ptrs)
-{
-    row_segment<I> g;
-    const int64_t first = int64_t(blockIdx.x) * 64;
-    g.row = first + threadIdx.x;
-    g.valid = g.row < n_rows;
-    const int64_t last = first + 64 < n_rows ? first + 64 : n_rows;
-    g.rs = row_ptrs[g.valid ? g.row : last];
-    g.re = row_ptrs[g.valid ? g.row + 1 : last];
-    g.K0 = row_ptrs[first];
-    g.K1 = row_ptrs[last];
-    return g;
-}
-
-template <typename T, typename I>
-__global__ __launch_bounds__(64) void extract_diag_kernel(
-    int64_t n_diag, const I* __restrict__ row_ptrs, const I* __restrict__ cols,
-    const T* __restrict__ vals, T* __restrict__ diag)
-{
-    __shared__ I lc[row_stage_cap];
-    const row_segment<I> g = load_row_segment<I>(n_diag, row_ptrs);
-    const bool staged = g.K1 - g.K0 <= row_stage_cap;
-    if (staged) {
-        for (int i = threadIdx.x; i < int(g.K1 - g.K0); i += 64) lc[i] = cols[g.K0 + i];
-        wave_lds_sync();
-    }
-    if (!g.valid) return;
-    T d = T(0);
-    for (int64_t k = g.rs; k < g.re; ++k) {
-        const I c = staged ? lc[k - g.K0] : cols[k];
-        if (int64_t(c) == g.row) {
-            d = vals[k];
-            break;
-        }
-    }
-    diag[g.row] = d;
-}
-
-template <typename I>
-__global__ __launch_bounds__(64) void is_sorted_kernel(
-    int64_t n_rows, const I* __restrict__ row_ptrs, const I* __restrict__ cols,
-    int* __restrict__ flag)
-{
-    __shared__ I lc[row_stage_cap];
-    const row_segment<I> g = load_row_segment<I>(n_rows, row_ptrs);
-    const bool staged = g.K1 - g.K0 <= row_stage_cap;
-    if (staged) {
-        for (int i = threadIdx.x; i < int(g.K1 - g.K0); i += 64) lc[i] = cols[g.K0 + i];
-        wave_lds_sync();
-    }
-    bool ok = true;
-    if (g.valid) {
-        for (int64_t k = g.rs + 1; k < g.re; ++k) {
-            const I a = staged ? lc[k - 1 - g.K0] : cols[k - 1];
-            const I b = staged ? lc[k - g.K0] : cols[k];
-            if (a > b) {
-                ok = false;
-                break;
-            }
-        }
-    }
-    if (__any(!ok) && threadIdx.x == 0) atomicAnd(flag, 0);
-}
-
-// stable insertion sort per row (rows are short on this path; Ginkgo only
-// calls it when is_sorted_by_column_index returned false)
-template <typename T, typename I>
-__global__ __launch_bounds__(64) void sort_rows_kernel(
-    int64_t n_rows, const I* __restrict__ row_ptrs, I* __restrict__ cols,
-    T* __restrict__ vals)
-{
-    __shared__ I lc[row_stage_cap];
-    __shared__ T lv[row_stage_cap];
-    const row_segment<I> g = load_row_segment<I>(n_rows, row_ptrs);
-    const bool staged = g.K1 - g.K0 <= row_stage_cap;
-    if (staged) {
-        const int seg = int(g.K1 - g.K0);
-        for (int i = threadIdx.x; i < seg; i += 64) {
-            lc[i] = cols[g.K0 + i];
-            lv[i] = vals[g.K0 + i];
-        }
-        wave_lds_sync();
-        if (g.valid) {
-            const int a = int(g.rs - g.K0), e = int(g.re - g.K0);
-            for (int i = a + 1; i < e; ++i) {
-                const I ci = lc[i];
-                const T vi = lv[i];
-                int k = i - 1;
-                while (k >= a && lc[k] > ci) {
-                    lc[k + 1] = lc[k];
-                    lv[k + 1] = lv[k];
-                    --k;
-                }
-                lc[k + 1] = ci;
-                lv[k + 1] = vi;
-            }
-        }
-        wave_lds_sync();
-        for (int i = threadIdx.x; i < seg; i += 64) {
-            cols[g.K0 + i] = lc[i];
-            vals[g.K0 + i] = lv[i];
-        }
-        return;
-    }
-    if (!g.valid) return;
-    for (int64_t i = g.rs + 1; i < g.re; ++i) {
-        const I ci = cols[i];
-        const T vi = vals[i];
-        int64_t k = i - 1;
-        while (k >= g.rs && cols[k] > ci) {
-            cols[k + 1] = cols[k];
-            vals[k + 1] = vals[k];
-            --k;
-        }
-        cols[k + 1] = ci;
-        vals[k + 1] = vi;
-    }
-}
-
 }  // namespace
-
-// (common.hpp) the index array(s) in [first, first + bytes) are freed or written: what was derived from them goes
-void csr_offsets_forget(const void* first, size_t bytes)
-{
-    const char* lo = static_cast<const char*>(first);
-    const char* hi = lo + (bytes ? bytes : 1);
-    std::vector<offsets_plan> gone;
-    {
-        std::lock_guard<std::mutex> g(g_off_mtx);
-        for (auto it = g_off_cache.begin(); it != g_off_cache.end();) {
-            const char* rp = static_cast<const char*>(std::get<1>(it->first));
-            const char* ci = static_cast<const char*>(std::get<2>(it->first));
-            // [lo, hi) overlaps either allocation (a copy into the middle of an array counts)
-            if ((lo < rp + it->second.rp_bytes && rp < hi) || (lo < ci + it->second.ci_bytes && ci < hi)) {
-                gone.push_back(it->second);
-                it = g_off_cache.erase(it);
-            } else {
-                ++it;
-            }
-        }
-        g_csr_offsets_cached.store(int(g_off_cache.size()));
-    }
-    offsets_release(gone);
-}
 
 // Complex values (round 6).  The product of round 5 was one thread per row walking global memory: 15.0 ms on
 // the 27-pt 256^3 matrix with complex<double> values = 0.63 TB/s, 78 % of a CbGmres<complex<double>> iteration
@@ -1284,105 +689,31 @@ GKOC_INST_CX(gkoc_c64, int64_t)
 
 using namespace gkoc;
 
-#define GKOC_DEF_CSR(T, TN, I, IN)                                             \
-    extern "C" int gkoc_csr_spmv_##TN##_##IN(                                  \
-        gkoc_stream_t s, int64_t n_rows, int64_t n_cols, const I* row_ptrs,    \
-        const I* col_idxs, const T* vals, const T* b, int64_t ldb, T* c,       \
-        int64_t ldc, int64_t nrhs)                                             \
-    {                                                                          \
-        return launch_csr<T, I, false>(s, n_rows, n_cols, nullptr, row_ptrs,   \
-                                       col_idxs, vals, b, ldb, nullptr, c,     \
-                                       ldc, nrhs);                             \
-    }                                                                          \
-    extern "C" int gkoc_csr_advanced_spmv_##TN##_##IN(                         \
-        gkoc_stream_t s, int64_t n_rows, int64_t n_cols, const T* alpha,       \
-        const I* row_ptrs, const I* col_idxs, const T* vals, const T* b,       \
-        int64_t ldb, const T* beta, T* c, int64_t ldc, int64_t nrhs)           \
-    {                                                                          \
-        return launch_csr<T, I, true>(s, n_rows, n_cols, alpha, row_ptrs,      \
-                                      col_idxs, vals, b, ldb, beta, c, ldc,    \
-                                      nrhs);                                   \
-    }                                                                          \
-    extern "C" int gkoc_x_csr_spmv_dot_##TN##_##IN(                            \
-        gkoc_stream_t s, int64_t n, const I* row_ptrs, const I* col_idxs,      \
-        const T* vals, const T* b, T* c, T* dot_out, void* work,               \
-        size_t work_bytes)                                                     \
-    {                                                                          \
-        return launch_csr_dot<T, I>(s, n, row_ptrs, col_idxs, vals, b, c,      \
-                                    dot_out, work, work_bytes);                \
-    }                                                                          \
-    extern "C" int gkoc_csr_extract_diagonal_##TN##_##IN(                      \
-        gkoc_stream_t s, int64_t n_rows, int64_t n_cols, const I* row_ptrs,    \
-        const I* col_idxs, const T* vals, T* diag)                             \
-    {                                                                          \
-        const int64_t nd = n_rows < n_cols ? n_rows : n_cols;                  \
-        if (nd <= 0) return GKOC_OK;                                           \
-        extract_diag_kernel<T, I>                                              \
-            <<<dim3(unsigned(ceildiv(nd, 64))), dim3(64), 0, as_stream(s)>>>(  \
-                nd, row_ptrs, col_idxs, vals, diag);                           \
-        GKOC_LAUNCH_OK();                                                      \
-        return GKOC_OK;                                                        \
-    }                                                                          \
-    extern "C" int gkoc_csr_is_sorted_by_column_index_##TN##_##IN(             \
-        gkoc_stream_t s, int64_t n_rows, const I* row_ptrs,                    \
-        const I* col_idxs, int* is_sorted_host)                                \
-    {                                                                          \
-        GKOC_REQUIRE(is_sorted_host, GKOC_E_INVALID, "null result");           \
-        *is_sorted_host = 1;                                                   \
-        if (n_rows <= 0) return GKOC_OK;                                       \
-        int* flag = nullptr;                                                   \
-        GKOC_TRY(scratch_malloc(as_stream(s), reinterpret_cast<void**>(&flag), \
-                                sizeof(int)));                                 \
-        /* any non-zero pattern = sorted; set on the device (an asynchronous */ \
-        /* copy from pageable host memory is not ordered with the kernel)    */ \
-        GKOC_HIP(hipMemsetAsync(flag, 1, sizeof(int), as_stream(s)));          \
-        is_sorted_kernel<I>                                                    \
-            <<<dim3(unsigned(ceildiv(n_rows, 64))), dim3(64), 0,               \
-               as_stream(s)>>>(n_rows, row_ptrs, col_idxs, flag);              \
-        GKOC_LAUNCH_OK();                                                      \
-        GKOC_HIP(hipMemcpyAsync(is_sorted_host, flag, sizeof(int),             \
-                                hipMemcpyDeviceToHost, as_stream(s)));         \
-        GKOC_HIP(hipStreamSynchronize(as_stream(s)));                          \
-        GKOC_TRY(scratch_free(as_stream(s), flag));                            \
-        *is_sorted_host = *is_sorted_host != 0;                                \
-        return GKOC_OK;                                                        \
-    }                                                                          \
-    extern "C" int gkoc_csr_sort_by_column_index_##TN##_##IN(                  \
-        gkoc_stream_t s, int64_t n_rows, const I* row_ptrs, I* col_idxs,       \
-        T* vals)                                                               \
-    {                                                                          \
-        if (n_rows <= 0) return GKOC_OK;                                       \
-        gkoc::csr_structure_written(col_idxs);                                 \
-        sort_rows_kernel<T, I>                                                 \
-            <<<dim3(unsigned(ceildiv(n_rows, 64))), dim3(64), 0,               \
-               as_stream(s)>>>(n_rows, row_ptrs, col_idxs, vals);              \
-        GKOC_LAUNCH_OK();                                                      \
-        return GKOC_OK;                                                        \
+#define GKOC_DEF_CSR(T, TN, I, IN)                                                                                  \
+    extern "C" int gkoc_csr_spmv_##TN##_##IN(gkoc_stream_t s, int64_t n_rows, int64_t n_cols, const I* row_ptrs,       \
+                                             const I* col_idxs, const T* vals, const T* b, int64_t ldb, T* c,          \
+                                             int64_t ldc, int64_t nrhs)                                                \
+    {                                                                                                                  \
+        return launch_csr<T, I, false>(s, n_rows, n_cols, nullptr, row_ptrs, col_idxs, vals, b, ldb, nullptr, c, ldc,  \
+                                       nrhs);                                                                          \
+    }                                                                                                                  \
+    extern "C" int gkoc_csr_advanced_spmv_##TN##_##IN(                                                                 \
+        gkoc_stream_t s, int64_t n_rows, int64_t n_cols, const T* alpha, const I* row_ptrs, const I* col_idxs,         \
+        const T* vals, const T* b, int64_t ldb, const T* beta, T* c, int64_t ldc, int64_t nrhs)                        \
+    {                                                                                                                  \
+        return launch_csr<T, I, true>(s, n_rows, n_cols, alpha, row_ptrs, col_idxs, vals, b, ldb, beta, c, ldc, nrhs); \
+    }                                                                                                                  \
+    extern "C" int gkoc_x_csr_spmv_dot_##TN##_##IN(gkoc_stream_t s, int64_t n, const I* row_ptrs, const I* col_idxs,   \
+                                                   const T* vals, const T* b, T* c, T* dot_out, void* work,            \
+                                                   size_t work_bytes)                                                  \
+    {                                                                                                                  \
+        return launch_csr_dot<T, I>(s, n, row_ptrs, col_idxs, vals, b, c, dot_out, work, work_bytes);                  \
     }
 
 GKOC_DEF_CSR(double, f64, int32_t, i32)
 GKOC_DEF_CSR(double, f64, int64_t, i64)
 GKOC_DEF_CSR(float, f32, int32_t, i32)
 GKOC_DEF_CSR(float, f32, int64_t, i64)
-
-// csr::sort_by_column_index for complex values (pairs; the kernel only moves them)
-#define GKOC_DEF_CSR_SORT(T, TN, I, IN)                                        \
-    extern "C" int gkoc_csr_sort_by_column_index_##TN##_##IN(                  \
-        gkoc_stream_t s, int64_t n_rows, const I* row_ptrs, I* col_idxs,       \
-        T* vals)                                                               \
-    {                                                                          \
-        if (n_rows <= 0) return GKOC_OK;                                       \
-        gkoc::csr_structure_written(col_idxs);                                 \
-        sort_rows_kernel<T, I>                                                 \
-            <<<dim3(unsigned(ceildiv(n_rows, 64))), dim3(64), 0,               \
-               as_stream(s)>>>(n_rows, row_ptrs, col_idxs, vals);              \
-        GKOC_LAUNCH_OK();                                                      \
-        return GKOC_OK;                                                        \
-    }
-GKOC_DEF_CSR_SORT(gkoc_c128, c128, int32_t, i32)
-GKOC_DEF_CSR_SORT(gkoc_c128, c128, int64_t, i64)
-GKOC_DEF_CSR_SORT(gkoc_c64, c64, int32_t, i32)
-GKOC_DEF_CSR_SORT(gkoc_c64, c64, int64_t, i64)
 
 #define GKOC_DEF_CSR_GATED(T, TN, I, IN)                                                             \
     extern "C" int gkoc_csr_spmv_gated_##TN##_##IN(                                                   \
@@ -1417,58 +748,6 @@ GKOC_DEF_CSR_GATED_DOT(double, f64, int64_t, i64)
 GKOC_DEF_CSR_GATED_DOT(float, f32, int32_t, i32)
 GKOC_DEF_CSR_GATED_DOT(float, f32, int64_t, i64)
 
-extern "C" int gkoc_csr_structure_changed(const void* index_array)
-{
-    gkoc::csr_structure_written(index_array);
-    return GKOC_OK;
-}
-
-extern "C" int gkoc_csr_plan_info(const void* row_ptrs, const void* col_idxs, int* state, int64_t* eligible_segments,
-                                  int64_t* segments, int64_t* bytes, int64_t* products_by_plan)
-{
-    int st = -1;
-    int64_t el = 0, ns = 0, by = 0, pr = 0;
-    int dev = 0;
-    GKOC_HIP(hipGetDevice(&dev));
-    {
-        std::lock_guard<std::mutex> g(gkoc::g_off_mtx);
-        for (const auto& kv : gkoc::g_off_cache) {
-            if (std::get<0>(kv.first) == dev && std::get<1>(kv.first) == row_ptrs &&
-                std::get<2>(kv.first) == col_idxs) {
-                st = kv.second.state;
-                el = kv.second.eligible;
-                ns = kv.second.n_seg;
-                by = kv.second.bytes;
-                pr = kv.second.products;
-            }
-        }
-    }
-    if (state) *state = st;
-    if (eligible_segments) *eligible_segments = el;
-    if (segments) *segments = ns;
-    if (bytes) *bytes = by;
-    if (products_by_plan) *products_by_plan = pr;
-    return GKOC_OK;
-}
-
-extern "C" int gkoc_csr_plan_classes(const void* row_ptrs, const void* col_idxs, uint64_t* classes)
-{
-    uint64_t nc = 0;
-    int dev = 0;
-    GKOC_HIP(hipGetDevice(&dev));
-    {
-        std::lock_guard<std::mutex> g(gkoc::g_off_mtx);
-        for (const auto& kv : gkoc::g_off_cache) {
-            if (std::get<0>(kv.first) == dev && std::get<1>(kv.first) == row_ptrs &&
-                std::get<2>(kv.first) == col_idxs) {
-                nc = uint64_t(kv.second.n_classes);
-            }
-        }
-    }
-    if (classes) *classes = nc;
-    return GKOC_OK;
-}
-
 extern "C" int gkoc_csr_spmv_gated_fits(int64_t n_rows, int64_t head_rows, int64_t tail_rows)
 {
     return gkoc::gated_fits(n_rows, head_rows, tail_rows) ? 1 : 0;
@@ -1494,24 +773,20 @@ extern "C" int gkoc_debug_delay(gkoc_stream_t s, int64_t usec, int blocks, int t
     return GKOC_OK;
 }
 
-#define GKOC_DEF_CSR_MIXED(I, IN)                                                                  \
-    extern "C" int gkoc_csr_spmv_f32_f64_##IN(gkoc_stream_t s, int64_t n_rows, int64_t n_cols,     \
-                                              const I* row_ptrs, const I* col_idxs,                \
-                                              const float* vals, const double* b, int64_t ldb,     \
-                                              double* c, int64_t ldc, int64_t nrhs)                \
-    {                                                                                              \
-        return launch_csr_mixed<double, float, I, false>(s, n_rows, n_cols, nullptr, row_ptrs,     \
-                                                         col_idxs, vals, b, ldb, nullptr, c, ldc,  \
-                                                         nrhs);                                    \
-    }                                                                                              \
-    extern "C" int gkoc_csr_advanced_spmv_f32_f64_##IN(                                            \
-        gkoc_stream_t s, int64_t n_rows, int64_t n_cols, const double* alpha, const I* row_ptrs,   \
-        const I* col_idxs, const float* vals, const double* b, int64_t ldb, const double* beta,    \
-        double* c, int64_t ldc, int64_t nrhs)                                                      \
-    {                                                                                              \
-        return launch_csr_mixed<double, float, I, true>(s, n_rows, n_cols, alpha, row_ptrs,        \
-                                                        col_idxs, vals, b, ldb, beta, c, ldc,      \
-                                                        nrhs);                                     \
+#define GKOC_DEF_CSR_MIXED(I, IN)                                                                                  \
+    extern "C" int gkoc_csr_spmv_f32_f64_##IN(gkoc_stream_t s, int64_t n_rows, int64_t n_cols, const I* row_ptrs,      \
+                                              const I* col_idxs, const float* vals, const double* b, int64_t ldb,      \
+                                              double* c, int64_t ldc, int64_t nrhs)                                    \
+    {                                                                                                                  \
+        return launch_csr_mixed<double, float, I, false>(s, n_rows, n_cols, nullptr, row_ptrs, col_idxs, vals, b, ldb, \
+                                                         nullptr, c, ldc, nrhs);                                       \
+    }                                                                                                                  \
+    extern "C" int gkoc_csr_advanced_spmv_f32_f64_##IN(                                                                \
+        gkoc_stream_t s, int64_t n_rows, int64_t n_cols, const double* alpha, const I* row_ptrs, const I* col_idxs,    \
+        const float* vals, const double* b, int64_t ldb, const double* beta, double* c, int64_t ldc, int64_t nrhs)     \
+    {                                                                                                                  \
+        return launch_csr_mixed<double, float, I, true>(s, n_rows, n_cols, alpha, row_ptrs, col_idxs, vals, b, ldb,    \
+                                                        beta, c, ldc, nrhs);                                           \
     }
 GKOC_DEF_CSR_MIXED(int32_t, i32)
 GKOC_DEF_CSR_MIXED(int64_t, i64)

@@ -300,7 +300,7 @@ int gkoc_malloc_managed(void** ptr, size_t bytes, unsigned int flags)
 
 int gkoc_free(void* ptr)
 {
-    gkoc::csr_long_rows_forget(ptr);     // what csr::spmv remembers about a matrix at this address (csr_spmv.hip)
+    gkoc::csr_long_rows_forget(ptr);     // what csr::spmv remembers about a matrix at this address (csr_structure.hip)
     gkoc::csr_structure_written(ptr);
     return arena_free(ptr);
 }

@@ -201,7 +201,8 @@ int gkoc_arena_probe(const void* x, size_t x_bytes, void* y, int read_kb_per_wav
 #define GKOC_TUNE_CSR_LONG_ROWS 12   /* csr::spmv, one right-hand side: 1 (default) the 64-row segments that hold a row
                                       longer than GKOC_CSR_LONG_ROW are found once per matrix (one scan of the row
                                       pointers, remembered per (row_ptrs, n_rows)) and multiplied by many workgroups
-                                      each (csrc/csr_long_rows.hpp) instead of by one wave; 0: one wave, as before.
+                                      each (csrc/csr_long_rows.hpp; the memory: csrc/csr_structure.hip) instead of by
+                                      one wave; 0: one wave, as before.
                                       The chunk sums go to a buffer per (matrix, stream): products with the SAME
                                       matrix may run at the same time on several streams.
                                       Stream capture: a product captured into a hipGraph takes the many-workgroup

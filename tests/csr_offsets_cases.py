@@ -1,6 +1,6 @@
 """Host model, matrices and shared helpers of the tests of the CSR column-offset plan (csrc/csr_offsets.hpp, the
-launcher in csrc/csr_spmv.hip): tests/test_csr_offsets_gpu.py, tests/test_csr_offsets_routes_gpu.py.  The model and
-the builders are checked on the CPU by tests/test_csr_offsets_cases_cpu.py, so that a bug in a builder cannot make
+launcher in csrc/csr_spmv.hip, the plan cache in csrc/csr_structure.hip): tests/test_csr_offsets_gpu.py,
+tests/test_csr_offsets_routes_gpu.py.  The model and the builders are checked on the CPU by tests/test_csr_offsets_cases_cpu.py, so that a bug in a builder cannot make
 a device case vacuous.
 
 plan_model is the definition of csr_offsets.hpp:3-15 in plain loops: a 64-row segment is ELIGIBLE if every row
@@ -20,8 +20,8 @@ import numpy as np
 
 OFFS_MAX = 32              # csr_offsets.hpp: offsets per segment = bits of a row's mask
 SEG = 64
-MIN_SHARE = 50             # csr_spmv.hip offsets_min_share, per cent
-CACHE_CAP = 128            # csr_spmv.hip offsets_cache_cap
+MIN_SHARE = 50             # csr_structure.hip offsets_min_share, per cent
+CACHE_CAP = 128            # csr_structure.hip offsets_cache_cap
 CAP = SEG * OFFS_MAX       # entries of a segment's stage
 
 KEY = 18                   # GKOC_TUNE_CSR_OFFSETS

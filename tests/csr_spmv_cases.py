@@ -24,8 +24,8 @@ import numpy as np
 
 LONG_ROW = 4096            # GKOC_CSR_LONG_ROW
 LONG_MAX_PER_SEG = 8       # csr_long_rows.hpp: long rows of one segment that are cut into chunks
-LONG_LIST_CAP = 4096       # csr_spmv.hip long_list_cap
-LONG_CACHE_CAP = 128       # csr_spmv.hip long_cache_cap
+LONG_LIST_CAP = 4096       # csr_structure.hip long_list_cap
+LONG_CACHE_CAP = 128       # csr_structure.hip long_cache_cap
 
 Mat = namedtuple("Mat", "rp ci v lens shape")
 Ref = namedtuple("Ref", "seq hubs exact S")     # seq (n, k); hubs (h,); exact, S (h, k) in np.longdouble

@@ -1,4 +1,4 @@
-"""The column-offset plan kept by class (csrc/csr_offsets.hpp, the plan code of csrc/csr_spmv.hip): segments whose
+"""The column-offset plan kept by class (csrc/csr_offsets.hpp, the plan code of csrc/csr_structure.hip): segments whose
 33 table words and 64 mask words are equal share one entry of the class tables.
 
 Every case goes through check_all_modes of tests/csr_offsets_cases.py - bit for bit against the sequential oracle and

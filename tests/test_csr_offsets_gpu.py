@@ -1,5 +1,5 @@
-"""The cached column-offset plan of the CSR SpMV (csrc/csr_offsets.hpp, launcher in csrc/csr_spmv.hip).
-The matrices, the host model of the plan and the helpers are tests/csr_offsets_cases.py (checked on the CPU by
+"""The cached column-offset plan of the CSR SpMV (csrc/csr_offsets.hpp, launcher in csrc/csr_spmv.hip, plan cache in
+csrc/csr_structure.hip).  The matrices, the host model of the plan and the helpers are tests/csr_offsets_cases.py (checked on the CPU by
 tests/test_csr_offsets_cases_cpu.py); the routes that drop a plan are tests/test_csr_offsets_routes_gpu.py.
 
 Index arrays come from the library's allocator even when tiny (only those ever get a plan).  Every product is

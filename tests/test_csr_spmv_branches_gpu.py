@@ -1,6 +1,6 @@
-"""Every branch of the CSR SpMV launchers (csrc/csr_spmv.hip) at the smallest size that selects it; the list of
-branches, the condition that selects each and the test that reaches it are in docs/binding_kernel_tests.md,
-"CSR SpMV launcher branches".
+"""Every branch of the CSR SpMV launchers (csrc/csr_spmv.hip; what they remember about a matrix is kept by
+csrc/csr_structure.hip) at the smallest size that selects it; the list of branches, the condition that selects each
+and the test that reaches it are in docs/binding_kernel_tests.md, "CSR SpMV launcher branches".
 
 Rows of at most GKOC_CSR_LONG_ROW = 4096 entries: bit-identical to the sequential oracle.  Longer rows, where a
 kernel sums them in another order: |got - exact| <= D eps S against an np.longdouble sum, D = ceil(len / 64) + 80
@@ -10,6 +10,7 @@ every test is recorded with util.record_perf (and printed with `pytest -s`).
 """
 import contextlib
 import ctypes as C
+import gc
 
 import numpy as np
 import pytest
@@ -52,6 +53,13 @@ def ratios(request):
 
 def keep(ratios, case, ratio):
     ratios[case] = max(ratios.get(case, 0.0), ratio)
+
+
+def _allocations(ex):
+    """live allocations of the arena, with Python's dead objects collected and the device idle"""
+    gc.collect()
+    ex.synchronize()
+    return ex.arena_info()["num_allocations"]
 
 
 def csr_of(g, ex, m, unaligned=False):
@@ -279,7 +287,12 @@ def test_cache_stale_flags(gexec, oracle, ratios):
 def test_cache_eviction(gexec, oracle, ratios):
     """130 matrices with a hub row, all alive, are more than the 128 the cache holds: the oldest entries make
     room (their flags and chunk buffers are freed), and the first three matrices, multiplied again, are looked
-    at again.  Every product is right."""
+    at again.  Every product is right.
+
+    Release accounting: after 128 arrivals a cache of 128 holds only this test's matrices, and each of them owns
+    the same three buffers (flags, list, the stream's chunk sums).  So every later arrival - first products number
+    129 and 130, then the three matrices that are multiplied again - frees exactly what it takes: the arena's
+    allocation count, taken after the product with its temporaries dropped, stays what it was after number 128."""
     import ginkgo_amd as g
     count = cc.LONG_CACHE_CAP + 2
     mats = [cc.case_evict(i) for i in range(count)]
@@ -287,39 +300,62 @@ def test_cache_eviction(gexec, oracle, ratios):
     nan = np.full(mats[0].shape[0], np.nan)
     alive = [csr_of(g, gexec, m) for m in mats]
     assert len({a.row_ptrs.data_ptr() for a in alive}) == count
-    for i in list(range(count)) + [0, 1, 2]:
+    full = None
+    for nth, i in enumerate(list(range(count)) + [0, 1, 2]):
         ref = cc.reference(oracle, mats[i], b)
         keep(ratios, "all", cc.judge(product(g, gexec, alive[i], b, nan), ref, mats[i]))
+        if nth + 1 == cc.LONG_CACHE_CAP:
+            full = _allocations(gexec)
+        elif nth + 1 > cc.LONG_CACHE_CAP:
+            assert _allocations(gexec) == full, (nth + 1, i)
 
 
 def test_cache_forgets_on_free(gexec, oracle, ratios):
     """row pointers from gkoc_malloc: gkoc_free drops the cache entry of the pointer (csr_long_rows_forget), so a
-    new matrix in a new allocation - the arena usually hands out the same block - is looked at afresh"""
+    new matrix in a new allocation - the arena usually hands out the same block - is looked at afresh.
+
+    Release accounting: the entry's flags, list and chunk sums go with the pointer - the arena's allocation count
+    after gkoc_free(p) is the one taken before gkoc_malloc of the round (after a warm-up round: what the library
+    keeps per stream)."""
     import ginkgo_amd as g
     from ginkgo_amd import _lib
     n, ncols = 64 * 2 + 5, 6000
     b = np.random.default_rng(70).uniform(-1, 1, ncols)
     db = g.Dense.from_numpy(gexec, b)
     ptrs = []
-    for seed, hubs in ((300, ((7, 5000),)), (301, ((64 + 9, 4097), (n - 1, 4500)))):
+
+    def products(m, p, ci_t, v_t):
+        outs = []
+        for _ in range(2):
+            dc = g.Dense.from_numpy(gexec, np.full(n, np.nan))
+            _lib.call("gkoc_csr_spmv_f64_i32", gexec.stream, n, ncols, p, ci_t, v_t, db.values, 1, dc.values, 1, 1)
+            outs.append(dc.to_numpy())
+        return outs
+
+    def round_(seed, hubs, case):
         m = cc.hub_matrix(seed, n, ncols, hubs)
         ci_t, v_t = gexec.to_device(m.ci), gexec.to_device(m.v)
+        before = _allocations(gexec)
         p = C.c_void_p()
         _lib.call("gkoc_malloc", C.byref(p), C.c_size_t(m.rp.nbytes))
         try:
             _lib.call("gkoc_memcpy_h2d", p, m.rp.ctypes.data_as(C.c_void_p), C.c_size_t(m.rp.nbytes), gexec.stream)
             ref = cc.reference(oracle, m, b)
-            outs = []
-            for _ in range(2):
-                dc = g.Dense.from_numpy(gexec, np.full(n, np.nan))
-                _lib.call("gkoc_csr_spmv_f64_i32", gexec.stream, n, ncols, p, ci_t, v_t, db.values, 1, dc.values, 1, 1)
-                outs.append(dc.to_numpy())
+            outs = products(m, p, ci_t, v_t)
             assert np.array_equal(outs[0], outs[1])
-            keep(ratios, f"matrix {len(ptrs) + 1}", cc.judge(outs[0], ref, m))
+            if case:
+                keep(ratios, case, cc.judge(outs[0], ref, m))
         finally:
             gexec.synchronize()
             _lib.call("gkoc_free", p)
-        ptrs.append(p.value)
+        after = _allocations(gexec)
+        assert case is None or after == before, (case, before, after)
+        return p.value
+
+    rounds = ((300, ((7, 5000),)), (301, ((64 + 9, 4097), (n - 1, 4500))))
+    round_(*rounds[0], None)      # (warm-up)
+    for seed, hubs in rounds:
+        ptrs.append(round_(seed, hubs, f"matrix {len(ptrs) + 1}"))
     record_perf("csr_spmv_branches", test="test_cache_forgets_on_free", address_reused=ptrs[0] == ptrs[1])
 
 

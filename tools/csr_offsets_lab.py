@@ -4,7 +4,7 @@
     <b, c> entry (gkoc_x_csr_spmv_dot_*; its c and dot must have the same bits either way);
   * the cost of the analysis: the second product from entry to return and to completion;
   * the stencil with every other segment made ineligible (an unsorted row): plan + row-segment kernel in one
-    product against the row-segment kernel alone - the "at least half of the segments" rule of csr_spmv.hip.
+    product against the row-segment kernel alone - the "at least half of the segments" rule of csr_structure.hip.
 A variant of the kernel that is not in the tree (a step of a change kept apart to be measured, say) is a second
 library built from a copy of the sources: --lib PATH loads that one instead of ginkgo_amd/lib, --only-kernels
 skips the analysis and the half-eligible matrix.  Two libraries cannot share one process' buffers, so such runs are
