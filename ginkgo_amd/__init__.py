@@ -12,7 +12,7 @@ from .executor import Cdna4Executor
 from .matrix import (Coo, Csr, Dense, DeviceMatrixData, Ell, Fbcsr, Hybrid, Sellp, entry_dtype, scalar,
                      stencil_csr)
 from .preconditioner import GaussSeidel, Ic, Ilu, Jacobi, Sor, compute_storage_scheme
-from .triangular import LowerTrs, UpperTrs
+from .triangular import Direct, LowerTrs, UpperTrs
 from .isai import GeneralIsai, LowerIsai, SpdIsai, UpperIsai
 from .multigrid import Multigrid, Pgm
 from . import multigrid
@@ -22,7 +22,7 @@ from .solver import Cg, Gmres, Identity, ortho_method
 from .krylov import Bicg, Bicgstab, Cgs, Chebyshev, Fcg, Gcr, Ir, Minres, PipeCg
 from . import stop
 
-__all__ = ["LowerTrs", "UpperTrs", "LowerIsai", "UpperIsai", "GeneralIsai", "SpdIsai", "Pgm", "Multigrid", "multigrid", "batch", "Sor", "GaussSeidel", "Ilu", "Ic", "factorization","Coo", "DeviceMatrixData", "entry_dtype", "Hybrid", "Bicg", "Bicgstab", "Chebyshev", "Gcr", "Ir", "Minres", "Cgs", "Fcg", "PipeCg", "Cdna4Executor", "Csr", "Dense", "Ell", "Fbcsr", "Sellp", "scalar",
+__all__ = ["LowerTrs", "UpperTrs", "Direct", "LowerIsai", "UpperIsai", "GeneralIsai", "SpdIsai", "Pgm", "Multigrid", "multigrid", "batch", "Sor", "GaussSeidel", "Ilu", "Ic", "factorization","Coo", "DeviceMatrixData", "entry_dtype", "Hybrid", "Bicg", "Bicgstab", "Chebyshev", "Gcr", "Ir", "Minres", "Cgs", "Fcg", "PipeCg", "Cdna4Executor", "Csr", "Dense", "Ell", "Fbcsr", "Sellp", "scalar",
            "stencil_csr", "Jacobi", "compute_storage_scheme", "Cg", "Gmres", "ortho_method", "Identity",
            "stop", "GkoError", "NotCompiled", "NotSupported",
            "DimensionMismatch", "LIB_PATH"]

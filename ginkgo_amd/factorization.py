@@ -33,6 +33,22 @@ gkoc_par_ilu_sweeps_from_* / gkoc_par_ic_sweeps_from_*; every new pattern comes 
 restatement in tests/par_ilut_refs.py.  The selection is always exact: `with_approximate_select` and
 `with_deterministic_sample` are accepted without effect.  A limit below 1.0 is refused.  Pivots are not checked;
 ParIct in particular can break down where IC(0) does not (docs/KERNELS.md 43).
+
+`Cholesky` / `Lu` - mirror of include/ginkgo/core/factorization/{cholesky,lu}.hpp (experimental::factorization) -
+are the DIRECT factorizations: the pattern of L is computed on the device (symbolic Cholesky of S = pattern(A) +
+pattern(A^T) + every diagonal: gkoc_symbolic_forest_* / _post_keys_* / _cholesky_count_* / _cholesky_expand_*, the
+triplet pipeline makes the sorted Csr), A is placed on it with +0 elsewhere (gkoc_par_ilut_gather_*) and the
+contracts of Ic / Ilu run on the filled pattern, where they ARE the Cholesky factorization and the LU factorization
+without pivoting (docs/KERNELS.md 44): bit-identical to tests/factorization_refs.py on the pattern of
+tests/symbolic_refs.py.  `Cholesky` reads the lower triangle of A only.  `Lu`'s combined pattern is L's row followed
+by the row of L^T.  A departure from Ginkgo: `with_symbolic_algorithm` accepts "general", "near_symmetric" and
+"symmetric" and all three run on the symmetrised pattern - for an unsymmetric pattern that is a superset of the
+true LU fill, whose extra entries come out as exact zeros.  `with_symbolic_factorization(csr)` takes a given
+pattern instead (for Cholesky its lower triangle); it is checked for square shape, sorted rows and stored diagonals
+only, and an entry of A outside it is dropped - with A's own pattern the result is Ilu's / Ic's.  Pivots are not
+checked and nothing is permuted: a zero pivot (negative for Cholesky) gives inf / NaN entries as in Ilu / Ic.  There
+is no fill-reducing ordering yet: in natural order the 27-point stencil's forest is a chain, so the fill is large
+and the numeric phase has n levels.
 """
 import ctypes as C
 import math
@@ -42,13 +58,21 @@ import torch
 from ._lib import IT, VT, DimensionMismatch, GkoError, NotSupported, call, lib
 from .executor import MEM_INDICES, MEM_VALUES
 from .isai import _lower_pattern
-from .matrix import Csr, DeviceMatrixData, Fbcsr
+from .matrix import Csr, DeviceMatrixData, Fbcsr, _np_dtype, entry_dtype
 
 
 def row_limits():
     """the row lengths at which the factorization kernels change path (gkoc_factorization_row_limits)"""
     limits, count = (C.c_int * 4)(), C.c_int(0)
     call("gkoc_factorization_row_limits", limits, C.byref(count))
+    return [int(limits[p]) for p in range(count.value)]
+
+
+def symbolic_row_limits():
+    """the numbers of strictly-lower entries of a row at which the symbolic kernels change path
+    (gkoc_symbolic_row_limits)"""
+    limits, count = (C.c_int * 4)(), C.c_int(0)
+    call("gkoc_symbolic_row_limits", limits, C.byref(count))
     return [int(limits[p]) for p in range(count.value)]
 
 
@@ -147,6 +171,36 @@ class _ParIctFactory(_ThresholdMixin, _IcFactory):
     pass
 
 
+class _DirectMixin:
+    """with_symbolic_factorization of the two direct factories"""
+    symbolic = None
+
+    def with_symbolic_factorization(self, pattern):
+        """a Csr whose pattern is used instead of the computed fill pattern (None: compute it)"""
+        if pattern is not None and not isinstance(pattern, Csr):
+            raise NotSupported("with_symbolic_factorization takes a Csr (its values are not read) or None")
+        self.symbolic = pattern
+        return self
+
+
+class _CholeskyFactory(_DirectMixin, _IcFactory):
+    pass
+
+
+SYMBOLIC_ALGORITHMS = ("general", "near_symmetric", "symmetric")
+
+
+class _LuFactory(_DirectMixin, _Factory):
+    symbolic_algorithm = "general"
+
+    def with_symbolic_algorithm(self, name):
+        """accepted for API compatibility: every algorithm runs on the symmetrised pattern"""
+        if name not in SYMBOLIC_ALGORITHMS:
+            raise GkoError(f"with_symbolic_algorithm: {name!r} is none of {SYMBOLIC_ALGORITHMS}")
+        self.symbolic_algorithm = name
+        return self
+
+
 def keep_counts(fill_in_limit, n_lower, n_upper):
     """(keep_L, keep_U): the entries a triangle of the threshold factors may hold beside ties"""
     return tuple(max(1, int(math.floor(fill_in_limit * count))) for count in (n_lower, n_upper))
@@ -166,6 +220,7 @@ class _Factorization:
         self.exec = factory.exec or a.exec
         self.size = a.size
         self.dtype = a.dtype
+        self._idx = a.col_idxs.dtype
         self._it = IT[a.col_idxs.dtype]
         self._suf = f"{VT[a.dtype]}_{self._it}"
 
@@ -321,6 +376,87 @@ class _Factorization:
         for _ in range(self.iterations):
             m = self._threshold_iteration(lower_only, a, src, m, self.keep)
         return m
+
+    # ---- Cholesky / Lu: the symbolic phase (include/gko_cdna4.h, "Symbolic Cholesky / sparse direct")
+    def _union_pattern(self, patterns):
+        """(row_ptrs, col_idxs) of the union of the sorted patterns [(rp, ci), ...]: their triplets side by side
+        through the triplet pipeline, all values 1"""
+        ex, n, idx = self.exec, self.size[0], patterns[0][1].dtype
+        total = sum(ci.numel() for _, ci in patterns)
+        rows, cols = ex.alloc((total,), idx), ex.alloc((total,), idx)
+        at = 0
+        for rp, ci in patterns:
+            call("gkoc_convert_ptrs_to_idxs_" + self._it, ex.stream, rp, n, rows[at:at + ci.numel()])
+            cols[at:at + ci.numel()].copy_(ci)
+            at += ci.numel()
+        data = DeviceMatrixData(ex, self.size, rows, cols, ex.alloc((total,), self.dtype).fill_(1))
+        data.sum_duplicates()
+        rp = Csr.read(data).row_ptrs
+        ex.synchronize()                # the triplets are released on return
+        return rp, data.col_idxs
+
+    def _symmetrized_lower(self, m):
+        """the lower triangle, diagonal last, of S = pattern(m) + pattern(m^T) for the prepared matrix m"""
+        ex = self.exec
+        mt = m.transpose()
+        return self._union_pattern([_lower_pattern(ex, self.size, x.row_ptrs, x.col_idxs, self.dtype)
+                                    for x in (m, mt)])
+
+    def _symbolic_cholesky(self, s_rp, s_ci):
+        """(row_ptrs, col_idxs) of L, rows sorted, from the lower triangle of S: the forest on the host, the rows
+        by the skeleton walk on the device, the sorted pattern from the triplet pipeline"""
+        ex, n, it, idx = self.exec, self.size[0], self._it, s_ci.dtype
+        nnz = s_ci.numel()
+        parent, post, first, inv_post = (ex.alloc((n,), idx) for _ in range(4))
+        call("gkoc_symbolic_forest_" + it, ex.stream, n, nnz, s_rp, s_ci, parent, post, first)
+        keys = ex.alloc((nnz,), idx)
+        call("gkoc_symbolic_post_keys_" + it, ex.stream, n, nnz, s_rp, s_ci, post, keys, inv_post)
+        # the row sort orders every row's neighbours by post rank; its values are not read afterwards
+        Csr(ex, self.size, ex.zeros((nnz,), self.dtype), keys, s_rp).sort_by_column_index()
+        offsets, total = ex.alloc((n + 1,), torch.int64), C.c_longlong(0)
+        forest = (ex.stream, n, nnz, s_rp, keys, parent, post, first, inv_post)
+        call("gkoc_symbolic_cholesky_count_" + it, *forest, offsets, C.byref(total))
+        # the pattern leaves as matrix_data entries (row, col, 1); the triplet pipeline takes them from there
+        t = total.value
+        width = entry_dtype(_np_dtype(self.dtype), _np_dtype(idx)).itemsize
+        entries = ex.alloc((t * width,), torch.uint8)
+        call("gkoc_symbolic_cholesky_expand_" + self._suf, *forest, offsets, t, entries)
+        rows, cols, vals = ex.alloc((t,), idx), ex.alloc((t,), idx), ex.alloc((t,), self.dtype)
+        call("gkoc_aos_to_soa_" + self._suf, ex.stream, t, entries, rows, cols, vals)
+        data = DeviceMatrixData(ex, self.size, rows, cols, vals)
+        data.sort_row_major()
+        rp = Csr.read(data).row_ptrs
+        ex.synchronize()                # the forest, the keys and the offsets are released on return
+        return rp, data.col_idxs
+
+    def _given_pattern(self, pattern, skip_sorting):
+        """the index arrays of a caller's pattern after the three checks it gets"""
+        name = type(self).__name__
+        if tuple(pattern.size) != tuple(self.size):
+            raise DimensionMismatch(f"factorization.{name}: the symbolic factorization is {tuple(pattern.size)}, "
+                                    f"the system matrix {tuple(self.size)}")
+        if pattern.col_idxs.dtype != self._idx:
+            raise NotSupported(f"factorization.{name}: the symbolic factorization has another index type")
+        if not skip_sorting and not pattern.is_sorted_by_column_index():
+            raise GkoError(f"factorization.{name}: the rows of the symbolic factorization are not sorted")
+        ex, n = self.exec, self.size[0]
+        shift, missing = ex.alloc((n + 1,), self._idx), C.c_int64(0)
+        call("gkoc_csr_missing_diagonal_shift_" + self._it, ex.stream, n, n, pattern.row_ptrs, pattern.col_idxs,
+             shift, C.byref(missing))
+        if missing.value:
+            raise GkoError(f"factorization.{name}: {missing.value} rows of the symbolic factorization store no "
+                           "diagonal entry")
+        return pattern.row_ptrs, pattern.col_idxs
+
+    def _on_pattern(self, rp, ci, src):
+        """a Csr on a copy of the pattern in the matrix' memory classes, with the values of `src` gathered"""
+        ex, idx = self.exec, ci.dtype
+        m_rp, m_ci = ex.alloc((rp.numel(),), idx, MEM_INDICES), ex.alloc((ci.numel(),), idx, MEM_INDICES)
+        m_v = ex.alloc((ci.numel(),), src.dtype, MEM_VALUES)
+        m_rp.copy_(rp)
+        m_ci.copy_(ci)
+        m_v.copy_(self._gather(rp, ci, src))
+        return Csr(ex, self.size, m_v, m_ci, m_rp)
 
     def last_sweep_changes(self):
         """the number of entries whose bits the last sweep changed; 0: the factors are a fixed point of the
@@ -482,3 +618,79 @@ class ParIct(_Factorization):
 
     def get_lt_factor(self):
         return self.lt
+
+
+class Cholesky(_Factorization):
+    """A = L L^T exactly, up to rounding: the contract of Ic on the pattern of L that the symbolic phase computes
+    (or that `with_symbolic_factorization` gives).  Reads the lower triangle of A."""
+
+    @staticmethod
+    def build():
+        return _CholeskyFactory(Cholesky)
+
+    def __init__(self, factory, a):
+        super().__init__(factory, a)
+        ex = self.exec
+        m = self._prepared(factory, a)
+        if factory.symbolic is None:
+            rp, ci = self._symbolic_cholesky(*self._symmetrized_lower(m))
+        else:
+            rp, ci = _lower_pattern(ex, self.size, *self._given_pattern(factory.symbolic, factory.skip_sorting),
+                                    self.dtype)
+        self.l = self._on_pattern(rp, ci, self._split(m, False))
+        self._factorize("gkoc_ic_factorize_", self.l)
+        self.both_factors = factory.both_factors
+        self.lt = self.l.transpose() if self.both_factors else None
+        self._symbolic = None
+        ex.synchronize()                # the prepared copy and the pattern's first copy are released on return
+
+    def get_l_factor(self):
+        return self.l
+
+    def get_lt_factor(self):
+        return self.lt
+
+    def get_symbolic(self):
+        """the pattern of L as a Csr of ones on the factor's own index arrays"""
+        if self._symbolic is None:
+            ones = self.exec.alloc((self.l.values.numel(),), self.dtype, MEM_VALUES).fill_(1)
+            self._symbolic = Csr(self.exec, self.size, ones, self.l.col_idxs, self.l.row_ptrs)
+        return self._symbolic
+
+
+class Lu(_Factorization):
+    """A = L U exactly, up to rounding, without pivoting: the contract of Ilu on the combined pattern - row i of
+    the symbolic Cholesky factor of the symmetrised pattern, then row i of its transpose - or on the pattern that
+    `with_symbolic_factorization` gives.  L has a unit diagonal, stored last; U its diagonal first."""
+
+    @staticmethod
+    def build():
+        return _LuFactory(Lu)
+
+    def __init__(self, factory, a):
+        super().__init__(factory, a)
+        ex = self.exec
+        self.symbolic_algorithm = factory.symbolic_algorithm
+        m = self._prepared(factory, a)
+        if factory.symbolic is None:
+            rp, ci = self._symbolic_cholesky(*self._symmetrized_lower(m))
+            low = Csr(ex, self.size, ex.alloc((ci.numel(),), self.dtype).fill_(1), ci, rp)
+            up = low.transpose()
+            # both hold the diagonal: the pipeline keeps one
+            rp, ci = self._union_pattern([(low.row_ptrs, low.col_idxs), (up.row_ptrs, up.col_idxs)])
+        else:
+            rp, ci = self._given_pattern(factory.symbolic, factory.skip_sorting)
+        self.combined = self._on_pattern(rp, ci, m)
+        self._factorize("gkoc_ilu_factorize_", self.combined)
+        self.l, self.u = self._split(self.combined, True)
+        ex.synchronize()                # the prepared copy and the pattern's first copy are released on return
+
+    def get_l_factor(self):
+        return self.l
+
+    def get_u_factor(self):
+        return self.u
+
+    def get_combined(self):
+        """the factored matrix on the combined pattern: L strictly below the diagonal, U on and above it"""
+        return self.combined

@@ -530,13 +530,13 @@ class _Factorized(LinOp):
 
 class Ilu(_Factorized):
     """preconditioner::Ilu: z = U^-1 L^-1 r (with_reverse_apply(True): z = L^-1 U^-1 r) with the
-    level-scheduled triangular solvers.  `generate` takes a factorization.Ilu / ParIlu / ParIlut object or a system
+    level-scheduled triangular solvers.  `generate` takes a factorization.Ilu / ParIlu / ParIlut / Lu object or a system
     matrix.  A system matrix is factorized here with the exact ILU(0) of factorization.Ilu - Ginkgo's default
     at this place is the iterative ParIlu, which `with_factorization(factorization.ParIlu.build()...)` selects:
     no level schedule is built for the factorization then.  `with_l_solver` / `with_u_solver` take a factory
     for the solver of either factor (e.g. LowerIsai / UpperIsai); default LowerTrs / UpperTrs."""
     _FACTORIZATION = _factorization.Ilu
-    _FACTORIZATIONS = (_factorization.Ilu, _factorization.ParIlu, _factorization.ParIlut)
+    _FACTORIZATIONS = (_factorization.Ilu, _factorization.ParIlu, _factorization.ParIlut, _factorization.Lu)
 
     @staticmethod
     def build():
@@ -553,13 +553,13 @@ class Ilu(_Factorized):
 
 class Ic(_Factorized):
     """preconditioner::Ic: z = L^-T L^-1 r with the level-scheduled triangular solvers.  `generate` takes
-    a factorization.Ic / ParIc / ParIct object or a system matrix.  A system matrix is factorized here with the exact
+    a factorization.Ic / ParIc / ParIct / Cholesky object or a system matrix.  A system matrix is factorized here with the exact
     IC(0) of factorization.Ic - Ginkgo's default at this place is the iterative ParIc, which
     `with_factorization(factorization.ParIc.build()...)` selects.  `with_l_solver` takes a factory for the solver S of L (e.g. LowerIsai); the solver of L^T is then
     S.transpose(), as in Ginkgo, so that z = S^T S r stays symmetric - a solver without transpose() (LowerTrs)
     is refused there."""
     _FACTORIZATION = _factorization.Ic
-    _FACTORIZATIONS = (_factorization.Ic, _factorization.ParIc, _factorization.ParIct)
+    _FACTORIZATIONS = (_factorization.Ic, _factorization.ParIc, _factorization.ParIct, _factorization.Cholesky)
 
     @staticmethod
     def build():

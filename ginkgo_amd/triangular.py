@@ -7,14 +7,22 @@ sparsity pattern once (lower_trs::generate: the level of every row, rows grouped
 more than `wide_threshold` rows, one single-workgroup launch per run of smaller levels.  The result
 is the reference's row-by-row loop bit for bit.  The full matrix may be passed: entries on the other
 side of the diagonal are ignored.
+
+`Direct` - mirror of include/ginkgo/core/solver/direct.hpp (experimental::solver::Direct) - solves A x = b
+exactly, up to rounding: `Direct.build().with_factorization(f).with_num_rhs(k).on(exec).generate(a)` factorizes
+with factorization.Lu (the default) or factorization.Cholesky and applies the two level-scheduled solves, L (unit
+diagonal for Lu) then U or L^T.  The vectors it needs are allocated at generate time for `num_rhs` columns, so an
+application enqueues kernels only and can be captured.  No pivoting and no fill-reducing ordering
+(factorization.py).
 """
 import ctypes as C
 
 import numpy as np
 
+from . import factorization as _factorization
 from ._lib import IT, VT, DimensionMismatch, NotSupported, call, lib
 from .base import LinOp
-from .matrix import Csr
+from .matrix import Csr, Dense
 
 
 class _TrsFactory:
@@ -113,3 +121,88 @@ class UpperTrs(_Trs):
     @staticmethod
     def build():
         return _TrsFactory(UpperTrs)
+
+
+class _DirectFactory:
+    def __init__(self):
+        self.factorization = None
+        self.num_rhs = 1
+        self.exec = None
+
+    def with_factorization(self, factory):
+        """the factory of factorization.Lu (default) or factorization.Cholesky"""
+        self.factorization = factory
+        return self
+
+    def with_num_rhs(self, v):
+        """the number of right-hand sides the work vectors are allocated for at generate time; an application
+        with another number allocates its own on first use"""
+        self.num_rhs = int(v)
+        return self
+
+    def on(self, exec_):
+        self.exec = exec_
+        return self
+
+    def generate(self, system_matrix):
+        return Direct(self, system_matrix)
+
+
+class Direct(LinOp):
+    """x = U^-1 L^-1 b on the factors of factorization.Lu, x = L^-T L^-1 b on those of factorization.Cholesky.
+    `generate` takes a system matrix or a generated Lu / Cholesky object."""
+
+    @staticmethod
+    def build():
+        return _DirectFactory()
+
+    def __init__(self, factory, a):
+        kinds = (_factorization.Lu, _factorization.Cholesky)
+        ex = factory.exec or a.exec
+        if not isinstance(a, kinds):
+            a = (factory.factorization or _factorization.Lu.build()).on(ex).generate(a)
+            if not isinstance(a, kinds):
+                raise NotSupported(f"Direct: with_factorization gave a {type(a).__name__}; a direct solve needs "
+                                   "factorization.Lu or factorization.Cholesky")
+        super().__init__(ex, a.size)
+        self.factorization, self.dtype = a, a.dtype
+        if isinstance(a, _factorization.Lu):
+            lower, upper, unit = a.get_l_factor(), a.get_u_factor(), True
+        else:
+            lt = a.get_lt_factor()
+            lower, upper, unit = a.get_l_factor(), a.get_l_factor().transpose() if lt is None else lt, False
+        self._lower = LowerTrs.build().with_unit_diagonal(unit).on(ex).generate(lower)
+        self._upper = UpperTrs.build().on(ex).generate(upper)
+        self._vectors = {}
+        self._work(max(1, factory.num_rhs))
+
+    def _work(self, cols):
+        """(the vector between the solves, the result of the advanced form) for `cols` right-hand sides"""
+        vs = self._vectors.get(cols)
+        if vs is None:
+            vs = self._vectors[cols] = tuple(Dense.create(self.exec, (self.size[0], cols), self.dtype)
+                                             for _ in range(2))
+        return vs
+
+    def get_lower_solver(self):
+        return self._lower
+
+    def get_upper_solver(self):
+        return self._upper
+
+    def get_factorization(self):
+        return self.factorization
+
+    def apply_impl(self, b, x):
+        if b.dtype != self.dtype or x.dtype != self.dtype:
+            raise NotSupported("Direct: vectors must have the matrix' value type")
+        tmp = self._work(b.size[1])[0]
+        self._lower.apply(b, tmp)
+        self._upper.apply(tmp, x)
+
+    def apply_advanced_impl(self, alpha, b, beta, x):
+        # x = beta * x + alpha * solve(b)
+        solved = self._work(b.size[1])[1]
+        self.apply_impl(b, solved)
+        x.scale(beta)
+        x.add_scaled(alpha, solved)

@@ -2827,6 +2827,75 @@ GKOC_DECL_PAR_ILUT(double, f64, int64_t, i64)
 GKOC_DECL_PAR_ILUT(float, f32, int32_t, i32)
 GKOC_DECL_PAR_ILUT(float, f32, int64_t, i64)
 
+/* ------------------------------------- Symbolic Cholesky / sparse direct (factorization::Cholesky / Lu,
+ * solver::Direct; Ginkgo's experimental::factorization::{Cholesky, Lu} and experimental::solver::Direct)
+ * The NUMERIC phase of the direct factorizations has no entry of its own: gkoc_ilu_factorize_* on a pattern that
+ * is closed under fill IS the LU factorization without pivoting, gkoc_ic_factorize_* on the filled lower triangle
+ * IS the Cholesky factorization, both bit for bit the loops stated above, and gkoc_par_ilut_gather_* places A on
+ * the filled pattern.  What is new is the SYMBOLIC phase, the pattern of L.  It is integer-exact:
+ *   S = pattern(A) + pattern(A^T) + every diagonal.  Row i of L holds exactly the columns j <= i of the filled
+ *   pattern of S: j == i, or S has a path from i to j whose inner vertices are all smaller than j.  Rows sorted
+ *   by column, so the diagonal is last.  (tests/symbolic_refs.py restates this with row marks and pins it
+ *   against boolean dense elimination.)
+ * The pieces, in the order the classes call them (n = rows, every index array of type I):
+ * forest: from the sorted rows (row_ptrs, col_idxs) of S - only the entries left of the diagonal are read, so
+ *   S or its lower triangle may be passed - the elimination forest parent[] (parent[v] > v, -1 for a root), a
+ *   postorder rank post[] (children visited in ascending index, roots in ascending index: the order is fixed)
+ *   and first[v] = the smallest post rank in the subtree of v.  Liu's algorithm with path compression ON THE
+ *   HOST from a copy of the pattern, like gkoc_lower_trs_generate_*; the three arrays are written to the device.
+ * post_keys: (row_ptrs, col_idxs) is the LOWER triangle of S, rows sorted, the diagonal stored and therefore
+ *   last.  keys[k] = post[col_idxs[k]] (same row pointers), inv_post[post[v]] = v.  The caller then sorts every
+ *   row of (row_ptrs, keys) ascending with the row sort (gkoc_csr_sort_by_column_index_*).  Because every
+ *   strictly-lower neighbour of i is a descendant of i, post[i] stays the last key of row i.
+ * cholesky_count / cholesky_expand: (row_ptrs, keys) as sorted above: the post ranks p_1 < ... < p_k of row i's
+ *   strictly-lower neighbours, then post[i].  Lane t walks a = inv_post[p_t], parent[a], ... and emits every a
+ *   that is below i and NOT an ancestor of q, q the node of rank p_{t+1} (q = i for the last lane); a is an
+ *   ancestor of q  <=>  first[a] <= post[q] <= post[a].  The emitted sets are disjoint and their union plus
+ *   {i} is row i of L: no marks, no atomics, one parent look-up per entry of L.
+ *   count writes offsets[0 .. n] (int64): where row i's triplets start, offsets[n] = *total_host = nnz(L).
+ *   expand writes the entries (row, col, 1) of L as matrix_data entries (struct { I row; I column; T value; },
+ *   natural alignment: the layout of gkoc_aos_to_soa_*), entry p in [offsets[i], offsets[i + 1]) for row i,
+ *   unordered inside a row, and nothing at a position outside [0, total).  gkoc_aos_to_soa_*,
+ *   gkoc_sort_row_major_* and gkoc_convert_idxs_to_ptrs_* make the sorted Csr pattern from them.
+ * The outputs are shaped like those of the Pgm entries below: the forest arrays, the keys, inv_post and the
+ * offsets are STATE of the symbolic factorization, typed by the index width of the entry (gkoc_symbolic_i32 /
+ * gkoc_symbolic_i64) - never row_ptrs or col_idxs of a matrix, so the entries that write them do not belong to
+ * the column-offset plan's contract and notify nothing; the pattern leaves expand as matrix_data entries and
+ * becomes index arrays only through gkoc_aos_to_soa and gkoc_sort_row_major, which the contract lists.  Host
+ * results are long long.
+ * GKOC_E_INVALID before any kernel indexes with the inputs, the outputs untouched: negative sizes, null pointers,
+ * row pointers that do not ascend from 0 to nnz, a column (key) outside [0, n); post_keys: post is no
+ * permutation; count / expand: parent[v] neither -1 nor inside (v, n), post and inv_post not inverse
+ * permutations of each other, a row that is empty or does not end with post[row].  n == 0 is GKOC_OK.
+ * Set-up calls: forest synchronises for its copies; post_keys and expand take scratch from the arena and
+ * synchronise once for the checks, count once more for the total.  They are not meant to be captured.
+ * Kernels: one group of 16 / 32 / 64 lanes per row, lane = stored strictly-lower entry, chosen per call from the
+ * most strictly-lower entries of a row at the limits gkoc_symbolic_row_limits reports (ascending, at most 4);
+ * a row beyond the last limit is streamed in rounds of 64 entries.  No length cap, no serial path. */
+typedef int32_t gkoc_symbolic_i32;
+typedef int64_t gkoc_symbolic_i64;
+int gkoc_symbolic_row_limits(int* limits_host, int* count_host);
+#define GKOC_DECL_SYMBOLIC(I, A, IN)                                                                         \
+    int gkoc_symbolic_forest_##IN(gkoc_stream_t s, int64_t n, int64_t nnz, const I* row_ptrs,                \
+                                  const I* col_idxs, A* parent, A* post, A* first);                          \
+    int gkoc_symbolic_post_keys_##IN(gkoc_stream_t s, int64_t n, int64_t nnz, const I* row_ptrs,             \
+                                     const I* col_idxs, const I* post, A* keys, A* inv_post);                \
+    int gkoc_symbolic_cholesky_count_##IN(gkoc_stream_t s, int64_t n, int64_t nnz, const I* row_ptrs,        \
+                                          const I* keys, const I* parent, const I* post, const I* first,     \
+                                          const I* inv_post, gkoc_symbolic_i64* offsets,                     \
+                                          long long* total_host);
+GKOC_DECL_SYMBOLIC(int32_t, gkoc_symbolic_i32, i32)
+GKOC_DECL_SYMBOLIC(int64_t, gkoc_symbolic_i64, i64)
+#define GKOC_DECL_SYMBOLIC_EXPAND(T, TN, I, IN)                                                              \
+    int gkoc_symbolic_cholesky_expand_##TN##_##IN(                                                           \
+        gkoc_stream_t s, int64_t n, int64_t nnz, const I* row_ptrs, const I* keys, const I* parent,          \
+        const I* post, const I* first, const I* inv_post, const int64_t* offsets, int64_t total,             \
+        void* entries);
+GKOC_DECL_SYMBOLIC_EXPAND(double, f64, int32_t, i32)
+GKOC_DECL_SYMBOLIC_EXPAND(double, f64, int64_t, i64)
+GKOC_DECL_SYMBOLIC_EXPAND(float, f32, int32_t, i32)
+GKOC_DECL_SYMBOLIC_EXPAND(float, f32, int64_t, i64)
+
 /* ------------------------------------- triangular ISAI (preconditioner::LowerIsai / UpperIsai)
  * isai::generate_tri_inverse (reference/preconditioner/isai_kernels.cpp): the incomplete sparse approximate
  * inverse W of a triangular matrix A on a given pattern, (W A)(i, S_i) = e_i(S_i) for every row i, S_i = the
