@@ -131,6 +131,13 @@ def call(name, *args):
         _tape.keep.append(args)
 
 
+def row_limits(entry_name):
+    """the row lengths at which a set-up kernel changes path, from its gkoc_*_row_limits entry"""
+    limits, count = (C.c_int * 4)(), C.c_int(0)
+    call(entry_name, limits, C.byref(count))
+    return [int(limits[p]) for p in range(count.value)]
+
+
 def bump(counter):
     """counter.value += 1 (a ctypes integer that is passed by value to later calls), now and
     again at this point of every replay of the tape being recorded: arguments of recorded calls

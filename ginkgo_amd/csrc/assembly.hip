@@ -28,13 +28,6 @@ namespace {
 
 inline size_t align_up(size_t v) { return (v + 255) / 256 * 256; }
 
-inline unsigned grid_for(int64_t n)
-{
-    int64_t b = ceildiv(n > 0 ? n : 1, 256);
-    if (b > 4 * max_stream_blocks) b = 4 * max_stream_blocks;
-    return unsigned(b);
-}
-
 // Ginkgo's matrix_data_entry<T, I> (matrix_data.hpp:60): { I row; I column; T value; }
 template <typename T, typename I>
 struct md_entry {
@@ -211,7 +204,7 @@ extern "C" size_t gkoc_compact_workspace_bytes(int64_t nnz)
                                                const T* vals, void* entries)                \
     {                                                                                       \
         if (nnz <= 0) return GKOC_OK;                                                       \
-        soa_to_aos_kernel<T, I><<<dim3(grid_for(nnz)), dim3(256), 0, as_stream(s)>>>(       \
+        soa_to_aos_kernel<T, I><<<dim3(stream_grid(nnz)), dim3(256), 0, as_stream(s)>>>(    \
             nnz, row_idxs, col_idxs, vals, static_cast<md_entry<T, I>*>(entries));          \
         GKOC_LAUNCH_OK();                                                                   \
         return GKOC_OK;                                                                     \
@@ -236,7 +229,7 @@ extern "C" size_t gkoc_compact_workspace_bytes(int64_t nnz)
         T* e = reinterpret_cast<T*>(w + 4 * seg);                                           \
         void* scratch = w + 4 * seg + align_up(size_t(nnz) * sizeof(T));                    \
         size_t scratch_bytes = sort_scratch_bytes<I>(nnz);                                  \
-        const dim3 grid(grid_for(nnz));                                                     \
+        const dim3 grid(stream_grid(nnz));                                                  \
         const int bits = int(8 * sizeof(I));                                                \
         iota_kernel<I><<<grid, dim3(256), 0, st>>>(nnz, a);                                 \
         GKOC_LAUNCH_OK();                                                                   \
@@ -267,7 +260,7 @@ extern "C" size_t gkoc_compact_workspace_bytes(int64_t nnz)
         gkoc::csr_structure_written(out_rows); gkoc::csr_structure_written(out_cols);       \
         if (nnz <= 0) return GKOC_OK;                                                       \
         GKOC_REQUIRE(work, GKOC_E_WORKSPACE, "null workspace");                             \
-        compact_kernel<T, I><<<dim3(grid_for(nnz)), dim3(256), 0, as_stream(s)>>>(          \
+        compact_kernel<T, I><<<dim3(stream_grid(nnz)), dim3(256), 0, as_stream(s)>>>(       \
             nnz, static_cast<const int64_t*>(work), row_idxs, col_idxs, vals, out_rows,     \
             out_cols, out_vals);                                                            \
         GKOC_LAUNCH_OK();                                                                   \
@@ -280,7 +273,7 @@ extern "C" size_t gkoc_compact_workspace_bytes(int64_t nnz)
         gkoc::csr_structure_written(out_rows); gkoc::csr_structure_written(out_cols);       \
         if (nnz <= 0) return GKOC_OK;                                                       \
         GKOC_REQUIRE(work, GKOC_E_WORKSPACE, "null workspace");                             \
-        sum_runs_kernel<T, I><<<dim3(grid_for(nnz)), dim3(256), 0, as_stream(s)>>>(         \
+        sum_runs_kernel<T, I><<<dim3(stream_grid(nnz)), dim3(256), 0, as_stream(s)>>>(      \
             nnz, static_cast<const int64_t*>(work), row_idxs, col_idxs, vals, out_rows,     \
             out_cols, out_vals);                                                            \
         GKOC_LAUNCH_OK();                                                                   \
@@ -307,7 +300,7 @@ GKOC_DEF_ASSEMBLY(gkoc_c64, c64, int64_t, i64)
         if (nnz <= 0) return GKOC_OK;                                                       \
         GKOC_REQUIRE(work && work_bytes >= compact_work_bytes(nnz), GKOC_E_WORKSPACE,       \
                      "workspace too small (gkoc_compact_workspace_bytes)");                 \
-        mark_nonzeros_kernel<T><<<dim3(grid_for(nnz + 1)), dim3(256), 0, as_stream(s)>>>(   \
+        mark_nonzeros_kernel<T><<<dim3(stream_grid(nnz + 1)), dim3(256), 0, as_stream(s)>>>(   \
             nnz, vals, static_cast<int64_t*>(work));                                        \
         GKOC_LAUNCH_OK();                                                                   \
         return scan_and_count(as_stream(s), nnz, work, count_host);                         \
@@ -328,7 +321,7 @@ GKOC_DEF_COUNT_NZ(gkoc_c64, c64)
         if (nnz <= 0) return GKOC_OK;                                                       \
         GKOC_REQUIRE(work && work_bytes >= compact_work_bytes(nnz), GKOC_E_WORKSPACE,       \
                      "workspace too small (gkoc_compact_workspace_bytes)");                 \
-        mark_run_heads_kernel<I><<<dim3(grid_for(nnz + 1)), dim3(256), 0, as_stream(s)>>>(  \
+        mark_run_heads_kernel<I><<<dim3(stream_grid(nnz + 1)), dim3(256), 0, as_stream(s)>>>(  \
             nnz, row_idxs, col_idxs, static_cast<int64_t*>(work));                          \
         GKOC_LAUNCH_OK();                                                                   \
         return scan_and_count(as_stream(s), nnz, work, count_host);                         \

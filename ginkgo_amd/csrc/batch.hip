@@ -403,12 +403,7 @@ int solve(gkoc_stream_t s, int64_t items, int64_t n, int64_t stored, const int32
 }
 
 // ------------------------------------------------------------------ apply
-inline unsigned flat_grid(int64_t total)
-{
-    int64_t blocks = ceildiv(total, batch_block);
-    if (blocks > 4 * max_stream_blocks) blocks = 4 * max_stream_blocks;
-    return unsigned(blocks < 1 ? 1 : blocks);
-}
+inline unsigned flat_grid(int64_t total) { return stream_grid(total, batch_block); }
 
 // one thread per (item, row, col): x = A b, or x = alpha[item] * (A b) + beta[item] * x
 template <int FMT, bool ADVANCED, typename T>
@@ -651,15 +646,6 @@ __global__ __launch_bounds__(batch_block) void ell_check_kernel(int64_t n_rows, 
         if (c < -1 || c >= n_cols) flags[0] = 1;
     }
 }
-
-struct scratch_guard {
-    hipStream_t st;
-    void* ptr;
-    ~scratch_guard()
-    {
-        if (ptr) (void)scratch_free(st, ptr);
-    }
-};
 
 int csr_check(gkoc_stream_t s, int64_t n_rows, int64_t n_cols, int64_t nnz, const int32_t* rp, const int32_t* ci)
 {

@@ -689,9 +689,7 @@ int cb_restart_impl(hipStream_t st, const cb_args& a, const T* residual, int64_t
                 GKOC_HIP(hipMemsetAsync(static_cast<S*>(a.bases) + a.st0, 0,
                                         size_t(a.krylov_dim) * size_t(a.st0) * sizeof(S), st));
             } else {
-                int64_t zb = ceildiv(a.krylov_dim * a.rows * a.nrhs, 256);
-                if (zb > 4 * max_stream_blocks) zb = 4 * max_stream_blocks;
-                cb_zero_bases_kernel<S><<<unsigned(zb), 256, 0, st>>>(
+                cb_zero_bases_kernel<S><<<stream_grid(a.krylov_dim * a.rows * a.nrhs), 256, 0, st>>>(
                     a.rows, a.nrhs, a.krylov_dim, static_cast<S*>(a.bases), a.st0, a.st1);
             }
         }

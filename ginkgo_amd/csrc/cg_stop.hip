@@ -599,10 +599,8 @@ GKOC_DEF_CG_STEPS(gkoc_c64, c64)
         const T* b, int64_t ldb, T* x, int64_t ldx)                            \
     {                                                                          \
         if (rows <= 0 || cols <= 0) return GKOC_OK;                            \
-        int64_t blocks = ceildiv(rows * cols, 256);                            \
-        if (blocks > 4 * max_stream_blocks) blocks = 4 * max_stream_blocks;    \
         scalar_jacobi_kernel<T, false>                                         \
-            <<<dim3(unsigned(blocks)), dim3(256), 0, as_stream(s)>>>(          \
+            <<<dim3(stream_grid(rows * cols)), dim3(256), 0, as_stream(s)>>>(  \
                 rows, cols, inv_diag, nullptr, b, ldb, nullptr, x, ldx);       \
         GKOC_LAUNCH_OK();                                                      \
         return GKOC_OK;                                                        \
@@ -614,10 +612,8 @@ GKOC_DEF_CG_STEPS(gkoc_c64, c64)
     {                                                                          \
         if (rows <= 0 || cols <= 0) return GKOC_OK;                            \
         GKOC_REQUIRE(alpha && beta, GKOC_E_INVALID, "null alpha/beta");        \
-        int64_t blocks = ceildiv(rows * cols, 256);                            \
-        if (blocks > 4 * max_stream_blocks) blocks = 4 * max_stream_blocks;    \
         scalar_jacobi_kernel<T, true>                                          \
-            <<<dim3(unsigned(blocks)), dim3(256), 0, as_stream(s)>>>(          \
+            <<<dim3(stream_grid(rows * cols)), dim3(256), 0, as_stream(s)>>>(  \
                 rows, cols, inv_diag, alpha, b, ldb, beta, x, ldx);            \
         GKOC_LAUNCH_OK();                                                      \
         return GKOC_OK;                                                        \

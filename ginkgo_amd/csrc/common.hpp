@@ -8,6 +8,7 @@
 
 #include "complex_type.hpp"
 #include "gko_cdna4.h"
+#include "launch_shape.hpp"
 
 namespace gkoc {
 
@@ -15,6 +16,11 @@ constexpr int wave_size = 64;
 // grid cap for HBM-bound grid-stride kernels: 256 CUs x 8 resident blocks
 // of 256 threads (cdna_hip_programming.md, Guideline 11)
 constexpr int max_stream_blocks = 2048;
+// the grid of a grid-stride kernel over `items` (launch_shape.hpp); a file with another block size or cap says so
+inline unsigned stream_grid(int64_t items, int per_block = 256, int64_t cap = 4 * max_stream_blocks)
+{
+    return capped_grid(items, per_block, cap);
+}
 
 void set_last_error(const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what, const char* file, int line);
@@ -66,6 +72,16 @@ size_t arena_allocation_bytes(const void* ptr);
 // sporadically wrong flags and scan offsets in Ginkgo's own test-suite.
 int scratch_malloc(hipStream_t st, void** ptr, size_t bytes);
 int scratch_free(hipStream_t st, void* ptr);
+// hands a scratch allocation back when the entry returns, on every path (hidden: the library exports no
+// symbol of it where its destructor is not inlined)
+struct __attribute__((visibility("hidden"))) scratch_guard {
+    hipStream_t st;
+    void* ptr;
+    ~scratch_guard()
+    {
+        if (ptr) (void)scratch_free(st, ptr);
+    }
+};
 
 #define GKOC_TRY(call)                              \
     do {                                            \

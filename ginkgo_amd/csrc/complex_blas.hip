@@ -53,13 +53,6 @@ __device__ __forceinline__ bool is_zero(cx<R> a) { return a.re == R(0) && a.im =
 template <typename R>
 __device__ __forceinline__ bool is_zero(R a) { return a == R(0); }
 
-inline unsigned grid_of(int64_t n)
-{
-    int64_t b = ceildiv(n > 0 ? n : 1, 256);
-    if (b > 4 * max_stream_blocks) b = 4 * max_stream_blocks;
-    return unsigned(b);
-}
-
 #define GKOC_FOR2(idx, total)                                                                          \
     for (int64_t idx = int64_t(blockIdx.x) * 256 + threadIdx.x, idx##_s = int64_t(gridDim.x) * 256;     \
          idx < (total); idx += idx##_s)
@@ -443,7 +436,7 @@ int cx_axpy(gkoc_stream_t s, int64_t rows, int64_t cols, const void* alpha, int6
 {
     if (rows <= 0 || cols <= 0) return GKOC_OK;
     GKOC_REQUIRE(alpha && (alpha_cols == 1 || alpha_cols == cols), GKOC_E_INVALID, "bad alpha");
-    cx_axpy_kernel<R, S, OP><<<dim3(grid_of(rows * cols)), dim3(256), 0, as_stream(s)>>>(
+    cx_axpy_kernel<R, S, OP><<<dim3(stream_grid(rows * cols)), dim3(256), 0, as_stream(s)>>>(
         rows, cols, static_cast<const S*>(alpha), alpha_cols, static_cast<const cx<R>*>(x), ldx,
         static_cast<cx<R>*>(y), ldy);
     GKOC_LAUNCH_OK();
@@ -518,7 +511,7 @@ using namespace gkoc;
     {                                                                                                       \
         GKOC_REQUIRE(mode >= 0 && mode <= 3, GKOC_E_INVALID, "mode");                                       \
         if (rows <= 0 || cols <= 0) return GKOC_OK;                                                         \
-        cx_convert_kernel<R><<<dim3(grid_of(rows * cols)), dim3(256), 0, as_stream(s)>>>(rows, cols, in,    \
+        cx_convert_kernel<R><<<dim3(stream_grid(rows * cols)), dim3(256), 0, as_stream(s)>>>(rows, cols, in,    \
                                                                                         ld_in, out, ld_out, \
                                                                                         mode);              \
         GKOC_LAUNCH_OK();                                                                                   \
@@ -533,7 +526,7 @@ GKOC_DEF_CBLAS(gkoc_c64, c64, float)
                                                       P* gathered, int64_t ld_gathered)                     \
     {                                                                                                       \
         if (n_gather <= 0 || cols <= 0) return GKOC_OK;                                                     \
-        cx_row_gather_kernel<R, I><<<dim3(grid_of(n_gather * cols)), dim3(256), 0, as_stream(s)>>>(         \
+        cx_row_gather_kernel<R, I><<<dim3(stream_grid(n_gather * cols)), dim3(256), 0, as_stream(s)>>>(     \
             n_gather, cols, rows, reinterpret_cast<const cx<R>*>(orig), ld_orig,                            \
             reinterpret_cast<cx<R>*>(gathered), ld_gathered);                                               \
         GKOC_LAUNCH_OK();                                                                                   \
@@ -544,7 +537,7 @@ GKOC_DEF_CBLAS(gkoc_c64, c64, float)
                                                                int64_t ld)                                  \
     {                                                                                                       \
         if (nnz <= 0) return GKOC_OK;                                                                       \
-        cx_fill_in_kernel<R, I><<<dim3(grid_of(nnz)), dim3(256), 0, as_stream(s)>>>(                        \
+        cx_fill_in_kernel<R, I><<<dim3(stream_grid(nnz)), dim3(256), 0, as_stream(s)>>>(                    \
             nnz, rows, cols, reinterpret_cast<const cx<R>*>(vals), reinterpret_cast<cx<R>*>(out), ld);      \
         GKOC_LAUNCH_OK();                                                                                   \
         return GKOC_OK;                                                                                     \
@@ -587,7 +580,7 @@ GKOC_DEF_MEAN(float, f32)
     {                                                                                                       \
         GKOC_REQUIRE(mode == 0 || mode == 1, GKOC_E_INVALID, "mode");                                       \
         if (rows <= 0 || cols <= 0) return GKOC_OK;                                                         \
-        cx_abs_kernel<R><<<dim3(grid_of(rows * cols)), dim3(256), 0, as_stream(s)>>>(                       \
+        cx_abs_kernel<R><<<dim3(stream_grid(rows * cols)), dim3(256), 0, as_stream(s)>>>(                   \
             rows, cols, reinterpret_cast<cx<R>*>(x), ldx, out, ld_out, mode);                               \
         GKOC_LAUNCH_OK();                                                                                   \
         return GKOC_OK;                                                                                     \
@@ -634,7 +627,7 @@ GKOC_DEF_CABS(gkoc_c64, c64, float)
                                                    beta, y, ldy);                                           \
             if (rc_ != GKOC_E_NOT_SUPPORTED) return rc_;                                                    \
         }                                                                                                   \
-        const dim3 g(grid_of(rows * nrhs));                                                                 \
+        const dim3 g(stream_grid(rows * nrhs));                                                             \
         if (alpha) {                                                                                        \
             cx_csr_spmv_kernel<R, I, true><<<g, dim3(256), 0, as_stream(s)>>>(                              \
                 rows, nrhs, row_ptrs, col_idxs, reinterpret_cast<const cx<R>*>(vals),                       \
@@ -654,7 +647,7 @@ GKOC_DEF_CABS(gkoc_c64, c64, float)
     {                                                                                                       \
         GKOC_REQUIRE(mode == 0 || mode == 1, GKOC_E_INVALID, "mode");                                       \
         if (rows <= 0) return GKOC_OK;                                                                      \
-        csr_row_scan_kernel<cx<R>, I><<<dim3(grid_of(rows)), dim3(256), 0, as_stream(s)>>>(                 \
+        csr_row_scan_kernel<cx<R>, I><<<dim3(stream_grid(rows)), dim3(256), 0, as_stream(s)>>>(             \
             rows, row_ptrs, col_idxs, reinterpret_cast<const cx<R>*>(vals), reinterpret_cast<cx<R>*>(out),  \
             mode);                                                                                          \
         GKOC_LAUNCH_OK();                                                                                   \
@@ -672,7 +665,7 @@ GKOC_DEF_CCSR(gkoc_c64, c64, float, int64_t, i64)
                                                               const I* row_ptrs, const T* vals, T* sums)    \
     {                                                                                                       \
         if (rows <= 0) return GKOC_OK;                                                                      \
-        csr_row_scan_kernel<T, I><<<dim3(grid_of(rows)), dim3(256), 0, as_stream(s)>>>(rows, row_ptrs,      \
+        csr_row_scan_kernel<T, I><<<dim3(stream_grid(rows)), dim3(256), 0, as_stream(s)>>>(rows, row_ptrs,  \
                                                                                       nullptr, vals, sums,  \
                                                                                       1);                   \
         GKOC_LAUNCH_OK();                                                                                   \
@@ -687,7 +680,7 @@ GKOC_DEF_RWAS(float, f32, int64_t, i64)
     extern "C" int gkoc_cjacobi_invert_diagonal_##TN(gkoc_stream_t s, int64_t n, const P* diag, P* inv)     \
     {                                                                                                       \
         if (n <= 0) return GKOC_OK;                                                                         \
-        cx_invert_kernel<R><<<dim3(grid_of(n)), dim3(256), 0, as_stream(s)>>>(                              \
+        cx_invert_kernel<R><<<dim3(stream_grid(n)), dim3(256), 0, as_stream(s)>>>(                          \
             n, reinterpret_cast<const cx<R>*>(diag), reinterpret_cast<cx<R>*>(inv));                        \
         GKOC_LAUNCH_OK();                                                                                   \
         return GKOC_OK;                                                                                     \
@@ -699,7 +692,7 @@ GKOC_DEF_RWAS(float, f32, int64_t, i64)
     {                                                                                                       \
         if (rows <= 0 || cols <= 0) return GKOC_OK;                                                         \
         GKOC_REQUIRE((alpha == nullptr) == (beta == nullptr), GKOC_E_INVALID, "alpha and beta go together");\
-        const dim3 g(grid_of(rows * cols));                                                                 \
+        const dim3 g(stream_grid(rows * cols));                                                             \
         if (alpha) {                                                                                        \
             cx_row_scale_kernel<R, true><<<g, dim3(256), 0, as_stream(s)>>>(                                \
                 rows, cols, reinterpret_cast<const cx<R>*>(diag), reinterpret_cast<const cx<R>*>(alpha),    \
@@ -724,7 +717,7 @@ GKOC_DEF_CJAC(gkoc_c64, c64, float)
     {                                                                                                       \
         GKOC_REQUIRE(mode >= 0 && mode <= 2, GKOC_E_INVALID, "mode");                                       \
         if (n_rows <= 0) return GKOC_OK;                                                                    \
-        cx_csr_scale_kernel<R, I><<<dim3(grid_of(n_rows)), dim3(256), 0, as_stream(s)>>>(                   \
+        cx_csr_scale_kernel<R, I><<<dim3(stream_grid(n_rows)), dim3(256), 0, as_stream(s)>>>(               \
             n_rows, row_ptrs, col_idxs, reinterpret_cast<const cx<R>*>(diag), mode,                         \
             reinterpret_cast<cx<R>*>(vals));                                                                \
         GKOC_LAUNCH_OK();                                                                                   \
@@ -743,7 +736,7 @@ GKOC_DEF_CCSR_SCALE(gkoc_c64, c64, float, int64_t, i64)
     {                                                                                                       \
         GKOC_REQUIRE(out_bytes == 4 || out_bytes == 8, GKOC_E_INVALID, "out_bytes");                        \
         if (rows <= 0) return GKOC_OK;                                                                      \
-        cx_dense_count_kernel<R><<<dim3(grid_of(rows)), dim3(256), 0, as_stream(s)>>>(                      \
+        cx_dense_count_kernel<R><<<dim3(stream_grid(rows)), dim3(256), 0, as_stream(s)>>>(                  \
             rows, cols, reinterpret_cast<const cx<R>*>(in), ld, out, out_bytes);                            \
         GKOC_LAUNCH_OK();                                                                                   \
         return GKOC_OK;                                                                                     \
@@ -756,7 +749,7 @@ GKOC_DEF_CDENSE_CSR(gkoc_c64, c64, float)
     {                                                                                                       \
         gkoc::csr_structure_written(out_cols);                                                              \
         if (rows <= 0) return GKOC_OK;                                                                      \
-        cx_dense_to_csr_kernel<R, I><<<dim3(grid_of(rows)), dim3(256), 0, as_stream(s)>>>(                  \
+        cx_dense_to_csr_kernel<R, I><<<dim3(stream_grid(rows)), dim3(256), 0, as_stream(s)>>>(              \
             rows, cols, reinterpret_cast<const cx<R>*>(in), ld, row_ptrs, out_cols,                         \
             reinterpret_cast<cx<R>*>(out_vals));                                                            \
         GKOC_LAUNCH_OK();                                                                                   \
@@ -774,7 +767,7 @@ GKOC_DEF_CDENSE_CSR_I(gkoc_c64, c64, float, int64_t, i64)
                                                int64_t ldb, P* c, int64_t ldc)                              \
     {                                                                                                       \
         if (nnz <= 0 || nrhs <= 0) return GKOC_OK;                                                          \
-        cx_coo_spmv2_kernel<R, I><<<dim3(grid_of(nnz * nrhs)), dim3(256), 0, as_stream(s)>>>(               \
+        cx_coo_spmv2_kernel<R, I><<<dim3(stream_grid(nnz * nrhs)), dim3(256), 0, as_stream(s)>>>(           \
             nnz, nrhs, rows, cols, reinterpret_cast<const cx<R>*>(vals),                                    \
             reinterpret_cast<const cx<R>*>(alpha), reinterpret_cast<const cx<R>*>(b), ldb,                  \
             reinterpret_cast<cx<R>*>(c), ldc);                                                              \

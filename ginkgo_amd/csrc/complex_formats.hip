@@ -77,12 +77,7 @@ __global__ __launch_bounds__(256) void cx_sellp_spmv_kernel(int64_t rows, int64_
     }
 }
 
-inline unsigned blocks_for(int64_t n)
-{
-    int64_t b = ceildiv(n > 0 ? n : 1, 256);
-    if (b > 8 * max_stream_blocks) b = 8 * max_stream_blocks;
-    return unsigned(b);
-}
+inline unsigned blocks_for(int64_t n) { return capped_grid(n, 256, 8 * max_stream_blocks); }
 
 }  // namespace
 }  // namespace gkoc

@@ -13,13 +13,6 @@
 namespace gkoc {
 namespace {
 
-inline unsigned cv_grid(int64_t n)
-{
-    int64_t b = ceildiv(n, 256);
-    if (b > 4 * max_stream_blocks) b = 4 * max_stream_blocks;
-    return unsigned(b < 1 ? 1 : b);
-}
-
 #define GKOC_FOR_EACH(i, n) \
     for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < (n); i += int64_t(gridDim.x) * 256)
 
@@ -887,7 +880,7 @@ __global__ __launch_bounds__(256) void add_diagonal_fill_kernel(int64_t n_rows, 
 #define CV_LAUNCH(kernel, n, ...)                                                     \
     do {                                                                              \
         if ((n) > 0) {                                                                \
-            kernel<<<dim3(cv_grid(n)), dim3(256), 0, as_stream(s)>>>(__VA_ARGS__);    \
+            kernel<<<dim3(stream_grid(n)), dim3(256), 0, as_stream(s)>>>(__VA_ARGS__);    \
             GKOC_LAUNCH_OK();                                                         \
         }                                                                             \
     } while (0)

@@ -34,12 +34,7 @@
 namespace gkoc {
 namespace {
 
-inline unsigned grid_for(int64_t n, int cap = 4 * max_stream_blocks)
-{
-    int64_t b = ceildiv(n > 0 ? n : 1, 256);
-    if (b > cap) b = cap;
-    return unsigned(b);
-}
+inline unsigned grid_for(int64_t n, int cap = 4 * max_stream_blocks) { return stream_grid(n, 256, cap); }
 
 // workspace: [row_ptrs (n_rows + 1) of I | pad to 16 | flag int32, pad | one T, pad |
 //             n_rows values: the copy of c that the one-pass forms of the operations reading c

@@ -336,9 +336,7 @@ int launch_row_gather(gkoc_stream_t s, int64_t n_gather, int64_t cols,
                       T* gathered, int64_t ld_gathered)
 {
     if (n_gather <= 0 || cols <= 0) return GKOC_OK;
-    int64_t blocks = ceildiv(n_gather * cols, 256);
-    if (blocks > 4 * max_stream_blocks) blocks = 4 * max_stream_blocks;
-    row_gather_kernel<T, I><<<dim3(unsigned(blocks)), dim3(256), 0, as_stream(s)>>>(
+    row_gather_kernel<T, I><<<dim3(stream_grid(n_gather * cols)), dim3(256), 0, as_stream(s)>>>(
         n_gather, cols, rows, orig, ld_orig, gathered, ld_gathered);
     GKOC_LAUNCH_OK();
     return GKOC_OK;

@@ -23,13 +23,6 @@
 namespace gkoc {
 namespace {
 
-inline unsigned grid_of(int64_t n)
-{
-    int64_t b = ceildiv(n > 0 ? n : 1, 256);
-    if (b > 4 * max_stream_blocks) b = 4 * max_stream_blocks;
-    return unsigned(b);
-}
-
 #define GKOC_GRID_STRIDE(i, n)                                                         \
     for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x, i##_stride = int64_t(gridDim.x) * 256; \
          i < (n); i += i##_stride)
@@ -216,7 +209,7 @@ int separate_count(gkoc_stream_t s, int64_t nnz, const G* rows, const G* cols, c
     hipStream_t st = as_stream(s);
     int64_t* pos = nullptr;
     GKOC_TRY(scratch_malloc(st, reinterpret_cast<void**>(&pos), size_t(2 * (nnz + 1)) * sizeof(int64_t)));
-    separate_mark_kernel<L, G><<<dim3(grid_of(nnz + 1)), dim3(256), 0, st>>>(
+    separate_mark_kernel<L, G><<<dim3(stream_grid(nnz + 1)), dim3(256), 0, st>>>(
         nnz, rows, cols, view_of<L, G>(rp), view_of<L, G>(cp), local_part, pos, pos + nnz + 1);
     GKOC_LAUNCH_OK();
     GKOC_TRY(exclusive_scan_inplace<int64_t>(st, pos, nnz + 1));
@@ -236,7 +229,7 @@ int separate_fill_w(hipStream_t st, int64_t nnz, const G* rows, const G* cols, c
                     const gkoc_partition* rp, const gkoc_partition* cp, const int64_t* pos, L* l_row, L* l_col,
                     void* l_val, L* n_row, G* n_col, void* n_val)
 {
-    separate_fill_kernel<L, G, W><<<dim3(grid_of(nnz)), dim3(256), 0, st>>>(
+    separate_fill_kernel<L, G, W><<<dim3(stream_grid(nnz)), dim3(256), 0, st>>>(
         nnz, rows, cols, static_cast<const W*>(vals), view_of<L, G>(rp), view_of<L, G>(cp), pos, pos + nnz + 1,
         l_row, l_col, static_cast<W*>(l_val), n_row, n_col, static_cast<W*>(n_val));
     GKOC_LAUNCH_OK();
@@ -293,7 +286,7 @@ int vector_build_local(gkoc_stream_t s, int64_t nnz, const G* rows, const G* col
     GKOC_REQUIRE(p && nnz >= 0, GKOC_E_INVALID, "bad argument");
     if (nnz == 0) return GKOC_OK;
     hipStream_t st = as_stream(s);
-    const dim3 g(grid_of(nnz));
+    const dim3 g(stream_grid(nnz));
     if (value_size == 4) {
         build_local_kernel<L, G, uint32_t><<<g, dim3(256), 0, st>>>(
             nnz, rows, cols, static_cast<const uint32_t*>(vals), view_of<L, G>(p), local_part,
@@ -415,7 +408,7 @@ int build_mapping_count(gkoc_stream_t s, int64_t n, const G* recv, const gkoc_pa
     // these two stay alive until the fill call
     GKOC_TRY(scratch_malloc(st, reinterpret_cast<void**>(&g2), size_t(n) * sizeof(G)));
     GKOC_TRY(scratch_malloc(st, reinterpret_cast<void**>(&p2), size_t(n) * sizeof(int32_t)));
-    const dim3 g(grid_of(n));
+    const dim3 g(stream_grid(n));
     iota_kernel2<int64_t><<<g, dim3(256), 0, st>>>(n, perm0);
     GKOC_LAUNCH_OK();
     GKOC_TRY((stable_sort_pairs<G, int64_t>(st, n, recv, g1, perm0, perm1)));
@@ -427,7 +420,7 @@ int build_mapping_count(gkoc_stream_t s, int64_t n, const G* recv, const gkoc_pa
     tmp.release();
     int64_t* pos = nullptr;
     GKOC_TRY(scratch_malloc(st, reinterpret_cast<void**>(&pos), size_t(2 * (n + 1)) * sizeof(int64_t)));
-    mapping_mark_kernel<G><<<dim3(grid_of(n + 1)), dim3(256), 0, st>>>(n, p2, g2, pos, pos + n + 1);
+    mapping_mark_kernel<G><<<dim3(stream_grid(n + 1)), dim3(256), 0, st>>>(n, p2, g2, pos, pos + n + 1);
     GKOC_LAUNCH_OK();
     GKOC_TRY(exclusive_scan_inplace<int64_t>(st, pos, n + 1));
     GKOC_TRY(exclusive_scan_inplace<int64_t>(st, pos + n + 1, n + 1));
@@ -453,11 +446,11 @@ int build_mapping_fill(gkoc_stream_t s, const gkoc_partition* part, void* state,
     int64_t* starts_next = nullptr;
     rc = scratch_malloc(st, reinterpret_cast<void**>(&starts_next), size_t(ms->n_part_unique + 1) * 8);
     if (rc == GKOC_OK) {
-        mapping_fill_kernel<L, G><<<dim3(grid_of(ms->n)), dim3(256), 0, st>>>(
+        mapping_fill_kernel<L, G><<<dim3(stream_grid(ms->n)), dim3(256), 0, st>>>(
             ms->n, ms->parts, static_cast<const G*>(ms->gids), ms->pos_u, ms->pos_p, view_of<L, G>(part),
             part_ids_out, remote_local, remote_global, starts_next);
         if (hipGetLastError() != hipSuccess) rc = GKOC_E_INVALID;
-        mapping_sizes_kernel<<<dim3(grid_of(ms->n_part_unique)), dim3(256), 0, st>>>(
+        mapping_sizes_kernel<<<dim3(stream_grid(ms->n_part_unique)), dim3(256), 0, st>>>(
             ms->n_part_unique, ms->n_unique, starts_next, remote_sizes);
         if (hipGetLastError() != hipSuccess) rc = GKOC_E_INVALID;
         (void)scratch_free(st, starts_next);
@@ -805,7 +798,7 @@ using namespace gkoc;
     {                                                                                                         \
         GKOC_REQUIRE(part && n >= 0 && index_space >= 0 && index_space <= 2, GKOC_E_INVALID, "bad argument"); \
         if (n == 0) return GKOC_OK;                                                                           \
-        map_to_local_kernel<L, G><<<dim3(grid_of(n)), dim3(256), 0, as_stream(s)>>>(                          \
+        map_to_local_kernel<L, G><<<dim3(stream_grid(n)), dim3(256), 0, as_stream(s)>>>(                      \
             n, global_ids, view_of<L, G>(part), n_targets, remote_target_ids, remote_global_flat,             \
             remote_offsets, rank, index_space, local_ids);                                                    \
         GKOC_LAUNCH_OK();                                                                                     \
@@ -818,7 +811,7 @@ using namespace gkoc;
     {                                                                                                         \
         GKOC_REQUIRE(n >= 0 && index_space >= 0 && index_space <= 2, GKOC_E_INVALID, "bad argument");         \
         if (n == 0) return GKOC_OK;                                                                           \
-        map_to_global_kernel<L, G><<<dim3(grid_of(n)), dim3(256), 0, as_stream(s)>>>(                         \
+        map_to_global_kernel<L, G><<<dim3(stream_grid(n)), dim3(256), 0, as_stream(s)>>>(                     \
             n, local_ids, range_bounds, starting_indices, L(local_size), local_ranges, n_local_ranges,        \
             remote_global_flat, remote_size, index_space, global_ids);                                        \
         GKOC_LAUNCH_OK();                                                                                     \
@@ -842,7 +835,7 @@ using namespace gkoc;
             GKOC_TRY(tmp.get(&ps, num_ranges));                                                               \
             GKOC_TRY(tmp.get(&sz, num_ranges + 1));                                                           \
             GKOC_TRY(tmp.get(&first, num_parts));                                                             \
-            const dim3 g(grid_of(num_ranges + 1));                                                            \
+            const dim3 g(stream_grid(num_ranges + 1));                                                        \
             iota_kernel2<int64_t><<<g, dim3(256), 0, st>>>(num_ranges, iota);                                 \
             GKOC_TRY((stable_sort_pairs<int32_t, int64_t>(st, num_ranges, range_parts, ps, iota, order)));    \
             range_sizes_kernel<L, G><<<g, dim3(256), 0, st>>>(num_ranges, order, range_offsets, sz);          \
@@ -856,7 +849,7 @@ using namespace gkoc;
         unsigned long long* cnt = nullptr;                                                                    \
         GKOC_TRY(scratch_malloc(st, reinterpret_cast<void**>(&cnt), 8));                                      \
         GKOC_HIP(hipMemsetAsync(cnt, 0, 8, st));                                                              \
-        count_zero_kernel<L><<<dim3(grid_of(num_parts)), dim3(256), 0, st>>>(num_parts, sizes, cnt);          \
+        count_zero_kernel<L><<<dim3(stream_grid(num_parts)), dim3(256), 0, st>>>(num_parts, sizes, cnt);      \
         unsigned long long h = 0;                                                                             \
         int rc = to_host(st, &h, cnt, 8);                                                                     \
         (void)scratch_free(st, cnt);                                                                          \
@@ -876,7 +869,7 @@ using namespace gkoc;
         GKOC_TRY(tmp.get(&key, nnz));                                                                         \
         GKOC_TRY(tmp.get(&key2, nnz));                                                                        \
         GKOC_TRY(tmp.get(&orig, nnz));                                                                        \
-        const dim3 g(grid_of(nnz));                                                                           \
+        const dim3 g(stream_grid(nnz));                                                                       \
         non_owning_mark_kernel<L, G><<<g, dim3(256), 0, st>>>(nnz, rows, view_of<L, G>(part), local_part,     \
                                                               key, orig, send_count);                         \
         GKOC_LAUNCH_OK();                                                                                     \
@@ -903,7 +896,7 @@ GKOC_DEF_DIST_LG(int64_t, i64, int64_t, i64)
             GKOC_HIP(hipMemsetAsync(range_bounds, 0, sizeof(G), st));                                         \
             return GKOC_OK;                                                                                   \
         }                                                                                                     \
-        from_contiguous_kernel<G><<<dim3(grid_of(num_ranges)), dim3(256), 0, st>>>(                           \
+        from_contiguous_kernel<G><<<dim3(stream_grid(num_ranges)), dim3(256), 0, st>>>(                       \
             num_ranges, ranges, part_id_mapping, range_bounds, part_ids);                                     \
         GKOC_LAUNCH_OK();                                                                                     \
         return GKOC_OK;                                                                                       \
@@ -919,10 +912,10 @@ GKOC_DEF_DIST_LG(int64_t, i64, int64_t, i64)
         }                                                                                                     \
         int64_t* pos = nullptr;                                                                               \
         GKOC_TRY(scratch_malloc(st, reinterpret_cast<void**>(&pos), size_t(n + 1) * 8));                      \
-        mapping_heads_kernel<<<dim3(grid_of(n + 1)), dim3(256), 0, st>>>(n, mapping, pos);                    \
+        mapping_heads_kernel<<<dim3(stream_grid(n + 1)), dim3(256), 0, st>>>(n, mapping, pos);                \
         GKOC_LAUNCH_OK();                                                                                     \
         GKOC_TRY(exclusive_scan_inplace<int64_t>(st, pos, n + 1));                                            \
-        from_mapping_fill_kernel<G><<<dim3(grid_of(n + 1)), dim3(256), 0, st>>>(n, mapping, pos,              \
+        from_mapping_fill_kernel<G><<<dim3(stream_grid(n + 1)), dim3(256), 0, st>>>(n, mapping, pos,          \
                                                                                range_bounds, part_ids);      \
         GKOC_LAUNCH_OK();                                                                                     \
         return scratch_free(st, pos);                                                                         \
@@ -931,7 +924,7 @@ GKOC_DEF_DIST_LG(int64_t, i64, int64_t, i64)
                                                                      G global_size, G* ranges)                \
     {                                                                                                         \
         GKOC_REQUIRE(num_parts > 0, GKOC_E_INVALID, "num_parts must be positive");                            \
-        ranges_from_size_kernel<G><<<dim3(grid_of(num_parts + 1)), dim3(256), 0, as_stream(s)>>>(             \
+        ranges_from_size_kernel<G><<<dim3(stream_grid(num_parts + 1)), dim3(256), 0, as_stream(s)>>>(         \
             num_parts, global_size, ranges);                                                                  \
         GKOC_LAUNCH_OK();                                                                                     \
         return GKOC_OK;                                                                                       \
@@ -951,7 +944,7 @@ GKOC_DEF_DIST_LG(int64_t, i64, int64_t, i64)
         GKOC_TRY(tmp.get(&iota, num_parts));                                                                  \
         GKOC_TRY(tmp.get(&perm, num_parts));                                                                  \
         GKOC_TRY(tmp.get(&pid, num_parts));                                                                   \
-        const dim3 g(grid_of(num_parts));                                                                     \
+        const dim3 g(stream_grid(num_parts));                                                                 \
         range_starts_kernel<G><<<g, dim3(256), 0, st>>>(num_parts, range_start_ends, starts);                 \
         iota_kernel2<int64_t><<<g, dim3(256), 0, st>>>(num_parts, iota);                                      \
         GKOC_TRY((stable_sort_pairs<G, int64_t>(st, num_parts, starts, starts2, iota, perm)));                \
@@ -975,7 +968,7 @@ GKOC_DEF_DIST_LG(int64_t, i64, int64_t, i64)
         int* flag = nullptr;                                                                                  \
         GKOC_TRY(scratch_malloc(st, reinterpret_cast<void**>(&flag), 4));                                     \
         GKOC_HIP(hipMemsetAsync(flag, 0, 4, st));                                                             \
-        not_consecutive_kernel<G><<<dim3(grid_of(num_parts)), dim3(256), 0, st>>>(num_parts,                  \
+        not_consecutive_kernel<G><<<dim3(stream_grid(num_parts)), dim3(256), 0, st>>>(num_parts,              \
                                                                                  range_start_ends, flag);    \
         int h = 0;                                                                                            \
         int rc = to_host(st, &h, flag, 4);                                                                    \
@@ -987,7 +980,7 @@ GKOC_DEF_DIST_LG(int64_t, i64, int64_t, i64)
                                                                const G* range_start_ends, G* range_offsets)   \
     {                                                                                                         \
         if (n_offsets <= 0) return GKOC_OK;                                                                   \
-        compress_ranges_kernel<G><<<dim3(grid_of(n_offsets)), dim3(256), 0, as_stream(s)>>>(                  \
+        compress_ranges_kernel<G><<<dim3(stream_grid(n_offsets)), dim3(256), 0, as_stream(s)>>>(              \
             n_offsets, range_start_ends, range_offsets);                                                      \
         GKOC_LAUNCH_OK();                                                                                     \
         return GKOC_OK;                                                                                       \
@@ -998,7 +991,7 @@ GKOC_DEF_DIST_LG(int64_t, i64, int64_t, i64)
     {                                                                                                         \
         if (nnz <= 0) return GKOC_OK;                                                                         \
         hipStream_t st = as_stream(s);                                                                        \
-        const dim3 g(grid_of(nnz));                                                                           \
+        const dim3 g(stream_grid(nnz));                                                                       \
         if (value_size == 4) {                                                                                \
             fill_send_kernel<G, uint32_t><<<g, dim3(256), 0, st>>>(                                           \
                 nnz, rows, cols, static_cast<const uint32_t*>(vals), send_positions, original_positions,      \
@@ -1031,7 +1024,7 @@ extern "C" int gkoc_partition_count_ranges(gkoc_stream_t s, int64_t n, const int
     unsigned long long* cnt = nullptr;
     GKOC_TRY(scratch_malloc(st, reinterpret_cast<void**>(&cnt), 8));
     GKOC_HIP(hipMemsetAsync(cnt, 0, 8, st));
-    count_ranges_kernel<<<dim3(grid_of(n)), dim3(256), 0, st>>>(n, mapping, cnt);
+    count_ranges_kernel<<<dim3(stream_grid(n)), dim3(256), 0, st>>>(n, mapping, cnt);
     unsigned long long h = 0;
     int rc = to_host(st, &h, cnt, 8);
     (void)scratch_free(st, cnt);
@@ -1052,9 +1045,9 @@ extern "C" int gkoc_partition_build_ranges_by_part(gkoc_stream_t s, const int32_
     int32_t* ps = nullptr;
     GKOC_TRY(tmp.get(&iota, num_ranges));
     GKOC_TRY(tmp.get(&ps, num_ranges));
-    iota_kernel2<uint64_t><<<dim3(grid_of(num_ranges)), dim3(256), 0, st>>>(num_ranges, iota);
+    iota_kernel2<uint64_t><<<dim3(stream_grid(num_ranges)), dim3(256), 0, st>>>(num_ranges, iota);
     GKOC_TRY((stable_sort_pairs<int32_t, uint64_t>(st, num_ranges, range_parts, ps, iota, range_ids)));
-    histogram_kernel<<<dim3(grid_of(num_ranges)), dim3(256), 0, st>>>(
+    histogram_kernel<<<dim3(stream_grid(num_ranges)), dim3(256), 0, st>>>(
         num_ranges, range_parts, reinterpret_cast<unsigned long long*>(sizes));
     GKOC_LAUNCH_OK();
     tmp.release();
@@ -1071,7 +1064,7 @@ extern "C" int gkoc_partition_has_ordered_parts(gkoc_stream_t s, int64_t num_ran
     int* flag = nullptr;
     GKOC_TRY(scratch_malloc(st, reinterpret_cast<void**>(&flag), 4));
     GKOC_HIP(hipMemsetAsync(flag, 0, 4, st));
-    unordered_kernel<<<dim3(grid_of(num_ranges)), dim3(256), 0, st>>>(num_ranges, part_ids, flag);
+    unordered_kernel<<<dim3(stream_grid(num_ranges)), dim3(256), 0, st>>>(num_ranges, part_ids, flag);
     int h = 0;
     int rc = to_host(st, &h, flag, 4);
     (void)scratch_free(st, flag);

@@ -158,16 +158,11 @@ int launch_elementwise(gkoc_stream_t s, int64_t rows, int64_t cols,
     const int64_t n = rows * cols;
     if (flat && aligned) {
         const int64_t n_vec = n / vec16<T>::width;
-        int64_t blocks = ceildiv(n_vec > 0 ? n_vec : 1, 256);
-        if (blocks > max_stream_blocks) blocks = max_stream_blocks;
         ew_flat_vec_kernel<T, OP, NIN, NOUT>
-            <<<dim3(unsigned(blocks)), dim3(256), 0, as_stream(s)>>>(n, a, op);
+            <<<dim3(stream_grid(n_vec, 256, max_stream_blocks)), dim3(256), 0, as_stream(s)>>>(n, a, op);
     } else {
-        int64_t blocks = ceildiv(n, 256);
-        if (blocks > 4 * max_stream_blocks) blocks = 4 * max_stream_blocks;
         ew_general_kernel<T, OP, NIN, NOUT>
-            <<<dim3(unsigned(blocks)), dim3(256), 0, as_stream(s)>>>(rows, cols,
-                                                                    a, op);
+            <<<dim3(stream_grid(n)), dim3(256), 0, as_stream(s)>>>(rows, cols, a, op);
     }
     GKOC_LAUNCH_OK();
     return GKOC_OK;

@@ -33,7 +33,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
-#include "factorization_common.hpp"
+#include "sparse_rows.hpp"
 #include "trs_struct.hpp"
 
 namespace gkoc {
@@ -140,9 +140,8 @@ int factorize_launch(hipStream_t st, gkoc_trs_struct_t t, const I* rp, const I* 
     for (const auto& seg : t->schedule) {
         if (seg.rows == 0) continue;
         if (seg.wide) {
-            int64_t blocks = ceildiv(seg.rows, fact_wide_block / W);
-            if (blocks > 4 * max_stream_blocks) blocks = 4 * max_stream_blocks;
-            factorize_wide_kernel<IC, W, T, I><<<dim3(unsigned(blocks)), dim3(fact_wide_block), 0, st>>>(
+            factorize_wide_kernel<IC, W, T, I>
+                <<<dim3(stream_grid(seg.rows, fact_wide_block / W)), dim3(fact_wide_block), 0, st>>>(
                 seg.rows, t->level_rows + seg.offset, rp, ci, diag, vals);
         } else {
             factorize_narrow_kernel<IC, W, T, I><<<dim3(1), dim3(fact_narrow_block), 0, st>>>(
@@ -165,37 +164,23 @@ int factorize(gkoc_stream_t s, gkoc_trs_struct_t t, int64_t n, const I* rp, cons
     GKOC_REQUIRE(rp && ci && vals, GKOC_E_INVALID, "null pointer");
     hipStream_t st = as_stream(s);
     // scratch: 4 status words, then the diagonal positions
-    void* raw = nullptr;
-    GKOC_TRY(scratch_malloc(st, &raw, 16 + sizeof(I) * size_t(n)));
-    scratch_guard guard{st, raw};
-    int* status = static_cast<int*>(raw);
-    I* diag = reinterpret_cast<I*>(static_cast<char*>(raw) + 16);
-    GKOC_HIP(hipMemsetAsync(status, 0, 16, st));
-    int64_t blocks = ceildiv(n, 256);
-    if (blocks > 4 * max_stream_blocks) blocks = 4 * max_stream_blocks;
-    locate_diagonals_kernel<I><<<dim3(unsigned(blocks)), dim3(256), 0, st>>>(n, t->nnz, rp, ci, diag, status);
+    status_words<4> status(st);
+    GKOC_TRY(status.init(sizeof(I) * size_t(n)));
+    I* diag = status.template behind<I>();
+    locate_diagonals_kernel<I><<<dim3(stream_grid(n)), dim3(256), 0, st>>>(n, t->nnz, rp, ci, diag, status.dev);
     GKOC_LAUNCH_OK();
-    int host[4] = {0, 0, 0, 0};
-    GKOC_HIP(hipMemcpyAsync(host, status, 16, hipMemcpyDeviceToHost, st));
-    GKOC_HIP(hipStreamSynchronize(st));
-    GKOC_REQUIRE(host[0] == 0, GKOC_E_INVALID,
+    GKOC_TRY(status.read());
+    GKOC_REQUIRE(status[0] == 0, GKOC_E_INVALID,
                  "row pointers or column indices do not fit the matrix the structure was generated for");
-    GKOC_REQUIRE(host[1] == 0, GKOC_E_INVALID, "a row without a stored diagonal");
-    GKOC_REQUIRE(!IC || host[2] == 0, GKOC_E_INVALID, "a row whose last entry is not its diagonal");
-    if (host[3] <= fact_row_limits[0]) return factorize_launch<IC, 16, T, I>(st, t, rp, ci, diag, vals);
-    if (host[3] <= fact_row_limits[1]) return factorize_launch<IC, 32, T, I>(st, t, rp, ci, diag, vals);
-    return factorize_launch<IC, 64, T, I>(st, t, rp, ci, diag, vals);
+    GKOC_REQUIRE(status[1] == 0, GKOC_E_INVALID, "a row without a stored diagonal");
+    GKOC_REQUIRE(!IC || status[2] == 0, GKOC_E_INVALID, "a row whose last entry is not its diagonal");
+    return with_lanes(status[3], fact_row_limits, [&](auto w) {
+        return factorize_launch<IC, decltype(w)::value, T, I>(st, t, rp, ci, diag, vals);
+    });
 }
 
 
 // ------------------------------------------------------------------ the split (one thread per row)
-inline unsigned split_grid(int64_t n)
-{
-    int64_t b = ceildiv(n, 256);
-    if (b > 4 * max_stream_blocks) b = 4 * max_stream_blocks;
-    return unsigned(b < 1 ? 1 : b);
-}
-
 // The VALUES of the split; the index arrays of L and U are those of the Sor set-up (trs.hip: the same
 // row pointers, strictly-lower columns then the diagonal, the diagonal then the strictly-upper columns), so
 // no entry of this file writes an index array.
@@ -237,7 +222,7 @@ int split(gkoc_stream_t s, int64_t n, const I* rp, const I* ci, const T* v, cons
     if (n == 0) return GKOC_OK;
     GKOC_REQUIRE(rp && l_rp && l_v, GKOC_E_INVALID, "null pointer");
     GKOC_REQUIRE(!WITH_U || (u_rp && u_v), GKOC_E_INVALID, "null pointer");
-    split_kernel<WITH_U, T, I><<<dim3(split_grid(n)), dim3(256), 0, as_stream(s)>>>(n, rp, ci, v, l_rp, l_v, u_rp,
+    split_kernel<WITH_U, T, I><<<dim3(stream_grid(n)), dim3(256), 0, as_stream(s)>>>(n, rp, ci, v, l_rp, l_v, u_rp,
                                                                                    u_v, diag_sqrt);
     GKOC_LAUNCH_OK();
     return GKOC_OK;
@@ -250,11 +235,7 @@ using namespace gkoc;
 
 extern "C" int gkoc_factorization_row_limits(int* limits_host, int* count_host)
 {
-    GKOC_REQUIRE(limits_host && count_host, GKOC_E_INVALID, "null pointer");
-    constexpr int count = int(sizeof(fact_row_limits) / sizeof(fact_row_limits[0]));
-    for (int p = 0; p < count; ++p) limits_host[p] = fact_row_limits[p];
-    *count_host = count;
-    return GKOC_OK;
+    return export_row_limits(fact_row_limits, limits_host, count_host);
 }
 
 #define GKOC_DEF_FACTORIZATION(T, TN, I, IN)                                                                   \

@@ -349,11 +349,7 @@ __global__ __launch_bounds__(256) void fbcsr_is_sorted_kernel(
     }
 }
 
-inline unsigned fb_grid(int64_t n)
-{
-    const int64_t g = ceildiv(n, 256);
-    return unsigned(g < max_stream_blocks ? (g > 0 ? g : 1) : max_stream_blocks);
-}
+inline unsigned fb_grid(int64_t n) { return capped_grid(n, 256, max_stream_blocks); }
 
 // the argument checks every entry makes before it touches HIP
 #define FB_CHECK_BS(bs)                                                                        \

@@ -556,10 +556,8 @@ __global__ __launch_bounds__(256) void fill_in_md_kernel(
     }
 }
 
-inline unsigned blocks_for(int64_t n)
-{
-    return unsigned(ceildiv(n > 0 ? n : 1, 256));
-}
+// these grids have no cap
+inline unsigned blocks_for(int64_t n) { return capped_grid(n, 256, no_grid_cap); }
 
 template <typename T, typename I, bool ADV>
 int launch_ell(gkoc_stream_t s, int64_t n_rows, int64_t n_cols, int64_t k,

@@ -324,13 +324,6 @@ __global__ __launch_bounds__(256) void gmres_solve_krylov_kernel(
     }
 }
 
-inline unsigned stream_blocks(int64_t n)
-{
-    int64_t b = ceildiv(n > 0 ? n : 1, 256);
-    if (b > 4 * max_stream_blocks) b = 4 * max_stream_blocks;
-    return unsigned(b);
-}
-
 }  // namespace
 }  // namespace gkoc
 
@@ -355,7 +348,7 @@ extern "C" size_t gkoc_gmres_multi_dot_workspace_bytes(int64_t rows, int64_t nrh
         if (nrhs <= 0) return GKOC_OK;                                         \
         const int64_t work = rows * nrhs > krylov_dim * nrhs ? rows * nrhs     \
                                                              : krylov_dim * nrhs; \
-        gmres_init_kernel<T><<<dim3(stream_blocks(work > nrhs ? work : nrhs)), \
+        gmres_init_kernel<T><<<dim3(stream_grid(work > nrhs ? work : nrhs)),      \
                                dim3(256), 0, as_stream(s)>>>(                  \
             rows, nrhs, b, ldb, residual, ldr, givens_sin, ld_sin, givens_cos, \
             ld_cos, krylov_dim, stop_status);                                  \
@@ -370,7 +363,7 @@ extern "C" size_t gkoc_gmres_multi_dot_workspace_bytes(int64_t rows, int64_t nrh
     {                                                                          \
         if (nrhs <= 0) return GKOC_OK;                                         \
         gmres_restart_kernel<T>                                                \
-            <<<dim3(stream_blocks(rows * nrhs > nrhs ? rows * nrhs : nrhs)),   \
+            <<<dim3(stream_grid(rows * nrhs > nrhs ? rows * nrhs : nrhs)),     \
                dim3(256), 0, as_stream(s)>>>(rows, nrhs, residual, ldr,        \
                                              residual_norm,                    \
                                              residual_norm_collection,         \
@@ -387,7 +380,7 @@ extern "C" size_t gkoc_gmres_multi_dot_workspace_bytes(int64_t rows, int64_t nrh
         if (nrhs <= 0) return GKOC_OK;                                         \
         if (rows > 0) {                                                        \
             gmres_multi_axpy_kernel<T>                                         \
-                <<<dim3(stream_blocks(rows * nrhs)), dim3(256), 0,             \
+                <<<dim3(stream_grid(rows * nrhs)), dim3(256), 0,               \
                    as_stream(s)>>>(rows, nrhs, krylov_bases, ldk, y, ldy,      \
                                    before_preconditioner, ldo,                 \
                                    final_iter_nums, stop_status);              \
@@ -436,7 +429,7 @@ extern "C" size_t gkoc_gmres_multi_dot_workspace_bytes(int64_t rows, int64_t nrh
         GKOC_REQUIRE(krylov_bases && h && next_krylov, GKOC_E_INVALID,         \
                      "null pointer");                                          \
         gmres_multi_sub_scaled_kernel<T>                                       \
-            <<<dim3(stream_blocks(rows * nrhs)), dim3(256), 0, as_stream(s)>>>( \
+            <<<dim3(stream_grid(rows * nrhs)), dim3(256), 0, as_stream(s)>>>(  \
                 rows, nrhs, int(num), krylov_bases, ldk, h, ldh, next_krylov,  \
                 ldn);                                                          \
         GKOC_LAUNCH_OK();                                                      \

@@ -25,11 +25,7 @@ namespace {
 constexpr int idr_block = 256;
 constexpr int idr_max_partials = 1024;
 
-inline unsigned idr_blocks(int64_t n)
-{
-    int64_t nb = ceildiv(n, idr_block);
-    return unsigned(nb > max_stream_blocks ? max_stream_blocks : (nb < 1 ? 1 : nb));
-}
+inline unsigned idr_blocks(int64_t n) { return capped_grid(n, idr_block, max_stream_blocks); }
 
 template <typename T>
 __global__ __launch_bounds__(idr_block) void idr_init_m_kernel(int64_t s, int64_t nrhs, T* m, int64_t ldm,

@@ -35,42 +35,13 @@
 #include <climits>
 
 #include "common.hpp"
+#include "sparse_rows.hpp"
 
 namespace gkoc {
 namespace {
 
 constexpr int isai_block = 256;
 constexpr int isai_row_limits[] = {16, 32, 64};
-
-// position of column c in ci[lo, hi) (ascending), -1 if it is not stored
-template <typename I>
-__device__ __forceinline__ int64_t find_column(const I* __restrict__ ci, int64_t lo, int64_t hi, int64_t c)
-{
-    const int64_t end = hi;
-    while (lo < hi) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (int64_t(ci[mid]) < c) {
-            lo = mid + 1;
-        } else {
-            hi = mid;
-        }
-    }
-    return lo < end && int64_t(ci[lo]) == c ? lo : int64_t(-1);
-}
-
-__device__ __forceinline__ bool is_finite(double v) { return ::isfinite(v); }
-__device__ __forceinline__ bool is_finite(float v) { return ::isfinite(v); }
-
-// `flag` of any lane of the group of W lanes this lane belongs to
-template <int W>
-__device__ __forceinline__ int group_any(int flag)
-{
-#pragma unroll
-    for (int off = W / 2; off > 0; off >>= 1) {
-        flag |= __shfl_xor(flag, off, W);
-    }
-    return flag;
-}
 
 // The off-diagonal part of row k of A and the position of its diagonal.
 template <bool LOWER, typename I>
@@ -192,30 +163,14 @@ __global__ __launch_bounds__(256) void check_triangle_kernel(int64_t n, int is_l
         const int64_t len = end - begin;
         longest = len > longest ? int(len > INT_MAX ? INT_MAX : len) : longest;
     }
-    longest = wave_max(longest);
-    if ((threadIdx.x & (wave_size - 1)) == 0 && longest > 0) atomicMax(&status[4], longest);
-}
-
-struct scratch_guard {
-    hipStream_t st;
-    void* ptr;
-    ~scratch_guard()
-    {
-        if (ptr) (void)scratch_free(st, ptr);
-    }
-};
-
-inline unsigned capped_grid(int64_t blocks)
-{
-    if (blocks > 4 * max_stream_blocks) blocks = 4 * max_stream_blocks;
-    return unsigned(blocks < 1 ? 1 : blocks);
+    note_longest(longest, &status[4]);
 }
 
 template <bool LOWER, int W, typename T, typename I>
 int tri_inverse_launch(hipStream_t st, int64_t n, const I* a_rp, const I* a_ci, const T* a_v, const I* w_rp,
                        const I* w_ci, T* w_v)
 {
-    tri_inverse_kernel<LOWER, W, T, I><<<dim3(capped_grid(ceildiv(n, isai_block / W))), dim3(isai_block), 0, st>>>(
+    tri_inverse_kernel<LOWER, W, T, I><<<dim3(stream_grid(n, isai_block / W)), dim3(isai_block), 0, st>>>(
         n, a_rp, a_ci, a_v, w_rp, w_ci, w_v);
     GKOC_LAUNCH_OK();
     return GKOC_OK;
@@ -225,9 +180,9 @@ template <bool LOWER, typename T, typename I>
 int tri_inverse_width(hipStream_t st, int longest, int64_t n, const I* a_rp, const I* a_ci, const T* a_v,
                       const I* w_rp, const I* w_ci, T* w_v)
 {
-    if (longest <= isai_row_limits[0]) return tri_inverse_launch<LOWER, 16, T, I>(st, n, a_rp, a_ci, a_v, w_rp, w_ci, w_v);
-    if (longest <= isai_row_limits[1]) return tri_inverse_launch<LOWER, 32, T, I>(st, n, a_rp, a_ci, a_v, w_rp, w_ci, w_v);
-    return tri_inverse_launch<LOWER, 64, T, I>(st, n, a_rp, a_ci, a_v, w_rp, w_ci, w_v);
+    return with_lanes(longest, isai_row_limits, [&](auto w) {
+        return tri_inverse_launch<LOWER, decltype(w)::value, T, I>(st, n, a_rp, a_ci, a_v, w_rp, w_ci, w_v);
+    });
 }
 
 template <typename T, typename I>
@@ -240,21 +195,17 @@ int generate_tri_inverse(gkoc_stream_t s, int64_t n, int is_lower, const I* a_rp
     hipStream_t st = as_stream(s);
     // scratch: 5 status words for A, 5 for the pattern
     constexpr int words = 5;
-    void* raw = nullptr;
-    GKOC_TRY(scratch_malloc(st, &raw, 2 * words * sizeof(int)));
-    scratch_guard guard{st, raw};
-    int* status = static_cast<int*>(raw);
-    GKOC_HIP(hipMemsetAsync(status, 0, 2 * words * sizeof(int), st));
-    const unsigned grid = capped_grid(ceildiv(n, 256));
-    check_triangle_kernel<I><<<dim3(grid), dim3(256), 0, st>>>(n, is_lower, a_rp, a_ci, status);
+    status_words<2 * words> status(st);
+    GKOC_TRY(status.init());
+    const unsigned grid = stream_grid(n);
+    check_triangle_kernel<I><<<dim3(grid), dim3(256), 0, st>>>(n, is_lower, a_rp, a_ci, status.dev);
     GKOC_LAUNCH_OK();
     if (w_rp != a_rp || w_ci != a_ci) {
-        check_triangle_kernel<I><<<dim3(grid), dim3(256), 0, st>>>(n, is_lower, w_rp, w_ci, status + words);
+        check_triangle_kernel<I><<<dim3(grid), dim3(256), 0, st>>>(n, is_lower, w_rp, w_ci, status.dev + words);
         GKOC_LAUNCH_OK();
     }
-    int host[2 * words] = {};
-    GKOC_HIP(hipMemcpyAsync(host, status, sizeof(host), hipMemcpyDeviceToHost, st));
-    GKOC_HIP(hipStreamSynchronize(st));
+    GKOC_TRY(status.read());
+    int* host = status.host;
     if (w_rp == a_rp && w_ci == a_ci) host[words + 4] = host[4];
     for (int m = 0; m < 2; ++m) {
         const int* h = host + m * words;
@@ -309,8 +260,6 @@ constexpr int general_wave_cap = 64;
 constexpr int general_cap = 128;
 constexpr int general_block = 2 * general_cap;
 
-__device__ __forceinline__ double root_of(double v) { return ::sqrt(v); }
-__device__ __forceinline__ float root_of(float v) { return ::sqrtf(v); }
 // what the pivot search compares: |v|, a NaN as the largest
 __device__ __forceinline__ double pivot_key(double v) { return v != v ? HUGE_VAL : __builtin_fabs(v); }
 __device__ __forceinline__ float pivot_key(float v) { return v != v ? HUGE_VALF : __builtin_fabsf(v); }
@@ -346,17 +295,6 @@ __device__ __forceinline__ void group_pivot(T& key, int& q)
     }
 }
 
-template <int W>
-__device__ __forceinline__ int group_max_int(int v)
-{
-#pragma unroll
-    for (int off = W / 2; off > 0; off >>= 1) {
-        const int o = __shfl_xor(v, off, W);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
 template <int W, typename T, typename I>
 __global__ __launch_bounds__(isai_block) void general_inverse_wave_kernel(
     int64_t n, int spd, const I* __restrict__ a_rp, const I* __restrict__ a_ci, const T* __restrict__ a_v,
@@ -374,7 +312,7 @@ __global__ __launch_bounds__(isai_block) void general_inverse_wave_kernel(
         if (len > W) continue;          // the workgroup kernel's row
         const bool valid = lane < len;
         const long long col_mine = valid ? (long long)(w_ci[begin + lane]) : -1LL;
-        const int p = group_max_int<W>(col_mine == row ? lane : -1);
+        const int p = group_max<W>(col_mine == row ? lane : -1);
         for (int k = 0; k < len; ++k) {
             const int64_t c_k = __shfl(col_mine, k, W);
             if (valid) mine[k] = entry_of_a<T, I>(c_k, col_mine, a_rp, a_ci, a_v);
@@ -399,7 +337,7 @@ __global__ __launch_bounds__(isai_block) void general_inverse_wave_kernel(
         }
         T w = valid ? rhs / mine[pivot_col] : T(0);
         if (spd) {
-            const int last = group_max_int<W>(pivot_col == len - 1 ? lane : -1);
+            const int last = group_max<W>(pivot_col == len - 1 ? lane : -1);
             w = w / root_of(__shfl(w, last, W));
         }
         if (group_any<W>(valid && !is_finite(w))) w = pivot_col == p ? T(1) : T(0);
@@ -500,15 +438,14 @@ __global__ __launch_bounds__(256) void check_general_kernel(int64_t n, const I* 
         const int64_t len = end - begin;
         longest = len > longest ? int(len > INT_MAX ? INT_MAX : len) : longest;
     }
-    longest = wave_max(longest);
-    if ((threadIdx.x & (wave_size - 1)) == 0 && longest > 0) atomicMax(&status[5], longest);
+    note_longest(longest, &status[5]);
 }
 
 template <int W, typename T, typename I>
 int general_inverse_wave_launch(hipStream_t st, int64_t n, int spd, const I* a_rp, const I* a_ci, const T* a_v,
                                 const I* w_rp, const I* w_ci, T* w_v)
 {
-    general_inverse_wave_kernel<W, T, I><<<dim3(capped_grid(ceildiv(n, isai_block / W))), dim3(isai_block), 0, st>>>(
+    general_inverse_wave_kernel<W, T, I><<<dim3(stream_grid(n, isai_block / W)), dim3(isai_block), 0, st>>>(
         n, spd, a_rp, a_ci, a_v, w_rp, w_ci, w_v);
     GKOC_LAUNCH_OK();
     return GKOC_OK;
@@ -523,24 +460,19 @@ int generate_general_inverse(gkoc_stream_t s, int64_t n, int spd, const I* a_rp,
     GKOC_REQUIRE(a_rp && a_ci && a_v && w_rp && w_ci && w_v, GKOC_E_INVALID, "null pointer");
     hipStream_t st = as_stream(s);
     constexpr int words = general_status_words;
-    void* raw = nullptr;
-    GKOC_TRY(scratch_malloc(st, &raw, 2 * words * sizeof(int)));
-    scratch_guard guard{st, raw};
-    int* status = static_cast<int*>(raw);
-    GKOC_HIP(hipMemsetAsync(status, 0, 2 * words * sizeof(int), st));
-    const unsigned grid = capped_grid(ceildiv(n, 256));
+    status_words<2 * words> status(st);
+    GKOC_TRY(status.init());
+    const unsigned grid = stream_grid(n);
     const bool shared = w_rp == a_rp && w_ci == a_ci;
     if (!shared) {
-        check_general_kernel<I><<<dim3(grid), dim3(256), 0, st>>>(n, a_rp, a_ci, status);
+        check_general_kernel<I><<<dim3(grid), dim3(256), 0, st>>>(n, a_rp, a_ci, status.dev);
         GKOC_LAUNCH_OK();
     }
-    check_general_kernel<I><<<dim3(grid), dim3(256), 0, st>>>(n, w_rp, w_ci, status + words);
+    check_general_kernel<I><<<dim3(grid), dim3(256), 0, st>>>(n, w_rp, w_ci, status.dev + words);
     GKOC_LAUNCH_OK();
-    int host[2 * words] = {};
-    GKOC_HIP(hipMemcpyAsync(host, status, sizeof(host), hipMemcpyDeviceToHost, st));
-    GKOC_HIP(hipStreamSynchronize(st));
+    GKOC_TRY(status.read());
     for (int m = shared ? 1 : 0; m < 2; ++m) {
-        const int* h = host + m * words;
+        const int* h = status.host + m * words;
         GKOC_REQUIRE(h[0] == 0, GKOC_E_INVALID,
                      m ? "the pattern's row pointers do not ascend from 0" : "A's row pointers do not ascend from 0");
         GKOC_REQUIRE(h[1] == 0, GKOC_E_INVALID,
@@ -548,7 +480,7 @@ int generate_general_inverse(gkoc_stream_t s, int64_t n, int spd, const I* a_rp,
         GKOC_REQUIRE(h[2] == 0, GKOC_E_INVALID,
                      m ? "a pattern row is not sorted by column" : "a row of A is not sorted by column");
     }
-    const int* h = host + words;
+    const int* h = status.host + words;
     GKOC_REQUIRE(h[3] == 0, GKOC_E_INVALID, "a pattern row without its diagonal");
     GKOC_REQUIRE(!spd || h[4] == 0, GKOC_E_INVALID, "spd: a pattern entry above the diagonal");
     const int longest = h[5];
@@ -557,16 +489,12 @@ int generate_general_inverse(gkoc_stream_t s, int64_t n, int spd, const I* a_rp,
                        __LINE__, longest, general_cap);
         return GKOC_E_NOT_SUPPORTED;
     }
-    if (longest <= general_row_limits[0]) {
-        return general_inverse_wave_launch<16, T, I>(st, n, spd, a_rp, a_ci, a_v, w_rp, w_ci, w_v);
-    }
-    if (longest <= general_row_limits[1]) {
-        return general_inverse_wave_launch<32, T, I>(st, n, spd, a_rp, a_ci, a_v, w_rp, w_ci, w_v);
-    }
+    GKOC_TRY(with_lanes(longest, general_row_limits, [&](auto w) {
+        return general_inverse_wave_launch<decltype(w)::value, T, I>(st, n, spd, a_rp, a_ci, a_v, w_rp, w_ci, w_v);
+    }));
     // a second launch for the rows above 64 entries; each kernel skips the other's rows
-    GKOC_TRY((general_inverse_wave_launch<64, T, I>(st, n, spd, a_rp, a_ci, a_v, w_rp, w_ci, w_v)));
     if (longest > general_wave_cap) {
-        general_inverse_block_kernel<T, I><<<dim3(capped_grid(n)), dim3(general_block), 0, st>>>(
+        general_inverse_block_kernel<T, I><<<dim3(stream_grid(n, 1)), dim3(general_block), 0, st>>>(
             n, spd, a_rp, a_ci, a_v, w_rp, w_ci, w_v);
         GKOC_LAUNCH_OK();
     }
@@ -580,11 +508,7 @@ using namespace gkoc;
 
 extern "C" int gkoc_isai_row_limits(int* limits_host, int* count_host)
 {
-    GKOC_REQUIRE(limits_host && count_host, GKOC_E_INVALID, "null pointer");
-    constexpr int count = int(sizeof(isai_row_limits) / sizeof(isai_row_limits[0]));
-    for (int p = 0; p < count; ++p) limits_host[p] = isai_row_limits[p];
-    *count_host = count;
-    return GKOC_OK;
+    return export_row_limits(isai_row_limits, limits_host, count_host);
 }
 
 #define GKOC_DEF_ISAI(T, TN, I, IN)                                                                            \
@@ -601,13 +525,10 @@ GKOC_DEF_ISAI(float, f32, int64_t, i64)
 
 extern "C" int gkoc_isai_general_row_limits(int* limits_host, int* count_host)
 {
-    GKOC_REQUIRE(limits_host && count_host, GKOC_E_INVALID, "null pointer");
     constexpr int count = int(sizeof(general_row_limits) / sizeof(general_row_limits[0]));
     static_assert(general_row_limits[count - 1] == general_cap && general_row_limits[count - 2] == general_wave_cap,
                   "the last limit is the cap, the one before it the last length of the wave path");
-    for (int p = 0; p < count; ++p) limits_host[p] = general_row_limits[p];
-    *count_host = count;
-    return GKOC_OK;
+    return export_row_limits(general_row_limits, limits_host, count_host);
 }
 
 #define GKOC_DEF_ISAI_GENERAL(T, TN, I, IN)                                                                    \

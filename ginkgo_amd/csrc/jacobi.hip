@@ -2136,9 +2136,8 @@ int launch_transpose_adaptive_any(gkoc_stream_t s, int64_t num_blocks, gkoc_jaco
     if (num_blocks <= 0) return GKOC_OK;
     GKOC_REQUIRE(block_ptrs && blocks && out, GKOC_E_INVALID, "null pointer");
     GKOC_REQUIRE(scheme.block_offset >= 1, GKOC_E_INVALID, "bad storage scheme");
-    int64_t nb = ceildiv(num_blocks * scheme.block_offset, 256);
-    if (nb > 4 * max_stream_blocks) nb = 4 * max_stream_blocks;      // (a grid-stride loop)
-    jacobi_transpose_adaptive_any_kernel<T, I><<<dim3(unsigned(nb)), dim3(256), 0, as_stream(s)>>>(
+    const unsigned nb = stream_grid(num_blocks * scheme.block_offset);      // (a grid-stride loop)
+    jacobi_transpose_adaptive_any_kernel<T, I><<<dim3(nb), dim3(256), 0, as_stream(s)>>>(
         num_blocks, scheme, block_ptrs, blocks, precisions, conj, out);
     GKOC_LAUNCH_OK();
     return GKOC_OK;
@@ -2411,9 +2410,8 @@ GKOC_DEF_JACOBI_ADAPTIVE_ANY(gkoc_c64, float, c64, int64_t, i64)
         GKOC_REQUIRE(scheme.block_offset >= 1, GKOC_E_INVALID, "bad storage scheme");       \
         GKOC_REQUIRE(precisions == nullptr || sizeof(T) == 8, GKOC_E_NOT_SUPPORTED,         \
                      "reduced float blocks: gkoc_jacobi_transpose_adaptive_f32_*");         \
-        int64_t nb = ceildiv(num_blocks * scheme.block_offset, 256);                        \
-        if (nb > 4 * max_stream_blocks) nb = 4 * max_stream_blocks;                         \
-        jacobi_transpose_kernel<T, I><<<dim3(unsigned(nb)), dim3(256), 0, as_stream(s)>>>(  \
+        const unsigned nb = stream_grid(num_blocks * scheme.block_offset);                  \
+        jacobi_transpose_kernel<T, I><<<dim3(nb), dim3(256), 0, as_stream(s)>>>(            \
             num_blocks, scheme, block_ptrs, blocks, precisions, out_blocks);                \
         GKOC_LAUNCH_OK();                                                                   \
         return GKOC_OK;                                                                     \

@@ -14,13 +14,6 @@
 namespace gkoc {
 namespace {
 
-inline unsigned grid_of(int64_t n)
-{
-    int64_t b = ceildiv(n > 0 ? n : 1, 256);
-    if (b > 4 * max_stream_blocks) b = 4 * max_stream_blocks;
-    return unsigned(b);
-}
-
 #define GKOC_FOR(i, n)                                                                               \
     for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x, i##_stride = int64_t(gridDim.x) * 256; \
          i < (n); i += i##_stride)
@@ -175,7 +168,7 @@ using namespace gkoc;
                                                      int64_t ldc, int inverse)                              \
     {                                                                                                       \
         if (rows <= 0 || cols <= 0) return GKOC_OK;                                                         \
-        diag_dense_kernel<T><<<dim3(grid_of(rows * cols)), dim3(256), 0, as_stream(s)>>>(                   \
+        diag_dense_kernel<T><<<dim3(stream_grid(rows * cols)), dim3(256), 0, as_stream(s)>>>(               \
             rows, cols, diag, b, ldb, c, ldc, inverse ? 1 : 0);                                             \
         GKOC_LAUNCH_OK();                                                                                   \
         return GKOC_OK;                                                                                     \
@@ -185,7 +178,7 @@ using namespace gkoc;
                                                            int64_t ldc)                                     \
     {                                                                                                       \
         if (rows <= 0 || cols <= 0) return GKOC_OK;                                                         \
-        diag_dense_kernel<T><<<dim3(grid_of(rows * cols)), dim3(256), 0, as_stream(s)>>>(                   \
+        diag_dense_kernel<T><<<dim3(stream_grid(rows * cols)), dim3(256), 0, as_stream(s)>>>(               \
             rows, cols, diag, b, ldb, c, ldc, 2);                                                           \
         GKOC_LAUNCH_OK();                                                                                   \
         return GKOC_OK;                                                                                     \
@@ -213,14 +206,14 @@ extern "C" int gkoc_reduce_add_array_u64(gkoc_stream_t s, int64_t n, const uint6
 extern "C" int gkoc_convert_precision_f32_f64(gkoc_stream_t s, int64_t n, const float* in, double* out)
 {
     if (n <= 0) return GKOC_OK;
-    convert_kernel<float, double><<<dim3(grid_of(n)), dim3(256), 0, as_stream(s)>>>(n, in, out);
+    convert_kernel<float, double><<<dim3(stream_grid(n)), dim3(256), 0, as_stream(s)>>>(n, in, out);
     GKOC_LAUNCH_OK();
     return GKOC_OK;
 }
 extern "C" int gkoc_convert_precision_f64_f32(gkoc_stream_t s, int64_t n, const double* in, float* out)
 {
     if (n <= 0) return GKOC_OK;
-    convert_kernel<double, float><<<dim3(grid_of(n)), dim3(256), 0, as_stream(s)>>>(n, in, out);
+    convert_kernel<double, float><<<dim3(stream_grid(n)), dim3(256), 0, as_stream(s)>>>(n, in, out);
     GKOC_LAUNCH_OK();
     return GKOC_OK;
 }
@@ -230,7 +223,7 @@ extern "C" int gkoc_convert_precision_f64_f32(gkoc_stream_t s, int64_t n, const 
                                                           const I* row_ptrs, T* vals, int inverse)          \
     {                                                                                                       \
         if (n_rows <= 0) return GKOC_OK;                                                                    \
-        diag_csr_rows_kernel<T, I><<<dim3(grid_of(n_rows * 64)), dim3(256), 0, as_stream(s)>>>(             \
+        diag_csr_rows_kernel<T, I><<<dim3(stream_grid(n_rows * 64)), dim3(256), 0, as_stream(s)>>>(         \
             n_rows, diag, row_ptrs, vals, inverse);                                                         \
         GKOC_LAUNCH_OK();                                                                                   \
         return GKOC_OK;                                                                                     \
@@ -239,7 +232,7 @@ extern "C" int gkoc_convert_precision_f64_f32(gkoc_stream_t s, int64_t n, const 
                                                                 const T* diag, const I* cols, T* vals)      \
     {                                                                                                       \
         if (nnz <= 0) return GKOC_OK;                                                                       \
-        diag_csr_cols_kernel<T, I><<<dim3(grid_of(nnz)), dim3(256), 0, as_stream(s)>>>(nnz, diag, cols,     \
+        diag_csr_cols_kernel<T, I><<<dim3(stream_grid(nnz)), dim3(256), 0, as_stream(s)>>>(nnz, diag, cols, \
                                                                                       vals);                \
         GKOC_LAUNCH_OK();                                                                                   \
         return GKOC_OK;                                                                                     \
@@ -248,7 +241,7 @@ extern "C" int gkoc_convert_precision_f64_f32(gkoc_stream_t s, int64_t n, const 
                                                             I* row_ptrs, I* cols, T* vals)                  \
     {                                                                                                       \
         gkoc::csr_structure_written(row_ptrs); gkoc::csr_structure_written(cols);                           \
-        diag_to_csr_kernel<T, I><<<dim3(grid_of(n + 1)), dim3(256), 0, as_stream(s)>>>(n, diag, row_ptrs,   \
+        diag_to_csr_kernel<T, I><<<dim3(stream_grid(n + 1)), dim3(256), 0, as_stream(s)>>>(n, diag, row_ptrs,   \
                                                                                       cols, vals);          \
         GKOC_LAUNCH_OK();                                                                                   \
         return GKOC_OK;                                                                                     \
@@ -258,7 +251,7 @@ extern "C" int gkoc_convert_precision_f64_f32(gkoc_stream_t s, int64_t n, const 
                                                                  const T* vals, T* diag)                    \
     {                                                                                                       \
         if (nnz <= 0) return GKOC_OK;                                                                       \
-        diag_fill_kernel<T, I><<<dim3(grid_of(nnz)), dim3(256), 0, as_stream(s)>>>(nnz, rows, cols, vals,   \
+        diag_fill_kernel<T, I><<<dim3(stream_grid(nnz)), dim3(256), 0, as_stream(s)>>>(nnz, rows, cols, vals,   \
                                                                                   diag);                    \
         GKOC_LAUNCH_OK();                                                                                   \
         return GKOC_OK;                                                                                     \
@@ -276,7 +269,7 @@ GKOC_DEF_MISC_TI(gkoc_c64, c64, int64_t, i64)
     extern "C" int gkoc_sparsity_csr_count_diagonal_##IN(gkoc_stream_t s, int64_t n_rows,                   \
                                                          const I* row_ptrs, const I* cols, I* counts)       \
     {                                                                                                       \
-        count_diag_kernel<I><<<dim3(grid_of(n_rows + 1)), dim3(256), 0, as_stream(s)>>>(n_rows, row_ptrs,   \
+        count_diag_kernel<I><<<dim3(stream_grid(n_rows + 1)), dim3(256), 0, as_stream(s)>>>(n_rows, row_ptrs,   \
                                                                                        cols, counts);       \
         GKOC_LAUNCH_OK();                                                                                   \
         return GKOC_OK;                                                                                     \
@@ -287,7 +280,7 @@ GKOC_DEF_MISC_TI(gkoc_c64, c64, int64_t, i64)
                                                           I* adj_idxs)                                      \
     {                                                                                                       \
         gkoc::csr_structure_written(adj_ptrs); gkoc::csr_structure_written(adj_idxs);                       \
-        remove_diag_kernel<I><<<dim3(grid_of(n_rows + 1)), dim3(256), 0, as_stream(s)>>>(                   \
+        remove_diag_kernel<I><<<dim3(stream_grid(n_rows + 1)), dim3(256), 0, as_stream(s)>>>(               \
             n_rows, row_ptrs, cols, diag_prefix_sum, adj_ptrs, adj_idxs);                                   \
         GKOC_LAUNCH_OK();                                                                                   \
         return GKOC_OK;                                                                                     \
@@ -313,7 +306,7 @@ extern "C" int gkoc_fill_array_small(gkoc_stream_t s, void* data, int64_t n, int
     GKOC_REQUIRE(elem_bytes == 1 || elem_bytes == 2 || elem_bytes == 4, GKOC_E_INVALID, "elem_bytes");
     if (n <= 0) return GKOC_OK;
     gkoc::csr_structure_written(data, size_t(n) * size_t(elem_bytes));
-    const dim3 g(grid_of(n));
+    const dim3 g(stream_grid(n));
     if (elem_bytes == 1) {
         fill_small_kernel<uint8_t><<<g, dim3(256), 0, as_stream(s)>>>(n, static_cast<uint8_t*>(data), uint8_t(pattern));
     } else if (elem_bytes == 2) {
@@ -424,7 +417,7 @@ __global__ __launch_bounds__(256) void spgeam_numeric_kernel(
         if (n_rows <= 0) return GKOC_OK;                                                                    \
         GKOC_REQUIRE((alpha == nullptr) == (beta == nullptr) && (alpha == nullptr || d_ptrs),               \
                      GKOC_E_INVALID, "alpha, beta and d go together");                                      \
-        spgemm_reuse_kernel<T, I><<<dim3(grid_of(n_rows)), dim3(256), 0, as_stream(s)>>>(                   \
+        spgemm_reuse_kernel<T, I><<<dim3(stream_grid(n_rows)), dim3(256), 0, as_stream(s)>>>(               \
             n_rows, a_ptrs, a_cols, a_vals, b_ptrs, b_cols, b_vals, alpha, beta, d_ptrs, d_cols, d_vals,    \
             c_ptrs, c_cols, c_vals);                                                                        \
         GKOC_LAUNCH_OK();                                                                                   \
@@ -436,7 +429,7 @@ __global__ __launch_bounds__(256) void spgeam_numeric_kernel(
         const I* c_ptrs, T* c_vals)                                                                         \
     {                                                                                                       \
         if (n_rows <= 0) return GKOC_OK;                                                                    \
-        spgeam_numeric_kernel<T, I><<<dim3(grid_of(n_rows)), dim3(256), 0, as_stream(s)>>>(                 \
+        spgeam_numeric_kernel<T, I><<<dim3(stream_grid(n_rows)), dim3(256), 0, as_stream(s)>>>(             \
             n_rows, alpha, a_ptrs, a_cols, a_vals, beta, b_ptrs, b_cols, b_vals, c_ptrs, c_vals);           \
         GKOC_LAUNCH_OK();                                                                                   \
         return GKOC_OK;                                                                                     \

@@ -38,7 +38,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
-#include "factorization_common.hpp"
+#include "sparse_rows.hpp"
 
 namespace gkoc {
 namespace {
@@ -152,14 +152,13 @@ template <bool IC, int W, typename T, typename I>
 int sweeps_launch(hipStream_t st, int64_t n, const I* rp, const I* ci, const I* diag, const T* a, const T* v0,
                   int64_t iterations, T* work, T* out, uint64_t* changed)
 {
-    int64_t blocks = ceildiv(n, sweep_block / W);
-    if (blocks > 4 * max_stream_blocks) blocks = 4 * max_stream_blocks;
+    const unsigned blocks = stream_grid(n, sweep_block / W);
     for (int64_t t = 1; t <= iterations; ++t) {
         // sweep t writes out if iterations - t is even: the last one always does
         const bool to_out = (iterations - t) % 2 == 0;
         T* next = to_out ? out : work;
         const T* prev = t == 1 ? v0 : (to_out ? work : out);
-        par_sweep_kernel<IC, W, T, I><<<dim3(unsigned(blocks)), dim3(sweep_block), 0, st>>>(
+        par_sweep_kernel<IC, W, T, I><<<dim3(blocks), dim3(sweep_block), 0, st>>>(
             n, rp, ci, diag, a, prev, next,
             t == iterations ? reinterpret_cast<unsigned long long*>(changed) : nullptr);
         GKOC_LAUNCH_OK();
@@ -194,31 +193,20 @@ int par_sweeps(gkoc_stream_t s, int64_t n, int64_t nnz, const I* rp, const I* ci
     GKOC_REQUIRE(v0 == a || (!overlap(v0, out, bytes) && (!work || !overlap(v0, work, bytes))), GKOC_E_INVALID,
                  "v0_vals must not overlap work or out_vals");
     // scratch: 4 status words, then the diagonal positions
-    void* raw = nullptr;
-    GKOC_TRY(scratch_malloc(st, &raw, 16 + sizeof(I) * size_t(n)));
-    scratch_guard guard{st, raw};
-    int* status = static_cast<int*>(raw);
-    I* diag = reinterpret_cast<I*>(static_cast<char*>(raw) + 16);
-    GKOC_HIP(hipMemsetAsync(status, 0, 16, st));
-    int64_t blocks = ceildiv(n, 256);
-    if (blocks > 4 * max_stream_blocks) blocks = 4 * max_stream_blocks;
-    locate_diagonals_kernel<I><<<dim3(unsigned(blocks)), dim3(256), 0, st>>>(n, nnz, rp, ci, diag, status);
+    status_words<4> status(st);
+    GKOC_TRY(status.init(sizeof(I) * size_t(n)));
+    I* diag = status.template behind<I>();
+    locate_diagonals_kernel<I><<<dim3(stream_grid(n)), dim3(256), 0, st>>>(n, nnz, rp, ci, diag, status.dev);
     GKOC_LAUNCH_OK();
-    int host[4] = {0, 0, 0, 0};
-    GKOC_HIP(hipMemcpyAsync(host, status, 16, hipMemcpyDeviceToHost, st));
-    GKOC_HIP(hipStreamSynchronize(st));
-    GKOC_REQUIRE(host[0] == 0, GKOC_E_INVALID,
+    GKOC_TRY(status.read());
+    GKOC_REQUIRE(status[0] == 0, GKOC_E_INVALID,
                  "row pointers that do not ascend from 0 to nnz, or a column outside the matrix");
-    GKOC_REQUIRE(host[1] == 0, GKOC_E_INVALID, "a row without a stored diagonal");
-    GKOC_REQUIRE(!IC || host[2] == 0, GKOC_E_INVALID, "a row whose last entry is not its diagonal");
+    GKOC_REQUIRE(status[1] == 0, GKOC_E_INVALID, "a row without a stored diagonal");
+    GKOC_REQUIRE(!IC || status[2] == 0, GKOC_E_INVALID, "a row whose last entry is not its diagonal");
     if (changed) GKOC_HIP(hipMemsetAsync(changed, 0, sizeof(uint64_t), st));
-    if (host[3] <= fact_row_limits[0]) {
-        return sweeps_launch<IC, 16, T, I>(st, n, rp, ci, diag, a, v0, iterations, work, out, changed);
-    }
-    if (host[3] <= fact_row_limits[1]) {
-        return sweeps_launch<IC, 32, T, I>(st, n, rp, ci, diag, a, v0, iterations, work, out, changed);
-    }
-    return sweeps_launch<IC, 64, T, I>(st, n, rp, ci, diag, a, v0, iterations, work, out, changed);
+    return with_lanes(status[3], fact_row_limits, [&](auto w) {
+        return sweeps_launch<IC, decltype(w)::value, T, I>(st, n, rp, ci, diag, a, v0, iterations, work, out, changed);
+    });
 }
 
 }  // namespace

@@ -27,7 +27,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
-#include "factorization_common.hpp"
+#include "sparse_rows.hpp"
 
 namespace gkoc {
 namespace {
@@ -148,27 +148,20 @@ template <bool IC, int W, typename T, typename I>
 int candidate_launch(hipStream_t st, int64_t n, const I* p_rp, const I* p_ci, const I* a_rp, const I* a_ci,
                      const T* a_v, const I* m_rp, const I* m_ci, const T* m_v, const I* m_diag, T* out)
 {
-    int64_t blocks = ceildiv(n, ilut_block / W);
-    if (blocks > 4 * max_stream_blocks) blocks = 4 * max_stream_blocks;
-    candidate_kernel<IC, W, T, I><<<dim3(unsigned(blocks)), dim3(ilut_block), 0, st>>>(
+    candidate_kernel<IC, W, T, I><<<dim3(stream_grid(n, ilut_block / W)), dim3(ilut_block), 0, st>>>(
         n, p_rp, p_ci, a_rp, a_ci, a_v, m_rp, m_ci, m_v, m_diag, out);
     GKOC_LAUNCH_OK();
     return GKOC_OK;
 }
 
-inline int64_t stream_blocks(int64_t n)
-{
-    const int64_t blocks = ceildiv(n, ilut_block / stream_lanes);
-    return blocks > max_stream_blocks ? max_stream_blocks : blocks;
-}
+// the grid of the plain streaming kernels
+inline unsigned stream_blocks(int64_t n) { return capped_grid(n, ilut_block / stream_lanes, max_stream_blocks); }
 
 // the checking pass of the sweeps on one matrix: status (4 ints) and diag (n_rows entries) in scratch
 template <typename I>
 int locate(hipStream_t st, int64_t n, int64_t nnz, const I* rp, const I* ci, I* diag, int* status)
 {
-    int64_t blocks = ceildiv(n, 256);
-    if (blocks > 4 * max_stream_blocks) blocks = 4 * max_stream_blocks;
-    locate_diagonals_kernel<I><<<dim3(unsigned(blocks)), dim3(256), 0, st>>>(n, nnz, rp, ci, diag, status);
+    locate_diagonals_kernel<I><<<dim3(stream_grid(n)), dim3(256), 0, st>>>(n, nnz, rp, ci, diag, status);
     GKOC_LAUNCH_OK();
     return GKOC_OK;
 }
@@ -187,21 +180,15 @@ int gather(gkoc_stream_t s, int64_t n, int64_t p_nnz, const I* p_rp, const I* p_
                  GKOC_E_INVALID, "null pointer");
     hipStream_t st = as_stream(s);
     // scratch: 2 x 4 status words, then one array of diagonal positions that both checks write (not used)
-    void* raw = nullptr;
-    GKOC_TRY(scratch_malloc(st, &raw, 32 + sizeof(I) * size_t(n)));
-    scratch_guard guard{st, raw};
-    int* status = static_cast<int*>(raw);
-    I* diag = reinterpret_cast<I*>(static_cast<char*>(raw) + 32);
-    GKOC_HIP(hipMemsetAsync(status, 0, 32, st));
-    GKOC_TRY(locate(st, n, p_nnz, p_rp, p_ci, diag, status));
-    GKOC_TRY(locate(st, n, s_nnz, s_rp, s_ci, diag, status + 4));
-    int host[8] = {};
-    GKOC_HIP(hipMemcpyAsync(host, status, 32, hipMemcpyDeviceToHost, st));
-    GKOC_HIP(hipStreamSynchronize(st));
-    GKOC_REQUIRE(host[0] == 0 && host[4] == 0, GKOC_E_INVALID, bad_structure);
+    status_words<8> status(st);
+    GKOC_TRY(status.init(sizeof(I) * size_t(n)));
+    I* diag = status.template behind<I>();
+    GKOC_TRY(locate(st, n, p_nnz, p_rp, p_ci, diag, status.dev));
+    GKOC_TRY(locate(st, n, s_nnz, s_rp, s_ci, diag, status.dev + 4));
+    GKOC_TRY(status.read());
+    GKOC_REQUIRE(status[0] == 0 && status[4] == 0, GKOC_E_INVALID, bad_structure);
     if (p_nnz == 0) return GKOC_OK;
-    gather_kernel<T, I><<<dim3(unsigned(stream_blocks(n))), dim3(ilut_block), 0, st>>>(n, p_rp, p_ci, s_rp, s_ci,
-                                                                                       s_v, out);
+    gather_kernel<T, I><<<dim3(stream_blocks(n)), dim3(ilut_block), 0, st>>>(n, p_rp, p_ci, s_rp, s_ci, s_v, out);
     GKOC_LAUNCH_OK();
     return GKOC_OK;
 }
@@ -221,37 +208,28 @@ int candidate_values(gkoc_stream_t s, int64_t n, int64_t p_nnz, const I* p_rp, c
     hipStream_t st = as_stream(s);
     // scratch: 4 x 4 status words (pattern, a, m, containment), the diagonal positions of m, and an array for
     // the positions of the other two, which nothing reads
-    void* raw = nullptr;
-    GKOC_TRY(scratch_malloc(st, &raw, 64 + 2 * sizeof(I) * size_t(n)));
-    scratch_guard guard{st, raw};
-    int* status = static_cast<int*>(raw);
-    I* m_diag = reinterpret_cast<I*>(static_cast<char*>(raw) + 64);
+    status_words<16> status(st);
+    GKOC_TRY(status.init(2 * sizeof(I) * size_t(n)));
+    I* m_diag = status.template behind<I>();
     I* unused = m_diag + n;
-    GKOC_HIP(hipMemsetAsync(status, 0, 64, st));
-    GKOC_TRY(locate(st, n, p_nnz, p_rp, p_ci, unused, status));
-    GKOC_TRY(locate(st, n, a_nnz, a_rp, a_ci, unused, status + 4));
-    GKOC_TRY(locate(st, n, m_nnz, m_rp, m_ci, m_diag, status + 8));
-    int host[16] = {};
-    GKOC_HIP(hipMemcpyAsync(host, status, 48, hipMemcpyDeviceToHost, st));
-    GKOC_HIP(hipStreamSynchronize(st));
-    GKOC_REQUIRE(host[0] == 0 && host[4] == 0 && host[8] == 0, GKOC_E_INVALID, bad_structure);
-    GKOC_REQUIRE(host[1] == 0 && host[9] == 0, GKOC_E_INVALID, "a row without a stored diagonal");
-    GKOC_REQUIRE(!IC || (host[2] == 0 && host[10] == 0), GKOC_E_INVALID,
+    GKOC_TRY(locate(st, n, p_nnz, p_rp, p_ci, unused, status.dev));
+    GKOC_TRY(locate(st, n, a_nnz, a_rp, a_ci, unused, status.dev + 4));
+    GKOC_TRY(locate(st, n, m_nnz, m_rp, m_ci, m_diag, status.dev + 8));
+    GKOC_TRY(status.read());
+    GKOC_REQUIRE(status[0] == 0 && status[4] == 0 && status[8] == 0, GKOC_E_INVALID, bad_structure);
+    GKOC_REQUIRE(status[1] == 0 && status[9] == 0, GKOC_E_INVALID, "a row without a stored diagonal");
+    GKOC_REQUIRE(!IC || (status[2] == 0 && status[10] == 0), GKOC_E_INVALID,
                  "a row whose last entry is not its diagonal");
     // the rows are valid now: the containment check may search them
-    contains_kernel<I><<<dim3(unsigned(stream_blocks(n))), dim3(ilut_block), 0, st>>>(n, p_rp, p_ci, m_rp, m_ci,
-                                                                                     status + 12);
+    contains_kernel<I><<<dim3(stream_blocks(n)), dim3(ilut_block), 0, st>>>(n, p_rp, p_ci, m_rp, m_ci,
+                                                                           status.dev + 12);
     GKOC_LAUNCH_OK();
-    GKOC_HIP(hipMemcpyAsync(host + 12, status + 12, 4, hipMemcpyDeviceToHost, st));
-    GKOC_HIP(hipStreamSynchronize(st));
-    GKOC_REQUIRE(host[12] == 0, GKOC_E_INVALID, "the pattern does not contain the pattern of the factor");
-    if (host[3] <= fact_row_limits[0]) {
-        return candidate_launch<IC, 16, T, I>(st, n, p_rp, p_ci, a_rp, a_ci, a_v, m_rp, m_ci, m_v, m_diag, out);
-    }
-    if (host[3] <= fact_row_limits[1]) {
-        return candidate_launch<IC, 32, T, I>(st, n, p_rp, p_ci, a_rp, a_ci, a_v, m_rp, m_ci, m_v, m_diag, out);
-    }
-    return candidate_launch<IC, 64, T, I>(st, n, p_rp, p_ci, a_rp, a_ci, a_v, m_rp, m_ci, m_v, m_diag, out);
+    GKOC_TRY(status.read());
+    GKOC_REQUIRE(status[12] == 0, GKOC_E_INVALID, "the pattern does not contain the pattern of the factor");
+    return with_lanes(status[3], fact_row_limits, [&](auto w) {
+        return candidate_launch<IC, decltype(w)::value, T, I>(st, n, p_rp, p_ci, a_rp, a_ci, a_v, m_rp, m_ci, m_v,
+                                                              m_diag, out);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------- select
@@ -356,7 +334,7 @@ int threshold_select(gkoc_stream_t s, int64_t n, const I* rp, const I* ci, const
     select_state* state = static_cast<select_state*>(work);
     unsigned long long* tables = reinterpret_cast<unsigned long long*>(state + 1);
     GKOC_HIP(hipMemsetAsync(work, 0, select_bytes, st));
-    const unsigned blocks = unsigned(stream_blocks(n));
+    const unsigned blocks = stream_blocks(n);
     for (int pass = 0; pass < bits_of<T>::passes; ++pass) {
         select_count_kernel<T, I><<<dim3(blocks), dim3(ilut_block), 0, st>>>(n, rp, ci, v, part, pass, state,
                                                                              tables + 256 * pass);
@@ -405,19 +383,15 @@ int keep_mask(gkoc_stream_t s, int64_t n, int64_t nnz, const I* rp, const I* ci,
     if (n == 0) return GKOC_OK;
     GKOC_REQUIRE(rp && thr_lower && (nnz == 0 || (ci && v && mask)), GKOC_E_INVALID, "null pointer");
     hipStream_t st = as_stream(s);
-    void* raw = nullptr;
-    GKOC_TRY(scratch_malloc(st, &raw, 16 + sizeof(I) * size_t(n)));
-    scratch_guard guard{st, raw};
-    int* status = static_cast<int*>(raw);
-    GKOC_HIP(hipMemsetAsync(status, 0, 16, st));
-    GKOC_TRY(locate(st, n, nnz, rp, ci, reinterpret_cast<I*>(static_cast<char*>(raw) + 16), status));
-    int host[4] = {};
-    GKOC_HIP(hipMemcpyAsync(host, status, 16, hipMemcpyDeviceToHost, st));
-    GKOC_HIP(hipStreamSynchronize(st));
-    GKOC_REQUIRE(host[0] == 0, GKOC_E_INVALID, bad_structure);
+    // scratch: 4 status words, then the diagonal positions (not used)
+    status_words<4> status(st);
+    GKOC_TRY(status.init(sizeof(I) * size_t(n)));
+    GKOC_TRY(locate(st, n, nnz, rp, ci, status.template behind<I>(), status.dev));
+    GKOC_TRY(status.read());
+    GKOC_REQUIRE(status[0] == 0, GKOC_E_INVALID, bad_structure);
     if (nnz == 0) return GKOC_OK;
-    keep_mask_kernel<T, I><<<dim3(unsigned(stream_blocks(n))), dim3(ilut_block), 0, st>>>(n, rp, ci, v, thr_lower,
-                                                                                         thr_upper, mask);
+    keep_mask_kernel<T, I><<<dim3(stream_blocks(n)), dim3(ilut_block), 0, st>>>(n, rp, ci, v, thr_lower, thr_upper,
+                                                                               mask);
     GKOC_LAUNCH_OK();
     return GKOC_OK;
 }

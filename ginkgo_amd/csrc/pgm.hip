@@ -31,6 +31,7 @@
 
 #include "common.hpp"
 #include "scan.hpp"
+#include "sparse_rows.hpp"
 
 namespace gkoc {
 namespace {
@@ -38,19 +39,11 @@ namespace {
 constexpr int pgm_block = 256;
 constexpr int pgm_row_limits[] = {16, 32, 64};
 
-struct scratch_guard {
-    hipStream_t st;
-    void* ptr;
-    ~scratch_guard()
-    {
-        if (ptr) (void)scratch_free(st, ptr);
-    }
-};
-
-inline unsigned capped_grid(int64_t blocks)
+// this file's grids: at most max_stream_blocks workgroups (the partials per block that match and check_csr
+// read back have that many places)
+inline unsigned pgm_grid(int64_t items, int per_block = pgm_block)
 {
-    if (blocks > max_stream_blocks) blocks = max_stream_blocks;
-    return unsigned(blocks < 1 ? 1 : blocks);
+    return capped_grid(items, per_block, max_stream_blocks);
 }
 
 // ------------------------------------------------------------------ the key
@@ -355,20 +348,11 @@ __global__ __launch_bounds__(pgm_block) void prolong_add_kernel(int64_t n, int64
 }
 
 // ------------------------------------------------------------------ host side
-// flags (zeroed device ints) to the host; synchronises the stream
-template <int N>
-int read_flags(hipStream_t st, const int* flags_dev, int (&host)[N])
-{
-    GKOC_HIP(hipMemcpyAsync(host, flags_dev, sizeof(int) * N, hipMemcpyDeviceToHost, st));
-    GKOC_HIP(hipStreamSynchronize(st));
-    return GKOC_OK;
-}
-
 // checks W's index arrays; *longest = its longest row
 template <typename I>
 int check_csr(hipStream_t st, int64_t n, const I* rp, const I* ci, int* longest)
 {
-    const unsigned grid = capped_grid(ceildiv(n, pgm_block));
+    const unsigned grid = pgm_grid(n);
     void* raw = nullptr;
     GKOC_TRY(scratch_malloc(st, &raw, sizeof(int) * (2 + size_t(grid))));
     scratch_guard guard{st, raw};
@@ -391,7 +375,7 @@ int select_launch(hipStream_t st, int64_t n, const I* rp, const I* ci, const T* 
                   I* out)
 {
     select_kernel<LEFTOVER, W, T, I>
-        <<<dim3(capped_grid(ceildiv(n, pgm_block / W)) * 4), dim3(pgm_block), 0, st>>>(n, rp, ci, wv, d, agg, out);
+        <<<dim3(pgm_grid(n, pgm_block / W) * 4), dim3(pgm_block), 0, st>>>(n, rp, ci, wv, d, agg, out);
     GKOC_LAUNCH_OK();
     return GKOC_OK;
 }
@@ -406,9 +390,9 @@ int select(gkoc_stream_t s, int64_t n, const I* rp, const I* ci, const T* wv, co
     hipStream_t st = as_stream(s);
     int longest = 0;
     GKOC_TRY(check_csr<I>(st, n, rp, ci, &longest));
-    if (longest <= pgm_row_limits[0]) return select_launch<LEFTOVER, 16, T, I>(st, n, rp, ci, wv, d, agg, out);
-    if (longest <= pgm_row_limits[1]) return select_launch<LEFTOVER, 32, T, I>(st, n, rp, ci, wv, d, agg, out);
-    return select_launch<LEFTOVER, 64, T, I>(st, n, rp, ci, wv, d, agg, out);
+    return with_lanes(longest, pgm_row_limits, [&](auto w) {
+        return select_launch<LEFTOVER, decltype(w)::value, T, I>(st, n, rp, ci, wv, d, agg, out);
+    });
 }
 
 template <typename I>
@@ -421,17 +405,14 @@ int match(gkoc_stream_t s, int64_t n, const I* prop, I* agg, long long* unassign
     GKOC_REQUIRE(prop && agg, GKOC_E_INVALID, "null pointer");
     GKOC_REQUIRE(prop != agg, GKOC_E_INVALID, "the proposals and the aggregation are one array");
     hipStream_t st = as_stream(s);
-    const unsigned grid = capped_grid(ceildiv(n, pgm_block));
-    void* raw = nullptr;
-    GKOC_TRY(scratch_malloc(st, &raw, sizeof(long long) * (1 + size_t(grid))));
-    scratch_guard guard{st, raw};
-    long long* counts = static_cast<long long*>(raw) + 1;
-    int* flag = static_cast<int*>(raw);
-    GKOC_HIP(hipMemsetAsync(raw, 0, sizeof(long long), st));
-    check_proposals_kernel<I><<<dim3(grid), dim3(pgm_block), 0, st>>>(n, prop, flag);
+    const unsigned grid = pgm_grid(n);
+    // scratch: the flag, then one count per block
+    status_words<1> bad(st);
+    GKOC_TRY(bad.init(sizeof(long long) * size_t(grid)));
+    long long* counts = bad.template behind<long long>();
+    check_proposals_kernel<I><<<dim3(grid), dim3(pgm_block), 0, st>>>(n, prop, bad.dev);
     GKOC_LAUNCH_OK();
-    int bad[1] = {0};
-    GKOC_TRY(read_flags(st, flag, bad));
+    GKOC_TRY(bad.read());
     GKOC_REQUIRE(bad[0] == 0, GKOC_E_INVALID, "a proposal outside the matrix");
     match_kernel<I><<<dim3(grid), dim3(pgm_block), 0, st>>>(n, prop, agg);
     GKOC_LAUNCH_OK();
@@ -453,19 +434,14 @@ int renumber(gkoc_stream_t s, int64_t n, I* agg, long long* num_aggregates_host)
     if (n == 0) return GKOC_OK;
     GKOC_REQUIRE(agg, GKOC_E_INVALID, "null pointer");
     hipStream_t st = as_stream(s);
-    const unsigned grid = capped_grid(ceildiv(n + 1, pgm_block));
-    // scratch: the ranks (n + 1 entries), then the flag
-    const size_t rank_bytes = (sizeof(I) * size_t(n + 1) + 7) / 8 * 8;
-    void* raw = nullptr;
-    GKOC_TRY(scratch_malloc(st, &raw, rank_bytes + sizeof(int)));
-    scratch_guard guard{st, raw};
-    I* rank = static_cast<I*>(raw);
-    int* flag = reinterpret_cast<int*>(static_cast<char*>(raw) + rank_bytes);
-    GKOC_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
-    check_roots_kernel<I><<<dim3(grid), dim3(pgm_block), 0, st>>>(n, agg, flag);
+    const unsigned grid = pgm_grid(n + 1);
+    // scratch: the flag, then the ranks (n + 1 entries)
+    status_words<1> bad(st);
+    GKOC_TRY(bad.init(sizeof(I) * size_t(n + 1)));
+    I* rank = bad.template behind<I>();
+    check_roots_kernel<I><<<dim3(grid), dim3(pgm_block), 0, st>>>(n, agg, bad.dev);
     GKOC_LAUNCH_OK();
-    int bad[1] = {0};
-    GKOC_TRY(read_flags(st, flag, bad));
+    GKOC_TRY(bad.read());
     GKOC_REQUIRE(bad[0] == 0, GKOC_E_INVALID, "an entry of agg is not the root of an aggregate");
     mark_roots_kernel<I><<<dim3(grid), dim3(pgm_block), 0, st>>>(n, agg, rank);
     GKOC_LAUNCH_OK();
@@ -487,20 +463,16 @@ int map_entries(gkoc_stream_t s, int64_t nnz, int64_t n, int64_t n_c, const I* a
     if (nnz == 0) return GKOC_OK;
     GKOC_REQUIRE(agg && rows_in && cols_in && vals && entries, GKOC_E_INVALID, "null pointer");
     hipStream_t st = as_stream(s);
-    const unsigned grid = capped_grid(ceildiv(nnz, pgm_block)), grid_n = capped_grid(ceildiv(n, pgm_block));
-    void* raw = nullptr;
-    GKOC_TRY(scratch_malloc(st, &raw, 2 * sizeof(int)));
-    scratch_guard guard{st, raw};
-    int* flags = static_cast<int*>(raw);
-    GKOC_HIP(hipMemsetAsync(flags, 0, 2 * sizeof(int), st));
-    check_range_kernel<I><<<dim3(grid_n), dim3(pgm_block), 0, st>>>(n, agg, 0, n_c, flags);
+    const unsigned grid = pgm_grid(nnz), grid_n = pgm_grid(n);
+    status_words<2> bad(st);
+    GKOC_TRY(bad.init());
+    check_range_kernel<I><<<dim3(grid_n), dim3(pgm_block), 0, st>>>(n, agg, 0, n_c, bad.dev);
     GKOC_LAUNCH_OK();
-    check_range_kernel<I><<<dim3(grid), dim3(pgm_block), 0, st>>>(nnz, rows_in, 0, n, flags + 1);
+    check_range_kernel<I><<<dim3(grid), dim3(pgm_block), 0, st>>>(nnz, rows_in, 0, n, bad.dev + 1);
     GKOC_LAUNCH_OK();
-    check_range_kernel<I><<<dim3(grid), dim3(pgm_block), 0, st>>>(nnz, cols_in, 0, n, flags + 1);
+    check_range_kernel<I><<<dim3(grid), dim3(pgm_block), 0, st>>>(nnz, cols_in, 0, n, bad.dev + 1);
     GKOC_LAUNCH_OK();
-    int bad[2] = {0, 0};
-    GKOC_TRY(read_flags(st, flags, bad));
+    GKOC_TRY(bad.read());
     GKOC_REQUIRE(bad[0] == 0, GKOC_E_INVALID, "an entry of agg outside [0, n_coarse)");
     GKOC_REQUIRE(bad[1] == 0, GKOC_E_INVALID, "a row or column index outside the matrix");
     map_entries_kernel<T, I><<<dim3(grid), dim3(pgm_block), 0, st>>>(nnz, agg, rows_in, cols_in, vals,
@@ -517,20 +489,16 @@ int check_transfers(gkoc_stream_t s, int64_t n, int64_t n_c, const I* agg, const
     if (n == 0) return GKOC_OK;
     GKOC_REQUIRE(agg && member_ptrs && members, GKOC_E_INVALID, "null pointer");
     hipStream_t st = as_stream(s);
-    const unsigned grid = capped_grid(ceildiv(n + 1, pgm_block));
-    void* raw = nullptr;
-    GKOC_TRY(scratch_malloc(st, &raw, 3 * sizeof(int)));
-    scratch_guard guard{st, raw};
-    int* flags = static_cast<int*>(raw);
-    GKOC_HIP(hipMemsetAsync(flags, 0, 3 * sizeof(int), st));
-    check_range_kernel<I><<<dim3(grid), dim3(pgm_block), 0, st>>>(n, agg, 0, n_c, flags);
+    const unsigned grid = pgm_grid(n + 1);
+    status_words<3> bad(st);
+    GKOC_TRY(bad.init());
+    check_range_kernel<I><<<dim3(grid), dim3(pgm_block), 0, st>>>(n, agg, 0, n_c, bad.dev);
     GKOC_LAUNCH_OK();
-    check_ptrs_kernel<I><<<dim3(grid), dim3(pgm_block), 0, st>>>(n_c, member_ptrs, n, flags + 1);
+    check_ptrs_kernel<I><<<dim3(grid), dim3(pgm_block), 0, st>>>(n_c, member_ptrs, n, bad.dev + 1);
     GKOC_LAUNCH_OK();
-    check_range_kernel<I><<<dim3(grid), dim3(pgm_block), 0, st>>>(n, members, 0, n, flags + 2);
+    check_range_kernel<I><<<dim3(grid), dim3(pgm_block), 0, st>>>(n, members, 0, n, bad.dev + 2);
     GKOC_LAUNCH_OK();
-    int bad[3] = {0, 0, 0};
-    GKOC_TRY(read_flags(st, flags, bad));
+    GKOC_TRY(bad.read());
     GKOC_REQUIRE(bad[0] == 0, GKOC_E_INVALID, "an entry of agg outside [0, n_coarse)");
     GKOC_REQUIRE(bad[1] == 0, GKOC_E_INVALID, "the member pointers do not ascend from 0 to the number of rows");
     GKOC_REQUIRE(bad[2] == 0, GKOC_E_INVALID, "a member outside the matrix");
@@ -545,7 +513,7 @@ int restrict_apply(gkoc_stream_t s, int64_t n_c, int64_t cols, const I* member_p
     if (n_c == 0 || cols == 0) return GKOC_OK;
     GKOC_REQUIRE(member_ptrs && members && r && bc, GKOC_E_INVALID, "null pointer");
     GKOC_REQUIRE(ldr >= cols && ldbc >= cols, GKOC_E_INVALID, "a stride smaller than the number of columns");
-    restrict_kernel<T, I><<<dim3(capped_grid(ceildiv(n_c * cols, pgm_block)) * 4), dim3(pgm_block), 0,
+    restrict_kernel<T, I><<<dim3(pgm_grid(n_c * cols) * 4), dim3(pgm_block), 0,
                             as_stream(s)>>>(n_c, cols, member_ptrs, members, r, ldr, bc, ldbc);
     GKOC_LAUNCH_OK();
     return GKOC_OK;
@@ -559,7 +527,7 @@ int prolong_add(gkoc_stream_t s, int64_t n, int64_t cols, const I* agg, const T*
     if (n == 0 || cols == 0) return GKOC_OK;
     GKOC_REQUIRE(agg && e && x, GKOC_E_INVALID, "null pointer");
     GKOC_REQUIRE(lde >= cols && ldx >= cols, GKOC_E_INVALID, "a stride smaller than the number of columns");
-    prolong_add_kernel<T, I><<<dim3(capped_grid(ceildiv(n * cols, pgm_block)) * 4), dim3(pgm_block), 0,
+    prolong_add_kernel<T, I><<<dim3(pgm_grid(n * cols) * 4), dim3(pgm_block), 0,
                                as_stream(s)>>>(n, cols, agg, e, lde, x, ldx);
     GKOC_LAUNCH_OK();
     return GKOC_OK;
@@ -572,11 +540,7 @@ using namespace gkoc;
 
 extern "C" int gkoc_pgm_row_limits(int* limits_host, int* count_host)
 {
-    GKOC_REQUIRE(limits_host && count_host, GKOC_E_INVALID, "null pointer");
-    constexpr int count = int(sizeof(pgm_row_limits) / sizeof(pgm_row_limits[0]));
-    for (int p = 0; p < count; ++p) limits_host[p] = pgm_row_limits[p];
-    *count_host = count;
-    return GKOC_OK;
+    return export_row_limits(pgm_row_limits, limits_host, count_host);
 }
 
 // A: the header's gkoc_pgm_i32 / gkoc_pgm_i64 (an aggregation array; the same type as I)

@@ -32,21 +32,14 @@
 #include <vector>
 
 #include "common.hpp"
-#include "factorization_common.hpp"
 #include "scan.hpp"
+#include "sparse_rows.hpp"
 
 namespace gkoc {
 namespace {
 
 constexpr int symb_row_limits[] = {16, 32, 64};
 constexpr int symb_block = 256;
-
-inline unsigned symb_grid(int64_t items, int per_block)
-{
-    int64_t b = ceildiv(items, per_block);
-    if (b > 4 * max_stream_blocks) b = 4 * max_stream_blocks;
-    return unsigned(b < 1 ? 1 : b);
-}
 
 // ------------------------------------------------------------------ checks (one thread per row / vertex)
 // status[0]: row pointers or columns (keys) out of range, [1]: parent, [2]: post / inv_post, [3]: the longest row,
@@ -94,8 +87,7 @@ __global__ __launch_bounds__(symb_block) void symbolic_check_kernel(
             }
         }
     }
-    longest = wave_max(longest);
-    if ((threadIdx.x & (wave_size - 1)) == 0 && longest > 0) atomicMax(&status[3], longest);
+    note_longest(longest, &status[3]);
 }
 
 // filled[post[v]] = v wherever post[v] is inside [0, n) (the check kernel reports the others)
@@ -182,9 +174,7 @@ __device__ __forceinline__ void symbolic_row(int64_t row, int lane, const I* __r
     if (EXPAND) {
         if (lane == 0 && base >= 0 && base < total) entries[base] = pattern_entry<T, I>{I(row), I(row), T(1)};
     } else {
-        long long sum = mine;
-#pragma unroll
-        for (int off = W / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off, W);
+        const long long sum = group_sum<W>((long long)(mine));
         if (lane == 0) counts[row] = sum + 1;
     }
 }
@@ -211,7 +201,7 @@ int symbolic_rows_launch(hipStream_t st, int64_t n, const I* rp, const I* keys, 
                          const I* first, const I* inv_post, int64_t* counts, const int64_t* offsets, int64_t total,
                          pattern_entry<T, I>* entries)
 {
-    symbolic_rows_kernel<EXPAND, W, T, I><<<dim3(symb_grid(n, symb_block / W)), dim3(symb_block), 0, st>>>(
+    symbolic_rows_kernel<EXPAND, W, T, I><<<dim3(stream_grid(n, symb_block / W)), dim3(symb_block), 0, st>>>(
         n, rp, keys, parent, post, first, inv_post, counts, offsets, total, entries);
     GKOC_LAUNCH_OK();
     return GKOC_OK;
@@ -223,22 +213,17 @@ template <typename I>
 int symbolic_checked(hipStream_t st, int64_t n, int64_t nnz, const I* rp, const I* keys, const I* parent,
                      const I* post, const I* inv_post, int* longest_lower)
 {
-    void* raw = nullptr;
-    GKOC_TRY(scratch_malloc(st, &raw, 32));
-    scratch_guard guard{st, raw};
-    int* status = static_cast<int*>(raw);
-    GKOC_HIP(hipMemsetAsync(status, 0, 32, st));
-    symbolic_check_kernel<I><<<dim3(symb_grid(n, symb_block)), dim3(symb_block), 0, st>>>(
-        n, nnz, rp, keys, parent, post, inv_post, static_cast<const I*>(nullptr), 1, status);
+    status_words<5> status(st);
+    GKOC_TRY(status.init());
+    symbolic_check_kernel<I><<<dim3(stream_grid(n, symb_block)), dim3(symb_block), 0, st>>>(
+        n, nnz, rp, keys, parent, post, inv_post, static_cast<const I*>(nullptr), 1, status.dev);
     GKOC_LAUNCH_OK();
-    int host[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    GKOC_HIP(hipMemcpyAsync(host, status, 32, hipMemcpyDeviceToHost, st));
-    GKOC_HIP(hipStreamSynchronize(st));
-    GKOC_REQUIRE(host[0] == 0, GKOC_E_INVALID, "row pointers do not ascend from 0 to nnz, or a key outside [0, n)");
-    GKOC_REQUIRE(host[1] == 0, GKOC_E_INVALID, "parent[v] is neither -1 nor inside (v, n)");
-    GKOC_REQUIRE(host[2] == 0, GKOC_E_INVALID, "post is no permutation with the inverse inv_post");
-    GKOC_REQUIRE(host[4] == 0, GKOC_E_INVALID, "a row that does not end with the post rank of its diagonal");
-    *longest_lower = host[3] - 1;
+    GKOC_TRY(status.read());
+    GKOC_REQUIRE(status[0] == 0, GKOC_E_INVALID, "row pointers do not ascend from 0 to nnz, or a key outside [0, n)");
+    GKOC_REQUIRE(status[1] == 0, GKOC_E_INVALID, "parent[v] is neither -1 nor inside (v, n)");
+    GKOC_REQUIRE(status[2] == 0, GKOC_E_INVALID, "post is no permutation with the inverse inv_post");
+    GKOC_REQUIRE(status[4] == 0, GKOC_E_INVALID, "a row that does not end with the post rank of its diagonal");
+    *longest_lower = status[3] - 1;
     return GKOC_OK;
 }
 
@@ -250,16 +235,10 @@ int symbolic_rows(gkoc_stream_t s, int64_t n, int64_t nnz, const I* rp, const I*
     hipStream_t st = as_stream(s);
     int longest = 0;
     GKOC_TRY(symbolic_checked<I>(st, n, nnz, rp, keys, parent, post, inv_post, &longest));
-    if (longest <= symb_row_limits[0]) {
-        return symbolic_rows_launch<EXPAND, 16, T, I>(st, n, rp, keys, parent, post, first, inv_post, counts, offsets,
-                                                   total, entries);
-    }
-    if (longest <= symb_row_limits[1]) {
-        return symbolic_rows_launch<EXPAND, 32, T, I>(st, n, rp, keys, parent, post, first, inv_post, counts, offsets,
-                                                   total, entries);
-    }
-    return symbolic_rows_launch<EXPAND, 64, T, I>(st, n, rp, keys, parent, post, first, inv_post, counts, offsets,
-                                               total, entries);
+    return with_lanes(longest, symb_row_limits, [&](auto w) {
+        return symbolic_rows_launch<EXPAND, decltype(w)::value, T, I>(st, n, rp, keys, parent, post, first, inv_post,
+                                                                      counts, offsets, total, entries);
+    });
 }
 
 template <typename I>
@@ -306,27 +285,22 @@ int symbolic_post_keys(gkoc_stream_t s, int64_t n, int64_t nnz, const I* rp, con
     if (n == 0) return GKOC_OK;
     GKOC_REQUIRE(rp && post && inv_post && (nnz == 0 || (ci && keys)), GKOC_E_INVALID, "null pointer");
     hipStream_t st = as_stream(s);
-    // scratch: 8 status words, then post^-1 - the caller's inv_post is written only after the checks
-    void* raw = nullptr;
-    GKOC_TRY(scratch_malloc(st, &raw, 32 + sizeof(I) * size_t(n)));
-    scratch_guard guard{st, raw};
-    int* status = static_cast<int*>(raw);
-    I* filled = reinterpret_cast<I*>(static_cast<char*>(raw) + 32);
-    GKOC_HIP(hipMemsetAsync(status, 0, 32, st));
+    // scratch: the status words, then post^-1 - the caller's inv_post is written only after the checks
+    status_words<5> status(st);
+    GKOC_TRY(status.init(sizeof(I) * size_t(n)));
+    I* filled = status.template behind<I>();
     GKOC_HIP(hipMemsetAsync(filled, 0xff, sizeof(I) * size_t(n), st));
-    symbolic_scatter_kernel<I><<<dim3(symb_grid(n, symb_block)), dim3(symb_block), 0, st>>>(n, post, filled);
+    symbolic_scatter_kernel<I><<<dim3(stream_grid(n, symb_block)), dim3(symb_block), 0, st>>>(n, post, filled);
     GKOC_LAUNCH_OK();
-    symbolic_check_kernel<I><<<dim3(symb_grid(n, symb_block)), dim3(symb_block), 0, st>>>(
-        n, nnz, rp, ci, static_cast<const I*>(nullptr), post, static_cast<const I*>(nullptr), filled, 0, status);
+    symbolic_check_kernel<I><<<dim3(stream_grid(n, symb_block)), dim3(symb_block), 0, st>>>(
+        n, nnz, rp, ci, static_cast<const I*>(nullptr), post, static_cast<const I*>(nullptr), filled, 0, status.dev);
     GKOC_LAUNCH_OK();
-    int host[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    GKOC_HIP(hipMemcpyAsync(host, status, 32, hipMemcpyDeviceToHost, st));
-    GKOC_HIP(hipStreamSynchronize(st));
-    GKOC_REQUIRE(host[0] == 0, GKOC_E_INVALID, "row pointers do not ascend from 0 to nnz, or a column outside the matrix");
-    GKOC_REQUIRE(host[2] == 0, GKOC_E_INVALID, "post is no permutation of [0, n)");
+    GKOC_TRY(status.read());
+    GKOC_REQUIRE(status[0] == 0, GKOC_E_INVALID, "row pointers do not ascend from 0 to nnz, or a column outside the matrix");
+    GKOC_REQUIRE(status[2] == 0, GKOC_E_INVALID, "post is no permutation of [0, n)");
     GKOC_HIP(hipMemcpyAsync(inv_post, filled, sizeof(I) * size_t(n), hipMemcpyDeviceToDevice, st));
     if (nnz > 0) {
-        symbolic_keys_kernel<I><<<dim3(symb_grid(nnz, symb_block)), dim3(symb_block), 0, st>>>(nnz, ci, post, keys);
+        symbolic_keys_kernel<I><<<dim3(stream_grid(nnz, symb_block)), dim3(symb_block), 0, st>>>(nnz, ci, post, keys);
         GKOC_LAUNCH_OK();
     }
     return GKOC_OK;
@@ -414,11 +388,7 @@ using namespace gkoc;
 
 extern "C" int gkoc_symbolic_row_limits(int* limits_host, int* count_host)
 {
-    GKOC_REQUIRE(limits_host && count_host, GKOC_E_INVALID, "null pointer");
-    constexpr int count = int(sizeof(symb_row_limits) / sizeof(symb_row_limits[0]));
-    for (int p = 0; p < count; ++p) limits_host[p] = symb_row_limits[p];
-    *count_host = count;
-    return GKOC_OK;
+    return export_row_limits(symb_row_limits, limits_host, count_host);
 }
 
 #define GKOC_DEF_SYMBOLIC(I, A, IN)                                                                            \

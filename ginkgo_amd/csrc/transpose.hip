@@ -42,13 +42,6 @@ __global__ __launch_bounds__(256) void gather_transposed_kernel(
     }
 }
 
-inline unsigned grid_for(int64_t n)
-{
-    int64_t b = ceildiv(n > 0 ? n : 1, 256);
-    if (b > 4 * max_stream_blocks) b = 4 * max_stream_blocks;
-    return unsigned(b);
-}
-
 inline int bits_for(int64_t n_cols)
 {
     int bits = 1;
@@ -112,14 +105,14 @@ extern "C" size_t gkoc_csr_transpose_workspace_bytes(int64_t nnz, int64_t n_cols
         size_t scratch_bytes = sort_scratch_bytes<I>(nnz, n_cols);                          \
         int rc = gkoc_convert_ptrs_to_idxs_##IN(s, row_ptrs, n_rows, row_of);               \
         if (rc != GKOC_OK) return rc;                                                       \
-        iota_kernel<I><<<dim3(grid_for(nnz)), dim3(256), 0, st>>>(nnz, pos);                \
+        iota_kernel<I><<<dim3(stream_grid(nnz)), dim3(256), 0, st>>>(nnz, pos);             \
         GKOC_LAUNCH_OK();                                                                   \
         GKOC_HIP(rocprim::radix_sort_pairs(scratch, scratch_bytes, col_idxs, keys_sorted,   \
                                            pos, perm, size_t(nnz), 0, bits_for(n_cols),     \
                                            st));                                            \
         rc = gkoc_convert_idxs_to_ptrs_##IN(s, nnz, keys_sorted, n_cols, t_row_ptrs);       \
         if (rc != GKOC_OK) return rc;                                                       \
-        gather_transposed_kernel<T, I><<<dim3(grid_for(nnz)), dim3(256), 0, st>>>(          \
+        gather_transposed_kernel<T, I><<<dim3(stream_grid(nnz)), dim3(256), 0, st>>>(       \
             nnz, perm, row_of, vals, t_col_idxs, t_vals);                                   \
         GKOC_LAUNCH_OK();                                                                   \
         return GKOC_OK;                                                                     \

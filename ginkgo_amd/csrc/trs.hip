@@ -213,9 +213,8 @@ int trs_solve(gkoc_stream_t s, gkoc_trs_struct_t t, int unit_diag, int64_t n, in
     for (const auto& seg : t->schedule) {
         if (seg.rows == 0) continue;
         if (seg.wide) {
-            int64_t blocks = ceildiv(seg.rows * nrhs, trs_wide_block);
-            if (blocks > 4 * max_stream_blocks) blocks = 4 * max_stream_blocks;
-            trs_wide_kernel<UPPER, T, I><<<dim3(unsigned(blocks)), dim3(trs_wide_block), 0, st>>>(
+            trs_wide_kernel<UPPER, T, I>
+                <<<dim3(stream_grid(seg.rows * nrhs, trs_wide_block)), dim3(trs_wide_block), 0, st>>>(
                 seg.rows, nrhs, unit_diag, t->level_rows + seg.offset, row_ptrs, col_idxs, vals, b, ldb, x, ldx);
         } else {
             trs_narrow_kernel<UPPER, T, I><<<dim3(1), dim3(trs_narrow_block), 0, st>>>(
@@ -229,13 +228,6 @@ int trs_solve(gkoc_stream_t s, gkoc_trs_struct_t t, int unit_diag, int64_t n, in
 
 
 // ------------------------------------------------------------------ Sor set-up (one thread per row)
-inline unsigned sor_grid(int64_t n)
-{
-    int64_t b = ceildiv(n, 256);
-    if (b > 4 * max_stream_blocks) b = 4 * max_stream_blocks;
-    return unsigned(b < 1 ? 1 : b);
-}
-
 // counts of strictly-lower + 1 and strictly-upper + 1 entries per row; entry n_rows = 0 for the scan
 template <typename I>
 __global__ __launch_bounds__(256) void count_l_u_kernel(int64_t n, const I* __restrict__ rp,
@@ -309,7 +301,7 @@ int row_ptrs_l_u(gkoc_stream_t s, int64_t n, const I* rp, const I* ci, I* l_rp, 
     GKOC_REQUIRE(n >= 0, GKOC_E_INVALID, "negative number of rows");
     GKOC_REQUIRE(l_rp && (n == 0 || rp), GKOC_E_INVALID, "null pointer");
     hipStream_t st = as_stream(s);
-    count_l_u_kernel<I><<<dim3(sor_grid(n + 1)), dim3(256), 0, st>>>(n, rp, ci, l_rp, u_rp);
+    count_l_u_kernel<I><<<dim3(stream_grid(n + 1)), dim3(256), 0, st>>>(n, rp, ci, l_rp, u_rp);
     GKOC_LAUNCH_OK();
     GKOC_TRY(device_exclusive_scan<I>(st, l_rp, n + 1));
     if (u_rp) GKOC_TRY(device_exclusive_scan<I>(st, u_rp, n + 1));
@@ -325,7 +317,7 @@ int weighted_l_u(gkoc_stream_t s, int64_t n, const I* rp, const I* ci, const T* 
     if (n == 0) return GKOC_OK;
     GKOC_REQUIRE(rp && l_rp && l_ci && l_v, GKOC_E_INVALID, "null pointer");
     GKOC_REQUIRE(!WITH_U || (u_rp && u_ci && u_v), GKOC_E_INVALID, "null pointer");
-    weighted_l_u_kernel<WITH_U, T, I><<<dim3(sor_grid(n)), dim3(256), 0, as_stream(s)>>>(
+    weighted_l_u_kernel<WITH_U, T, I><<<dim3(stream_grid(n)), dim3(256), 0, as_stream(s)>>>(
         n, rp, ci, v, T(weight), l_rp, l_ci, l_v, u_rp, u_ci, u_v);
     GKOC_LAUNCH_OK();
     return GKOC_OK;

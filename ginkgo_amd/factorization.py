@@ -55,6 +55,7 @@ import math
 
 import torch
 
+from . import _lib
 from ._lib import IT, VT, DimensionMismatch, GkoError, NotSupported, call, lib
 from .executor import MEM_INDICES, MEM_VALUES
 from .isai import _lower_pattern
@@ -63,17 +64,13 @@ from .matrix import Csr, DeviceMatrixData, Fbcsr, _np_dtype, entry_dtype
 
 def row_limits():
     """the row lengths at which the factorization kernels change path (gkoc_factorization_row_limits)"""
-    limits, count = (C.c_int * 4)(), C.c_int(0)
-    call("gkoc_factorization_row_limits", limits, C.byref(count))
-    return [int(limits[p]) for p in range(count.value)]
+    return _lib.row_limits("gkoc_factorization_row_limits")
 
 
 def symbolic_row_limits():
     """the numbers of strictly-lower entries of a row at which the symbolic kernels change path
     (gkoc_symbolic_row_limits)"""
-    limits, count = (C.c_int * 4)(), C.c_int(0)
-    call("gkoc_symbolic_row_limits", limits, C.byref(count))
-    return [int(limits[p]) for p in range(count.value)]
+    return _lib.row_limits("gkoc_symbolic_row_limits")
 
 
 class _Factory:
@@ -448,15 +445,20 @@ class _Factorization:
                            "diagonal entry")
         return pattern.row_ptrs, pattern.col_idxs
 
-    def _on_pattern(self, rp, ci, src):
-        """a Csr on a copy of the pattern in the matrix' memory classes, with the values of `src` gathered"""
+    def _in_matrix_memory(self, rp, ci, values):
+        """a Csr on copies of the three arrays where a matrix' read-only arrays belong (the originals live with
+        the vectors)"""
         ex, idx = self.exec, ci.dtype
         m_rp, m_ci = ex.alloc((rp.numel(),), idx, MEM_INDICES), ex.alloc((ci.numel(),), idx, MEM_INDICES)
-        m_v = ex.alloc((ci.numel(),), src.dtype, MEM_VALUES)
+        m_v = ex.alloc((ci.numel(),), values.dtype, MEM_VALUES)
         m_rp.copy_(rp)
         m_ci.copy_(ci)
-        m_v.copy_(self._gather(rp, ci, src))
+        m_v.copy_(values)
         return Csr(ex, self.size, m_v, m_ci, m_rp)
+
+    def _on_pattern(self, rp, ci, src):
+        """a Csr on a copy of the pattern in the matrix' memory classes, with the values of `src` gathered"""
+        return self._in_matrix_memory(rp, ci, self._gather(rp, ci, src))
 
     def last_sweep_changes(self):
         """the number of entries whose bits the last sweep changed; 0: the factors are a fixed point of the
@@ -473,7 +475,32 @@ class _Factorization:
         return self.size
 
 
-class Ilu(_Factorization):
+class _LuFactors(_Factorization):
+    """the accessors of a factorization A ~ L U"""
+
+    def get_l_factor(self):
+        return self.l
+
+    def get_u_factor(self):
+        return self.u
+
+
+class _LltFactors(_Factorization):
+    """the accessors of a factorization A ~ L L^T, and the transpose it keeps unless the factory says no"""
+
+    def _keep_l(self, factory, l):
+        self.l = l
+        self.both_factors = factory.both_factors
+        self.lt = self.l.transpose() if self.both_factors else None
+
+    def get_l_factor(self):
+        return self.l
+
+    def get_lt_factor(self):
+        return self.lt
+
+
+class Ilu(_LuFactors):
     """A ~ L U on the pattern of A: L unit lower triangular, U upper triangular (exact ILU(0))."""
 
     @staticmethod
@@ -488,14 +515,8 @@ class Ilu(_Factorization):
         self.l, self.u = self._split(m, True)
         ex.synchronize()                # the factored copy is released on return
 
-    def get_l_factor(self):
-        return self.l
 
-    def get_u_factor(self):
-        return self.u
-
-
-class Ic(_Factorization):
+class Ic(_LltFactors):
     """A ~ L L^T on the pattern of A's lower triangle (exact IC(0))."""
 
     @staticmethod
@@ -506,20 +527,13 @@ class Ic(_Factorization):
         super().__init__(factory, a)
         ex = self.exec
         m = self._prepared(factory, a)
-        self.l = self._split(m, False)
-        self._factorize("gkoc_ic_factorize_", self.l)
-        self.both_factors = factory.both_factors
-        self.lt = self.l.transpose() if self.both_factors else None
+        l = self._split(m, False)
+        self._factorize("gkoc_ic_factorize_", l)
+        self._keep_l(factory, l)
         ex.synchronize()                # the prepared copy is released on return
 
-    def get_l_factor(self):
-        return self.l
 
-    def get_lt_factor(self):
-        return self.lt
-
-
-class ParIlu(_Factorization):
+class ParIlu(_LuFactors):
     """A ~ L U on the pattern of A by `iterations` fixed-point sweeps; the exact ILU(0) once the sweeps reach
     the number of levels of the lower solve, an approximation of it before."""
 
@@ -534,14 +548,8 @@ class ParIlu(_Factorization):
         self.l, self.u = self._split(self._sweeps("gkoc_par_ilu_sweeps_", factory, m), True)
         ex.synchronize()                # the prepared copy and the sweeps' buffers are released on return
 
-    def get_l_factor(self):
-        return self.l
 
-    def get_u_factor(self):
-        return self.u
-
-
-class ParIc(_Factorization):
+class ParIc(_LltFactors):
     """A ~ L L^T on the pattern of A's lower triangle by `iterations` fixed-point sweeps; the exact IC(0) once
     the sweeps reach the number of levels of the lower solve, an approximation of it before."""
 
@@ -553,19 +561,11 @@ class ParIc(_Factorization):
         super().__init__(factory, a)
         ex = self.exec
         m = self._prepared(factory, a)
-        self.l = self._sweeps("gkoc_par_ic_sweeps_", factory, self._split(m, False))
-        self.both_factors = factory.both_factors
-        self.lt = self.l.transpose() if self.both_factors else None
+        self._keep_l(factory, self._sweeps("gkoc_par_ic_sweeps_", factory, self._split(m, False)))
         ex.synchronize()                # the prepared copy and the sweeps' buffers are released on return
 
-    def get_l_factor(self):
-        return self.l
 
-    def get_lt_factor(self):
-        return self.lt
-
-
-class ParIlut(_Factorization):
+class ParIlut(_LuFactors):
     """A ~ L U on a pattern the factorization chooses by magnitude: `iterations` rounds of "add the pattern of
     L U, sweep, keep the fill_in_limit * nnz largest entries of either triangle, sweep" (steps 1-6 of
     include/gko_cdna4.h).  `keep` holds the two limits."""
@@ -581,14 +581,8 @@ class ParIlut(_Factorization):
         self.l, self.u = self._split(self._threshold_loop(factory, False, m, m, m), True)
         ex.synchronize()                # the prepared copy and the last iterate are released on return
 
-    def get_l_factor(self):
-        return self.l
 
-    def get_u_factor(self):
-        return self.u
-
-
-class ParIct(_Factorization):
+class ParIct(_LltFactors):
     """A ~ L L^T on a pattern the factorization chooses by magnitude: the loop of ParIlut on the lower
     triangle, with one limit."""
 
@@ -602,25 +596,11 @@ class ParIct(_Factorization):
         m = self._prepared(factory, a)
         last = self._threshold_loop(factory, True, m, self._split(m, False), self._split(m, False, diag_sqrt=True))
         # the iterate's arrays live with the vectors; the factor's go where a matrix' read-only arrays belong
-        nnz, idx = last.values.numel(), last.col_idxs.dtype
-        rp, ci = ex.alloc((self.size[0] + 1,), idx, MEM_INDICES), ex.alloc((nnz,), idx, MEM_INDICES)
-        v = ex.alloc((nnz,), last.dtype, MEM_VALUES)
-        rp.copy_(last.row_ptrs)
-        ci.copy_(last.col_idxs)
-        v.copy_(last.values)
-        self.l = Csr(ex, self.size, v, ci, rp)
-        self.both_factors = factory.both_factors
-        self.lt = self.l.transpose() if self.both_factors else None
+        self._keep_l(factory, self._in_matrix_memory(last.row_ptrs, last.col_idxs, last.values))
         ex.synchronize()                # the prepared copy and the last iterate are released on return
 
-    def get_l_factor(self):
-        return self.l
 
-    def get_lt_factor(self):
-        return self.lt
-
-
-class Cholesky(_Factorization):
+class Cholesky(_LltFactors):
     """A = L L^T exactly, up to rounding: the contract of Ic on the pattern of L that the symbolic phase computes
     (or that `with_symbolic_factorization` gives).  Reads the lower triangle of A."""
 
@@ -637,18 +617,11 @@ class Cholesky(_Factorization):
         else:
             rp, ci = _lower_pattern(ex, self.size, *self._given_pattern(factory.symbolic, factory.skip_sorting),
                                     self.dtype)
-        self.l = self._on_pattern(rp, ci, self._split(m, False))
-        self._factorize("gkoc_ic_factorize_", self.l)
-        self.both_factors = factory.both_factors
-        self.lt = self.l.transpose() if self.both_factors else None
+        l = self._on_pattern(rp, ci, self._split(m, False))
+        self._factorize("gkoc_ic_factorize_", l)
+        self._keep_l(factory, l)
         self._symbolic = None
         ex.synchronize()                # the prepared copy and the pattern's first copy are released on return
-
-    def get_l_factor(self):
-        return self.l
-
-    def get_lt_factor(self):
-        return self.lt
 
     def get_symbolic(self):
         """the pattern of L as a Csr of ones on the factor's own index arrays"""
@@ -658,7 +631,7 @@ class Cholesky(_Factorization):
         return self._symbolic
 
 
-class Lu(_Factorization):
+class Lu(_LuFactors):
     """A = L U exactly, up to rounding, without pivoting: the contract of Ilu on the combined pattern - row i of
     the symbolic Cholesky factor of the symmetrised pattern, then row i of its transpose - or on the pattern that
     `with_symbolic_factorization` gives.  L has a unit diagonal, stored last; U its diagonal first."""
@@ -684,12 +657,6 @@ class Lu(_Factorization):
         self._factorize("gkoc_ilu_factorize_", self.combined)
         self.l, self.u = self._split(self.combined, True)
         ex.synchronize()                # the prepared copy and the pattern's first copy are released on return
-
-    def get_l_factor(self):
-        return self.l
-
-    def get_u_factor(self):
-        return self.u
 
     def get_combined(self):
         """the factored matrix on the combined pattern: L strictly below the diagonal, U on and above it"""

@@ -32,6 +32,7 @@ import ctypes as C
 
 import torch
 
+from . import _lib
 from ._lib import IT, VT, DimensionMismatch, GkoError, NotSupported, call
 from .base import LinOp
 from .executor import MEM_INDICES, MEM_VALUES
@@ -40,9 +41,7 @@ from .matrix import Csr, Dense, DeviceMatrixData, Fbcsr
 
 def row_limits():
     """the pattern-row lengths at which the generate kernel changes path (gkoc_isai_row_limits)"""
-    limits, count = (C.c_int * 4)(), C.c_int(0)
-    call("gkoc_isai_row_limits", limits, C.byref(count))
-    return [int(limits[p]) for p in range(count.value)]
+    return _lib.row_limits("gkoc_isai_row_limits")
 
 
 class _IsaiFactory:
@@ -201,9 +200,7 @@ LowerIsai._OTHER, UpperIsai._OTHER = UpperIsai, LowerIsai
 def general_row_limits():
     """the pattern-row lengths at which the general / spd generate kernel changes path; the last one is the
     cap, the longest pattern row it takes (gkoc_isai_general_row_limits)"""
-    limits, count = (C.c_int * 4)(), C.c_int(0)
-    call("gkoc_isai_general_row_limits", limits, C.byref(count))
-    return [int(limits[p]) for p in range(count.value)]
+    return _lib.row_limits("gkoc_isai_general_row_limits")
 
 
 def _lower_pattern(ex, size, rp, ci, dtype):

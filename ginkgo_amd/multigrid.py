@@ -29,6 +29,7 @@ import ctypes as C
 
 import torch
 
+from . import _lib
 from ._lib import IT, VT, DimensionMismatch, GkoError, NotSupported, call
 from .base import LinOp
 from .executor import MEM_INDICES, MEM_VALUES
@@ -40,9 +41,7 @@ from . import stop as _stop
 
 def row_limits():
     """the row lengths of the weight matrix at which the selection kernel changes path (gkoc_pgm_row_limits)"""
-    limits, count = (C.c_int * 4)(), C.c_int(0)
-    call("gkoc_pgm_row_limits", limits, C.byref(count))
-    return [int(limits[p]) for p in range(count.value)]
+    return _lib.row_limits("gkoc_pgm_row_limits")
 
 
 class _PgmFactory:
