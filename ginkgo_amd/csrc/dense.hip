@@ -249,6 +249,16 @@ __global__ __launch_bounds__(red_block) void reduce_stage2(
     if (threadIdx.x == 0) result[col] = SQRT ? sqrt(r) : r;
 }
 
+// partials (= stage-1 blocks) per column of the strided column reductions: a block per 4 rows per thread, with
+// max_partials in all columns together, and never fewer than one per column
+inline int64_t strided_partials(int64_t rows, int64_t cols)
+{
+    int64_t nb = ceildiv(rows, int64_t(red_block) * 4);
+    const int64_t cap = max_partials / (cols < max_partials ? cols : max_partials);
+    if (nb > cap) nb = cap;
+    return nb < 1 ? 1 : nb;
+}
+
 template <typename T, int SQUARE, bool SQRT>
 int launch_reduce(gkoc_stream_t s, int64_t rows, int64_t cols, const T* x,
                   int64_t ldx, const T* y, int64_t ldy, T* result, void* work,
@@ -290,10 +300,7 @@ int launch_reduce(gkoc_stream_t s, int64_t rows, int64_t cols, const T* x,
             <<<dim3(unsigned(nb)), dim3(red_block), 0, as_stream(s)>>>(
                 rows, x, y, partial, vec_ok);
     } else {
-        int64_t nb = ceildiv(rows, int64_t(red_block) * 4);
-        const int64_t cap = max_partials / (cols < max_partials ? cols : max_partials);
-        if (nb > cap) nb = cap;
-        if (nb < 1) nb = 1;
+        const int64_t nb = strided_partials(rows, cols);
         n_partials = static_cast<int>(nb);
         reduce_cols_stage1<T, SQUARE>
             <<<dim3(unsigned(nb), unsigned(cols)), dim3(red_block), 0,
@@ -576,10 +583,7 @@ int launch_cnorm2(gkoc_stream_t s, int64_t rows, int64_t cols, const R* x, int64
     GKOC_REQUIRE(x && work_bytes >= gkoc_reduction_workspace_bytes(rows, cols, sizeof(R)), GKOC_E_WORKSPACE,
                  "reduction workspace too small");
     R* partial = static_cast<R*>(work);
-    int64_t nb = ceildiv(rows, int64_t(red_block) * 4);
-    const int64_t cap = max_partials / (cols < max_partials ? cols : max_partials);
-    if (nb > cap) nb = cap;
-    if (nb < 1) nb = 1;
+    const int64_t nb = strided_partials(rows, cols);
     cnorm2_stage1<R><<<dim3(unsigned(nb), unsigned(cols)), dim3(red_block), 0, as_stream(s)>>>(
         rows, x, 2 * ld_complex, partial);
     GKOC_LAUNCH_OK();

@@ -252,6 +252,30 @@ def test_squared_norm2(gexec, tn):
     assert raises_invalid("gkoc_cdense_compute_squared_norm2_" + tn, gexec.stream, -1, 2, dx, 5, out)
 
 
+# --------------------------------------------------------------------------------- dot, conj dot
+@pytest.mark.parametrize("rows,cols", [(0, 3), (2048, 1), (2049, 3), (524289, 1), (5, 0), (0, 0)])
+@pytest.mark.parametrize("conjugate_x", [0, 1])
+@pytest.mark.parametrize("tn", TN)
+def test_compute_dot_launcher_edges(gexec, tn, conjugate_x, rows, cols):
+    """x . y and conj(x) . y per column at the edges of the two-stage launcher: no rows (zeros), no columns
+    (nothing written), one block per column and its first split, one row past the cap of 256 blocks of 2048
+    rows.  Gaussian integers in [-3, 3]: both parts of every product are integers of modulus <= 18, every
+    partial sum stays below 524289 * 18 < 2^24, so the result is exact in every summation order"""
+    t = br.TYPES[tn]
+    rng = np.random.default_rng(rows + cols)
+    x, y = [(rng.integers(-3, 4, (rows, cols)) + 1j * rng.integers(-3, 4, (rows, cols))).astype(t) for _ in range(2)]
+    fx, fy = padded(x, cols + 2), padded(y, cols + 1)
+    dx, dy, out = Dev(gexec, fx), Dev(gexec, fy), _out(gexec, cols, t)
+    _call("gkoc_cdense_compute_dot_" + tn, gexec.stream, rows, cols, dx, cols + 2, dy, cols + 1, out, conjugate_x)
+    sync()
+    got = head_of(out, cols, cols, fill=np.nan)
+    assert same_bits(dx.get(), fx) and same_bits(dy.get(), fy)
+    wx, wy = x.astype(np.complex128), y.astype(np.complex128)
+    assert np.array_equal(got.astype(np.complex128), np.sum((np.conj(wx) if conjugate_x else wx) * wy, axis=0))
+    if rows == 0:
+        assert same_bits(got, np.zeros(cols, t))
+
+
 # ------------------------------------------------------------------------------------------ moduli
 def _within_ulps(got, ref, k):
     """|got - ref| <= k ulp of the type at ref (subnormal results: k times the smallest subnormal)"""

@@ -205,6 +205,39 @@ def test_norm1_mean_exact_on_small_integers(gexec, tn, rows, cols):
 
 
 @pytest.mark.parametrize("tn", TN)
+@pytest.mark.parametrize("rows,cols", [(0, 3), (2048, 1), (2049, 3), (524289, 1), (5, 0), (0, 0)])
+def test_norm1_mean_launcher_edges(gexec, tn, rows, cols):
+    """the two-stage column reductions at the edges of their launcher: no rows (zeros, and a mean of zero,
+    not 0 / 0), no columns (nothing written), one block per column and its first split (2048 | 2049 rows),
+    and one row past the cap of 256 blocks of 2048 rows.  The data of
+    test_norm1_mean_exact_on_small_integers: |entries| <= 4, so column sums stay below 524289 * 4 < 2^24
+    and are exact in every summation order"""
+    t = br.TYPES[tn]
+    rt = br.real_of(t)
+    rng = np.random.default_rng(rows + cols)
+    re = rng.integers(-4, 5, (rows, cols)).astype(np.float64)
+    x = re.astype(t)
+    if br.is_complex(t):
+        x = np.where(rng.integers(0, 2, (rows, cols)).astype(bool), 1j * re, re).astype(t)
+    wide = x.astype(np.clongdouble if br.is_complex(t) else np.longdouble)
+    total = np.sum(wide, axis=0)
+    for ld in (cols, cols + 1):
+        got = _norm1_mean(gexec, tn, x, ld)        # (asserts the canary after the last column)
+        assert all(g.shape == (cols,) for g in got)
+        assert np.array_equal(got[0].astype(np.longdouble), np.sum(np.abs(wide), axis=0))
+        if br.is_complex(t):
+            assert np.array_equal(got[2].astype(wide.dtype), total)
+        if rows == 0:
+            assert all(same_bits(g, np.zeros(cols, g.dtype)) for g in got)
+            assert not np.any(np.isnan(got[1]))
+        elif br.is_complex(t):
+            assert np.array_equal(got[1].real, total.real.astype(rt) / rt(rows))
+            assert np.array_equal(got[1].imag, total.imag.astype(rt) / rt(rows))
+        else:
+            assert np.array_equal(got[1], total.astype(rt) / rt(rows))
+
+
+@pytest.mark.parametrize("tn", TN)
 @pytest.mark.parametrize("rows,cols", [(1, 1), (63, 3), (65, 1), (1025, 3), (100003, 3), (100003, 1)])
 def test_norm1_mean_random(gexec, tn, rows, cols):
     """the header's contract for the tree reductions: |err| <= 450 eps sum|terms|"""

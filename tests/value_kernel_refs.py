@@ -10,8 +10,8 @@ real operation rounded on its own (complex products as (ac - bd, ad + bc)) is wh
 bit for bit and what sizes rule R.  Copies, gathers and integer kernels have one restatement; their independent
 formulations live in tests/test_value_kernel_refs_cpu.py.  Nothing here touches a GPU.
 
-The quotient.  complex_blas.hip divides by Smith's scaled quotient, operation for operation the one of
-csrc/complex_type.hpp (`smith`).  `unscaled_quotient` is the conjugate form a (conj b) / |b|^2 that the file
+The quotient.  complex_blas.hip divides by Smith's scaled quotient, the operator/ of csrc/complex_type.hpp
+(`smith`).  `unscaled_quotient` is the conjugate form a (conj b) / |b|^2 that the file
 used before: kept here only so that the CPU test can show that the sweep of `quotient_sweep` rejects it.
 
 Layouts.  Ell: entry k of row r at r + k * stride, padding value 0 / column -1.  Sellp: slice sl holds the rows
