@@ -2,8 +2,10 @@
 Python mirror against the oracle (oracle/gko_oracle_mixed.inc, pinned by the live reference built with
 GINKGO_MIXED_PRECISION: tests/test_mixed_cpu.py) and against tests/golden/mixed_spmv.npz.
 Bar: BIT-EXACT for the real triples (the kernels keep the reference's order: widen, multiply, add in
-k order, narrow once).  The complex triples are checked against the live reference in
-tests/dropin/mixed_test.cpp (tests/test_dropin_gpu.py::test_mixed_precision_core_flavor)."""
+k order, narrow once).  The complex triples, the edge shapes of the two plain kernels, the guards and the gather
+between complex precisions are in tests/test_mixed_triples_gpu.py (against tests/mixed_refs.py, through the C ABI);
+where the Ginkgo tree is present, tests/dropin/mixed_test.cpp checks the complex triples against the live reference
+as well (tests/test_dropin_gpu.py::test_mixed_precision_core_flavor)."""
 import ctypes as C
 import os
 import sys
