@@ -22,12 +22,15 @@
 // one pass applies all iter+1 updates and produces the partials of the new 2-norm and inf-norm
 // from the registers that hold the result.  Reductions: fixed two-level tree (deterministic).
 // With one right-hand side every lane works on four consecutive rows (one 32/16/8-byte load per
-// basis vector); several right-hand sides take the strided path.
+// basis vector); several right-hand sides take the strided path.  The Givens update of the new
+// Hessenberg column and the back substitution are gmres_hessenberg.hpp's, shared with gmres.hip
+// and cb_gmres_complex.hip.
 #include <cmath>
 #include <limits>
 #include <type_traits>
 
 #include "common.hpp"
+#include "gmres_hessenberg.hpp"
 
 namespace gkoc {
 namespace {
@@ -415,8 +418,8 @@ __global__ __launch_bounds__(256) void cb_finish_kernel(
 }
 
 // givens_rotation + calculate_sin_and_cos + calculate_next_residual_norm
-// (reference/solver/cb_gmres_kernels.cpp:151-231), one thread per column, the reference's
-// operation order
+// (reference/solver/cb_gmres_kernels.cpp:151-231), one thread per column: gmres_hessenberg.hpp.
+// The norm of a zero residual is +0.0, the reference's abs (not the -0.0 that tabs would keep).
 template <typename T>
 __global__ __launch_bounds__(256) void cb_givens_kernel(
     int64_t cols, int64_t iter, T* __restrict__ gsin, int64_t lds_, T* __restrict__ gcos,
@@ -425,35 +428,7 @@ __global__ __launch_bounds__(256) void cb_givens_kernel(
 {
     const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
     if (i >= cols || status_has_stopped(stop[i])) return;
-    for (int64_t j = 0; j < iter; ++j) {
-        const T c = gcos[j * ldc + i], s = gsin[j * lds_ + i];
-        const T hj = h[j * ldh + i], hj1 = h[(j + 1) * ldh + i];
-        const T temp = c * hj + s * hj1;
-        h[(j + 1) * ldh + i] = -s * hj + c * hj1;
-        h[j * ldh + i] = temp;
-    }
-    const T this_h = h[iter * ldh + i];
-    const T next_h = h[(iter + 1) * ldh + i];
-    T c, s;
-    if (this_h == T(0)) {
-        c = T(0);
-        s = T(1);
-    } else {
-        const T scale = tabs(this_h) + tabs(next_h);
-        const T hyp = scale * sqrt(tabs(this_h / scale) * tabs(this_h / scale) +
-                                   tabs(next_h / scale) * tabs(next_h / scale));
-        c = this_h / hyp;
-        s = next_h / hyp;
-    }
-    gcos[iter * ldc + i] = c;
-    gsin[iter * lds_ + i] = s;
-    h[iter * ldh + i] = c * this_h + s * next_h;
-    h[(iter + 1) * ldh + i] = T(0);
-    const T r = rnc[iter * ldr + i];
-    const T rn = -s * r;
-    rnc[(iter + 1) * ldr + i] = rn;
-    rnc[iter * ldr + i] = c * r;
-    residual_norm[i] = tabs(rn);
+    hessenberg_column_step<T>(i, iter, gsin, lds_, gcos, ldc, h, ldh, rnc, ldr, residual_norm);
 }
 
 // ---- restart ------------------------------------------------------------------------------
@@ -580,12 +555,7 @@ __global__ __launch_bounds__(256) void cb_solve_upper_kernel(int64_t cols, const
 {
     const int64_t k = int64_t(blockIdx.x) * 256 + threadIdx.x;
     if (k >= cols) return;
-    const int64_t m = int64_t(fin[k]);
-    for (int64_t i = m - 1; i >= 0; --i) {
-        T temp = rnc[i * ldr + k];
-        for (int64_t j = i + 1; j < m; ++j) temp -= h[i * ldh + j * cols + k] * y[j * ldy + k];
-        y[i * ldy + k] = temp / h[i * ldh + i * cols + k];
-    }
+    upper_solve_column<T, hessenberg_layout::matrix>(k, cols, int64_t(fin[k]), rnc, ldr, h, ldh, y, ldy);
 }
 
 // before_preconditioner(r, c) = sum_{j < final_iter_nums[c]} basis_j(r, c) * y(j, c), in j order
@@ -662,6 +632,7 @@ int cb_restart_impl(hipStream_t st, const cb_args& a, const T* residual, int64_t
     const int64_t nb = ceildiv(a.rows > 0 ? a.rows : 1, cb_chunk);
     T* work = nullptr;
     GKOC_TRY(scratch_malloc(st, reinterpret_cast<void**>(&work), size_t(2 * nb * a.nrhs) * sizeof(T)));
+    scratch_guard guard{st, work};
     T* pnrm = work;
     T* pmax = work + nb * a.nrhs;
     const dim3 grid(unsigned(nb), unsigned(a.nrhs));
@@ -695,7 +666,7 @@ int cb_restart_impl(hipStream_t st, const cb_args& a, const T* residual, int64_t
         }
     }
     GKOC_LAUNCH_OK();
-    return scratch_free(st, work);
+    return GKOC_OK;
 }
 
 template <typename T, int KIND>
@@ -718,6 +689,7 @@ int cb_arnoldi_impl(hipStream_t st, const cb_args& a, T* next, int64_t ldn, T* g
     const size_t ctrl_off = (flag_off + size_t(a.nrhs) + 15) / 16 * 16;
     char* work = nullptr;
     GKOC_TRY(scratch_malloc(st, reinterpret_cast<void**>(&work), ctrl_off + sizeof(cb_ctrl)));
+    scratch_guard guard{st, work};
     T* pdot = reinterpret_cast<T*>(work);
     T* pnrm = pdot + n_pdot;
     T* pmax = pnrm + n_p;
@@ -774,7 +746,7 @@ int cb_arnoldi_impl(hipStream_t st, const cb_args& a, T* next, int64_t ldn, T* g
     cb_givens_kernel<T><<<unsigned(ceildiv(a.nrhs, 256)), 256, 0, st>>>(
         a.nrhs, iter, gsin, ld_sin, gcos, ld_cos, residual_norm, rnc, ld_rnc, h, ldh, stop);
     GKOC_LAUNCH_OK();
-    return scratch_free(st, work);
+    return GKOC_OK;
 }
 
 template <typename T, int KIND>

@@ -16,10 +16,13 @@
 // are always enqueued and leave at once where no column asks for them.  Reductions: per block a fixed
 // tree, the blocks' partials folded in block order (deterministic).  Not tuned beyond that: one row per
 // thread and step (the real kernels' four-row vector loads and fused second pass are not repeated here).
+// The Givens update of the new Hessenberg column and the back substitution are gmres_hessenberg.hpp's,
+// shared with gmres.hip and cb_gmres.hip.
 #include <cmath>
 
 #include "common.hpp"
 #include "complex_type.hpp"
+#include "gmres_hessenberg.hpp"
 
 namespace gkoc {
 namespace {
@@ -273,36 +276,9 @@ __global__ void cx_givens(int64_t cols, int64_t iter, T* __restrict__ gsin, int6
                           int64_t ldc, T* __restrict__ h, int64_t ldh, real_t<T>* __restrict__ residual_norm,
                           T* __restrict__ rnc, int64_t ld_rnc, const uint8_t* __restrict__ stop)
 {
-    using R = real_t<T>;
     const int64_t c = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (c >= cols || status_has_stopped(stop[c])) return;
-    for (int64_t j = 0; j < iter; ++j) {
-        const T hj = h[j * ldh + c], hj1 = h[(j + 1) * ldh + c];
-        const T cs = gcos[j * ldc + c], sn = gsin[j * lds_ + c];
-        h[j * ldh + c] = cs * hj + sn * hj1;
-        h[(j + 1) * ldh + c] = -conj_v(sn) * hj + conj_v(cs) * hj1;
-    }
-    const T this_h = h[iter * ldh + c], next_h = h[(iter + 1) * ldh + c];
-    T cs, sn;
-    if (this_h.re == R(0) && this_h.im == R(0)) {
-        cs = T(R(0), R(0));
-        sn = T(R(1), R(0));
-    } else {
-        const R scale = abs_v(this_h) + abs_v(next_h);
-        const R a = abs_v(this_h / scale), b = abs_v(next_h / scale);
-        const R hyp = scale * ::sqrt(a * a + b * b);
-        cs = conj_v(this_h) / hyp;
-        sn = conj_v(next_h) / hyp;
-    }
-    gcos[iter * ldc + c] = cs;
-    gsin[iter * lds_ + c] = sn;
-    h[iter * ldh + c] = cs * this_h + sn * next_h;
-    h[(iter + 1) * ldh + c] = T(R(0), R(0));
-    const T rn = rnc[iter * ld_rnc + c];
-    const T nxt = -conj_v(sn) * rn;
-    rnc[(iter + 1) * ld_rnc + c] = nxt;
-    rnc[iter * ld_rnc + c] = cs * rn;
-    residual_norm[c] = abs_v(nxt);
+    hessenberg_column_step<T>(c, iter, gsin, lds_, gcos, ldc, h, ldh, rnc, ld_rnc, residual_norm);
 }
 
 // ---- solve_krylov ---------------------------------------------------------------------------------
@@ -312,12 +288,7 @@ __global__ void cx_solve_upper(int64_t cols, const T* __restrict__ rnc, int64_t 
 {
     const int64_t k = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (k >= cols) return;
-    const int64_t n = int64_t(fin[k]);
-    for (int64_t i = n - 1; i >= 0; --i) {
-        T t = rnc[i * ld_rnc + k];
-        for (int64_t j = i + 1; j < n; ++j) t = t - hess[i * ldh + j * cols + k] * y[j * ldy + k];
-        y[i * ldy + k] = t / hess[i * ldh + i * cols + k];
-    }
+    upper_solve_column<T, hessenberg_layout::matrix>(k, cols, int64_t(fin[k]), rnc, ld_rnc, hess, ldh, y, ldy);
 }
 
 template <typename T, typename S>
@@ -335,28 +306,6 @@ __global__ __launch_bounds__(CXB) void cx_qy(int64_t rows, int64_t cols, const S
     out[r * ldo + c] = acc;
 }
 
-// per-stream scratch of the arnoldi passes (partials, coefficients, flags, control block)
-struct cx_scratch {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
-thread_local cx_scratch t_scratch;
-
-int scratch(size_t bytes, void** out)
-{
-    if (t_scratch.bytes < bytes) {
-        if (t_scratch.p) (void)gkoc_free(t_scratch.p);
-        t_scratch.p = nullptr;
-        t_scratch.bytes = 0;
-        void* q = nullptr;
-        GKOC_TRY(gkoc_malloc(&q, bytes));
-        t_scratch.p = q;
-        t_scratch.bytes = bytes;
-    }
-    *out = t_scratch.p;
-    return GKOC_OK;
-}
-
 template <typename T, typename S>
 int restart_impl(gkoc_stream_t s, int64_t rows, int64_t cols, int64_t krylov_dim, const T* residual, int64_t ldr,
                  real_t<T>* residual_norm, T* rnc, int64_t ld_rnc, S* bases, int64_t st0, int64_t st1, T* next,
@@ -364,10 +313,11 @@ int restart_impl(gkoc_stream_t s, int64_t rows, int64_t cols, int64_t krylov_dim
 {
     using R = real_t<T>;
     const int64_t nb = ceildiv(rows, int64_t(CX_ROWS));
-    void* w = nullptr;
-    GKOC_TRY(scratch(size_t(nb) * size_t(cols) * sizeof(R) + 256, &w));
-    R* part = static_cast<R*>(w);
     hipStream_t st = as_stream(s);
+    void* w = nullptr;
+    GKOC_TRY(scratch_malloc(st, &w, size_t(nb) * size_t(cols) * sizeof(R) + 256));
+    scratch_guard guard{st, w};
+    R* part = static_cast<R*>(w);
     cx_sqnorm_partial<T><<<dim3(unsigned(nb), unsigned(cols)), dim3(CXB), 0, st>>>(rows, residual, ldr, part);
     GKOC_LAUNCH_OK();
     cx_restart_fold<T><<<dim3(unsigned(cols)), dim3(CXB), 0, st>>>(nb, krylov_dim, part, residual_norm, rnc, ld_rnc, fin);
@@ -391,15 +341,16 @@ int arnoldi_impl(gkoc_stream_t s, int64_t rows, int64_t cols, int64_t iter, T* n
     const size_t b_pnrm = size_t(cols) * size_t(nb) * sizeof(R);
     const size_t b_coef = size_t(num_k) * size_t(cols) * sizeof(T);
     auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    hipStream_t st = as_stream(s);
     void* w = nullptr;
-    GKOC_TRY(scratch(up(b_pdot) + up(b_pnrm) + up(b_coef) + up(size_t(cols)) + 256, &w));
+    GKOC_TRY(scratch_malloc(st, &w, up(b_pdot) + up(b_pnrm) + up(b_coef) + up(size_t(cols)) + 256));
+    scratch_guard guard{st, w};
     char* base = static_cast<char*>(w);
     T* pdot = reinterpret_cast<T*>(base);
     R* pnrm = reinterpret_cast<R*>(base + up(b_pdot));
     T* coef = reinterpret_cast<T*>(base + up(b_pdot) + up(b_pnrm));
     uint8_t* active = reinterpret_cast<uint8_t*>(base + up(b_pdot) + up(b_pnrm) + up(b_coef));
     cx_ctrl* ctrl = reinterpret_cast<cx_ctrl*>(base + up(b_pdot) + up(b_pnrm) + up(b_coef) + up(size_t(cols)));
-    hipStream_t st = as_stream(s);
     GKOC_HIP(hipMemsetAsync(ctrl, 0, sizeof(cx_ctrl), st));
     const dim3 grid_rc{static_cast<unsigned>(nb), static_cast<unsigned>(cols), 1u};
     const dim3 blk{unsigned(CXB), 1u, 1u};

@@ -215,6 +215,15 @@ __device__ __forceinline__ bool status_has_stopped(uint8_t s)
 {
     return (s & 0x3f) != 0;
 }
+__device__ __forceinline__ bool status_is_finalized(uint8_t s)
+{
+    return (s & 0x40) != 0;
+}
+// stopping_status::finalize(): a stopped column becomes finalized, any other flag stays
+__device__ __forceinline__ uint8_t status_finalized(uint8_t s)
+{
+    return status_has_stopped(s) ? uint8_t(s | 0x40) : s;
+}
 
 #endif  // __HIPCC__
 

@@ -18,12 +18,14 @@
 //    vectors in j order (bit-identical to the reference).
 //  * restart / initialize: element-wise.  hessenberg_qr / solve_krylov: one
 //    thread per right-hand side, same operation order as the reference
-//    (bit-identical: IEEE divide and sqrt, no FMA contraction).
+//    (bit-identical: IEEE divide and sqrt, no FMA contraction); the arithmetic
+//    is gmres_hessenberg.hpp's, shared with the two CB-GMRES files.
 #include <cmath>
 
 #include "common.hpp"
 #include "elementwise.hpp"
 #include "fused.hpp"
+#include "gmres_hessenberg.hpp"
 
 namespace gkoc {
 namespace {
@@ -86,7 +88,7 @@ __global__ __launch_bounds__(256) void gmres_multi_axpy_kernel(
          idx += stride) {
         const int64_t i = cols == 1 ? idx : idx / cols;
         const int64_t k = cols == 1 ? 0 : idx - i * cols;
-        if (stop[k] & 0x40) continue;  // is_finalized
+        if (status_is_finalized(stop[k])) continue;
         const int64_t nj = int64_t(final_iter_nums[k]);
         T acc = T(0);
         int64_t j = 0;
@@ -198,15 +200,12 @@ __global__ __launch_bounds__(256) void gmres_mgs_step_kernel(
     if (threadIdx.x == 0) partial[blockIdx.x] = r;
 }
 
-// stop_status[k].finalize() for stopped, not yet finalized columns (runs after
-// the axpy kernel, which must still see the old flags)
+// stop_status[k].finalize() (runs after the axpy kernel, which must still see
+// the old flags)
 __global__ void gmres_finalize_kernel(int64_t cols, uint8_t* stop)
 {
     const int64_t k = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (k < cols) {
-        const uint8_t s = stop[k];
-        if (!(s & 0x40) && (s & 0x3f)) stop[k] = s | uint8_t(0x40);
-    }
+    if (k < cols) stop[k] = status_finalized(stop[k]);
 }
 
 // stage 1 of multi_dot for one rhs column: block = 1024-row chunk, loops the
@@ -265,43 +264,12 @@ __global__ __launch_bounds__(256) void gmres_hessenberg_qr_kernel(
     int64_t ldr, T* __restrict__ h, int64_t ldh, int64_t iter,
     uint64_t* __restrict__ final_iter_nums, const uint8_t* __restrict__ stop)
 {
-    using R = real_t<T>;
     const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
     if (i >= cols) return;
-    if (stop[i] & 0x3f) return;
+    if (status_has_stopped(stop[i])) return;
     final_iter_nums[i]++;
-    // givens_rotation (common_gmres_kernels.cpp:52-90; conj_v is the identity for real T)
-    for (int64_t j = 0; j < iter; ++j) {
-        const T c = gcos[j * ldc + i], s = gsin[j * lds_ + i];
-        const T hj = h[j * ldh + i], hj1 = h[(j + 1) * ldh + i];
-        const T temp = c * hj + s * hj1;
-        h[(j + 1) * ldh + i] = -conj_v(s) * hj + conj_v(c) * hj1;
-        h[j * ldh + i] = temp;
-    }
-    // calculate_sin_and_cos (:29-48)
-    const T this_h = h[iter * ldh + i];
-    const T next_h = h[(iter + 1) * ldh + i];
-    T c, s;
-    if (this_h == T(0)) {
-        c = T(0);
-        s = T(1);
-    } else {
-        const R scale = abs_v(this_h) + abs_v(next_h);
-        const R hyp = scale * sqrt(abs_v(this_h / scale) * abs_v(this_h / scale) +
-                                   abs_v(next_h / scale) * abs_v(next_h / scale));
-        c = conj_v(this_h) / hyp;
-        s = conj_v(next_h) / hyp;
-    }
-    gcos[iter * ldc + i] = c;
-    gsin[iter * lds_ + i] = s;
-    h[iter * ldh + i] = c * this_h + s * next_h;
-    h[(iter + 1) * ldh + i] = T(0);
-    // calculate_next_residual_norm (:93-113)
-    const T r = rnc[iter * ldr + i];
-    const T rn = -conj_v(s) * r;
-    rnc[(iter + 1) * ldr + i] = rn;
-    rnc[iter * ldr + i] = c * r;
-    residual_norm[i] = abs_v(rn);
+    hessenberg_column_step<T>(i, iter, gsin, lds_, gcos, ldc, h, ldh, rnc, ldr,
+                              residual_norm);
 }
 
 template <typename T>
@@ -313,15 +281,10 @@ __global__ __launch_bounds__(256) void gmres_solve_krylov_kernel(
 {
     const int64_t k = int64_t(blockIdx.x) * 256 + threadIdx.x;
     if (k >= cols) return;
-    if (stop[k] & 0x40) return;  // is_finalized
+    if (status_is_finalized(stop[k])) return;
     const int64_t m = int64_t(final_iter_nums[k]);
-    for (int64_t i = m - 1; i >= 0; --i) {
-        T temp = rnc[i * ldr + k];
-        for (int64_t j = i + 1; j < m; ++j) {
-            temp -= h[j * ldh + i * cols + k] * y[j * ldy + k];
-        }
-        y[i * ldy + k] = temp / h[i * ldh + i * cols + k];
-    }
+    upper_solve_column<T, hessenberg_layout::row_per_step>(k, cols, m, rnc, ldr,
+                                                           h, ldh, y, ldy);
 }
 
 }  // namespace

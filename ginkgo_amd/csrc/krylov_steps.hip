@@ -190,7 +190,7 @@ struct op_bicgstab_finalize {
 __global__ void finalize_status_kernel(int64_t cols, uint8_t* stop)
 {
     const int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (j < cols && status_has_stopped(stop[j])) stop[j] |= uint8_t(0x40);
+    if (j < cols) stop[j] = status_finalized(stop[j]);
 }
 
 // --------------------------------------------------------------------- cgs

@@ -70,7 +70,7 @@ class State:
         self.t = br.TYPES[tn]
         self.rt = br.real_of(self.t)
         self.cx = br.is_complex(self.t)
-        self.nrhs, self.st1, self.ldn, aligned = LAYOUTS[layout]
+        self.nrhs, self.st1, self.ldn, aligned = LAYOUTS[layout] if isinstance(layout, str) else layout
         self.st0 = rows * self.st1
         if aligned:
             self.st0 = (self.st0 + 3) // 4 * 4 + 8
@@ -137,8 +137,10 @@ class State:
                   self.st1, d["scalars"], self.lds, d["next"], self.ldn, d["fin"])
         sync()
 
-    def arnoldi(self, it):
-        d, st = self.dev, self.gexec.stream
+    def arnoldi(self, it, stream=None, **operands):
+        """operands: device arrays that stand in for those of self.dev in this call; with a stream the step
+        is only enqueued there"""
+        d, st = {**self.dev, **operands}, self.gexec.stream if stream is None else stream
         buf = d["buffer"] if self.with_buffer else None
         head = (st, self.rows, self.nrhs, it, d["next"], self.ldn, d["gsin"], self.lds, d["gcos"], self.lds,
                 d["residual_norm"], d["rnc"], self.lds, self.kind, self.bases, self.st0, self.st1)
@@ -147,7 +149,8 @@ class State:
             _call("gkoc_cb_gmres_arnoldi_" + self.tn, *head, *tail)
         else:
             _call("gkoc_cb_gmres_arnoldi_" + self.tn, *head, d["scalars"], self.lds, *tail)
-        sync()
+        if stream is None:
+            sync()
 
     def solve(self, hess, ld_h, y, out):
         d, st = self.dev, self.gexec.stream
@@ -479,6 +482,126 @@ def test_arnoldi_leaves_a_stopped_column_alone(gexec, pair):
     for col in (0, 2):
         ok, ratio = br.rule_r(st.get("next")[:, col], n_hp[:, col], n_pl[:, col], t)
         assert ok, ratio
+
+
+@pytest.mark.parametrize("pair", [("f64", br.KEEP), ("f32", br.KEEP), ("c128", br.KEEP)], ids=_ids)
+def test_arnoldi_norm_of_a_zero_column_is_plus_zero(gexec, pair):
+    """The middle one of three columns has next_krylov = 0 and residual_norm_collection(0) = 0: its Hessenberg
+    entries are zero, the rotation is (cos, sin) = (0, 1) and the next residual norm is -conj(1) * 0, a
+    negative zero for the real types.  residual_norm is its abs, as in the reference: +0.0.  The other two
+    columns are ordinary and held against the references like test_arnoldi's."""
+    tn, kind = pair
+    t = br.TYPES[tn]
+    rows, kd = 5, 1
+    st = State(gexec, tn, kind, rows, kd, "three")
+    rng = np.random.default_rng(11)
+    st.put("residual", _rand(rng, (rows, 3), t))
+    st.restart()
+    st.put("gsin", np.zeros((kd, 3), t)), st.put("gcos", np.zeros((kd, 3), t))
+    rnc = st.get("rnc")
+    rnc[0, 1] = 0
+    st.put("rnc", rnc)
+    hp, pl = st.ref_state(br.hp(t)), st.ref_state(br.plain(t))
+    bases, scal = _sync_refs(st, (hp, pl))
+    w = np.stack([_operator(_decompress(st, bases, scal, 0, c, t)) for c in range(3)], axis=1).astype(t)
+    w[:, 1] = 0
+    st.put("next", w)
+    st.arnoldi(0)
+    with np.errstate(all="ignore"):         # the references divide the zero column by its norm as well
+        n_hp, n_pl = hp.arnoldi(0, w), pl.arnoldi(0, w)
+    rn, h, rnc = st.get("residual_norm"), st.get("h")[:2], st.get("rnc")
+    assert np.all(h[:, 1] == 0) and rnc[1, 1] == 0
+    assert rn[1] == 0 and not np.signbit(rn[1])
+    gs, gc = st.get("gsin"), st.get("gcos")
+    assert gc[0, 1] == 0 and gs[0, 1] == 1
+    cols = [0, 2]
+    for name, got, ref, plain_v in (
+            ("next", st.get("next"), n_hp, n_pl), ("hessenberg", h, hp.hess[0], pl.hess[0]),
+            ("rnc", rnc, hp.rnc, pl.rnc), ("residual_norm", rn[None], hp.residual_norm[None], pl.residual_norm[None]),
+            ("givens", np.stack([gs[0], gc[0]]), np.stack([hp.gsin[0], hp.gcos[0]]),
+             np.stack([pl.gsin[0], pl.gcos[0]]))):
+        ok, ratio = br.rule_r(got[:, cols], ref[:, cols], plain_v[:, cols], t)
+        assert ok, (name, ratio)
+    if not st.cx:
+        assert same_bits(rn[cols], np.abs(rnc[1, cols]))
+
+
+# ------------------------------------------------------------------- a step's scratch is its own
+def _walsh(k, rows):
+    """row k of the Sylvester-Hadamard matrix of order 1024 on rows 1 .. 1024, zero elsewhere: entries +-1,
+    different k orthogonal, squared norm 1024 - and the rows straddle the two row blocks of 1024"""
+    r, par = np.arange(1024), np.zeros(1024, np.int64)
+    for b in range(10):
+        par ^= ((r & k) >> b) & 1
+    v = np.zeros(rows)
+    v[1:1025] = 1 - 2 * par
+    return v
+
+
+def _exact_steps(gexec, tn, seed, first):
+    """Operands of the Arnoldi steps first .. first + 3 of a two-column problem in which every sum is exact
+    (integers over 32, far below 2^24): basis vector k of column c is a Walsh vector over 32 (norm one), the
+    next_krylov of step it the vectors 0 .. it with Gaussian-integer coefficients of parts in [-3, 3] plus a
+    multiple of vector it + 1, which is what the step leaves: times 4 in column 0, times 1 in column 1 (the
+    norm drops enough for a re-orthogonalisation round), times a unit that changes with the step.  Every step
+    has its own next_krylov, Hessenberg column and residual_norm.  Returns (state, operands per step)."""
+    t = br.TYPES[tn]
+    rows, kd = 1025, 5
+    st = State(gexec, tn, br.KEEP, rows, kd, (2, 2, 2, False))
+    rng = np.random.default_rng(seed)
+    walsh = np.stack([np.stack([_walsh(1 + 32 * seed + 8 * c + k, rows) for c in range(2)], axis=1)
+                      for k in range(kd + 1)])
+    st.put_bases((walsh / 32).astype(st.sdt))
+    rot = np.zeros((kd, 2), t)
+    st.put("gsin", rot)
+    rot[:first] = 1                                       # the steps before `first`: identity rotations
+    st.put("gcos", rot)
+    st.put("rnc", rng.integers(1, 9, (kd + 1, 2)).astype(t))
+    st.put("fin", np.full(2, first, np.uint64))
+    ops = []
+    for it in range(first, first + 4):
+        a = rng.integers(-3, 4, (it + 1, 2)) + 1j * rng.integers(-3, 4, (it + 1, 2))
+        lead = np.array([4, 1]) * (1, 1j, -1, -1j)[it % 4]
+        w = np.einsum("kc,krc->rc", a, walsh[:it + 1]) + lead * walsh[it + 1]
+        ops.append(dict(next=Dev(gexec, w.astype(t)), h=Dev(gexec, np.full((kd + 2, 2), CANARY, t)),
+                        residual_norm=Dev(gexec, np.full(2, CANARY, st.rt))))
+    return st, ops
+
+
+def _step_outputs(st, ops):
+    return ([v.get() for o in ops for v in o.values()] + [st.get_bases()] +
+            [st.get(k) for k in ("gsin", "gcos", "rnc", "an", "fin")])
+
+
+@pytest.mark.parametrize("pair", [("c128", br.KEEP), ("c64", br.KEEP)], ids=_ids)
+def test_arnoldi_scratch_is_private_to_the_step(gexec, pair):
+    """Steps 0 .. 3 of problem A on a second stream that a delay kernel holds, each followed at once by step
+    it + 1 of an independent problem B on the executor's stream - B's scratch request is the larger one every
+    time, and all of A's steps are still waiting when B's run.  A's outputs must be, bit for bit, those of the
+    same four steps run alone: the partials, coefficients and flags of a step belong to that step."""
+    import ctypes as C
+    import torch
+    tn = pair[0]
+    alone, ops = _exact_steps(gexec, tn, 0, 0)
+    for it in range(4):
+        alone.arnoldi(it, **ops[it])
+    want = _step_outputs(alone, ops)
+    assert np.all(want[-1] == 4)
+    held, ops_a = _exact_steps(gexec, tn, 0, 0)
+    other, ops_b = _exact_steps(gexec, tn, 1, 1)
+    side = torch.cuda.Stream()
+    sst = C.c_void_p(side.cuda_stream)
+    sync()
+    _call("gkoc_debug_delay", sst, C.c_int64(3000), 1, 64, 0)
+    for it in range(4):
+        held.arnoldi(it, stream=sst, **ops_a[it])
+        other.arnoldi(it + 1, stream=gexec.stream, **ops_b[it])
+    sync()
+    got = _step_outputs(held, ops_a)
+    assert len(got) == len(want)
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert same_bits(g, w), f"output {i} of the held steps differs from the run alone"
+    assert np.all(np.isfinite(np.concatenate([v.get().reshape(-1) for o in ops_b for v in o.values()])))
 
 
 # --------------------------------------------------------------------------------------- solve_krylov
