@@ -72,12 +72,20 @@ GKOC_CX gkoc_cplx<R> operator/(gkoc_cplx<R> a, gkoc_cplx<R> b)
     const R r = b.re / b.im, den = b.re * r + b.im;
     return {(a.re * r + a.im) / den, (a.im * r - a.re) / den};
 }
-// principal square root (std::sqrt(std::complex) up to rounding)
+// principal square root (std::sqrt(std::complex) up to rounding: within 4 eps of the exact root for
+// moduli between 4 * the smallest normal number and a quarter of the largest; outside that range
+// hypot or the sum below may overflow or lose bits, and nothing is promised).  The larger part is
+// t = sqrt((|z| + |re|) / 2), a sum of non-negative terms; the other one is |im| / (2 t) - taking
+// it as sqrt((|z| - |re|) / 2) cancels whenever |im| << |re|, which is where sqrt(<r, z>) of Minres
+// lives.  sqrt(+-0 + 0 i) = 0; the imaginary part has the sign of z.im.
 template <typename R>
 GKOC_CX gkoc_cplx<R> sqrt(gkoc_cplx<R> z)
 {
     const R m = ::hypot(z.re, z.im);
-    const R a = ::sqrt((m + z.re) / R(2)), b = ::sqrt((m - z.re) / R(2));
+    if (m == R(0)) return {R(0), R(0)};
+    const R t = ::sqrt((m + (z.re < R(0) ? -z.re : z.re)) / R(2));
+    const R u = (z.im < R(0) ? -z.im : z.im) / (R(2) * t);
+    const R a = z.re < R(0) ? u : t, b = z.re < R(0) ? t : u;
     return {a, z.im < R(0) ? -b : b};
 }
 template <typename R>

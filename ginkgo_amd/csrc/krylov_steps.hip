@@ -1218,7 +1218,10 @@ int launch_pipe_cg_step2_step1_dots(gkoc_stream_t s, int64_t n, T* x, T* r, T* z
 
 GKOC_DEF_KRYLOV(double, f64)
 GKOC_DEF_KRYLOV(float, f32)
-// (complex value types: the same templates on gkoc_cplx; agree with the reference to rounding)
+// (complex value types: the same templates on gkoc_cplx.  Every output is bit-identical to the plain
+// restatement with the textbook product, Smith's quotient and == on both parts; only what passes
+// through hypot or the complex sqrt - the scalars of minres::initialize / step_1, beta of
+// pipe_cg::step_2 - agrees with long double to rounding: tests/test_krylov_steps_gpu.py)
 GKOC_DEF_KRYLOV(gkoc_c128, c128)
 GKOC_DEF_KRYLOV(gkoc_c64, c64)
 GKOC_DEF_KRYLOV_X(double, f64)

@@ -52,7 +52,9 @@ typedef void* gkoc_stream_t;
 /* complex<double> / complex<float> of the value-type lists (include/ginkgo/core/base/types.hpp:471,
  * 689): two reals, real part first (the layout of the C and C++ complex types).  Complex kernels follow the
  * reference's expressions with the textbook complex product and a scaled quotient: they agree with the
- * reference to rounding (its own tolerance r<value_type>), not bit for bit. */
+ * reference to rounding (its own tolerance r<value_type>), not bit for bit.  Where a family says more, it says
+ * so: the Krylov step kernels (gkoc_bicgstab_* ... gkoc_ir_initialize below, gkoc_cg_*) are bit-identical in the
+ * complex types too, to their expressions evaluated with that product, that quotient and == on both parts. */
 #ifndef GKOC_COMPLEX_TYPES_DEFINED   /* (the library defines the same two layouts with arithmetic) */
 typedef struct { double re, im; } gkoc_c128;
 typedef struct { float re, im; } gkoc_c64;
@@ -1516,7 +1518,11 @@ GKOC_DECL_X_GMRES(gkoc_c64, c64)
         uint8_t* flags);                                                       \
     /* pipe_cg::step_2 of one iteration and step_1 of the next in one pass, with the partial sums \
      * of <r,z>, <w,z>, <r,r> (out3): ten vectors in, eight out; vectors bit-identical to the two \
-     * kernels.  beta_in / beta_out: two different scalars (the caller alternates them). */       \
+     * kernels.  beta_in / beta_out: two different scalars (the caller alternates them; the same  \
+     * address is GKOC_E_INVALID).  A stopped column keeps its vectors and gets beta_out =       \
+     * beta_in, and out3 holds the sums of the old vectors.  rows == 0: out3 = +0 and nothing     \
+     * else is touched, beta_out included.  work: at least 3 * 1024 * sizeof(T) bytes, else        \
+     * GKOC_E_WORKSPACE. */                                                                        \
     int gkoc_x_pipe_cg_step_2_step_1_dots_##TN(                                \
         gkoc_stream_t s, int64_t rows, T* x, T* r, T* z, T* w, T* p, T* q,     \
         T* f, T* g, const T* m, const T* n, const T* prev_rho, const T* rho,   \
@@ -1525,7 +1531,10 @@ GKOC_DECL_X_GMRES(gkoc_c64, c64)
         const gkoc_step_gate* gate);                                           \
     /* pipe_cg::step_1 (one column, unit strides; vectors bit-identical) and     \
      * out3 = {<r,z>, <w,z>, <r,r>} of the updated vectors: the three values a   \
-     * distributed PipeCg iteration all-reduces in one message */              \
+     * distributed PipeCg iteration all-reduces in one message.  beta == 0 or  \
+     * a stopped column: the vectors keep their bits, out3 holds the sums of   \
+     * the old ones.  rows == 0: out3 = +0, nothing else touched.  work: at    \
+     * least 3 * 1024 * sizeof(T) bytes, else GKOC_E_WORKSPACE. */             \
     int gkoc_x_pipe_cg_step_1_dots_##TN(                                       \
         gkoc_stream_t s, int64_t rows, T* x, T* r, T* z, T* w, const T* p,     \
         const T* q, const T* f, const T* g, const T* rho, const T* beta,       \
@@ -2223,7 +2232,20 @@ GKOC_DECL_TRANSPOSE(float, f32, int64_t, i64)
  * Argument order = the reference kernel's, every rows x cols operand followed by
  * its leading dimension; scalars are device arrays of `cols` values; columns whose
  * stop_status has stopped are left untouched.  Results bit-identical to the
- * reference (same expressions, no contraction). */
+ * reference (same expressions, no contraction) in the real types.  In the complex types every
+ * vector, stored scalar and stop byte is bit-identical to the same expressions with the textbook
+ * product, Smith's quotient, complex over real by parts and == on both parts (a scalar that is zero
+ * in one part only is not zero; a prev_rho * omega whose product underflows to zero is); the only
+ * outputs that agree with the reference to rounding instead are those behind a modulus (hypot) or
+ * the complex square root: beta, eta, eta_next of gkoc_minres_initialize, the scalars of
+ * gkoc_minres_step_1, beta of gkoc_pipe_cg_step_2.  The square root is within 4 eps of the exact
+ * one for moduli between 4 * the smallest normal number and a quarter of the largest.
+ * A scalar a step kernel stores (alpha of bicgstab_step_2 and cgs_step_2, omega of bicgstab_step_3,
+ * beta of cgs_step_1 and pipe_cg_step_2) is written by the thread of row 0 of a column that has
+ * not stopped: a stopped column keeps the scalar it had, and so does every column when rows == 0.
+ * The per-column kernels of the initialize entry points, gkoc_minres_step_1 and gkoc_gcr_restart
+ * run with rows == 0 as well; gkoc_bicgstab_finalize leaves stop_status alone then.
+ * All of this is what tests/test_krylov_steps_gpu.py holds the kernels to. */
 #define GKOC_DECL_KRYLOV(T, TN) \
     int gkoc_bicgstab_initialize_##TN(gkoc_stream_t s, int64_t rows, int64_t \
         cols, const T* b, int64_t ldb, T* r, int64_t ldr, T* rr, int64_t \

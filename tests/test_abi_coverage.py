@@ -17,7 +17,7 @@ _SUFFIX = re.compile(r"(_(f64|f32|c128|c64|i32|i64|u64))+$")
 # families this repository tests directly (tests/test_idr_gpu.py, test_cb_gmres_gpu.py, test_dense_gpu.py,
 # test_csr_struct_gpu.py, test_csr_diag_gpu.py, test_dist_partition_gpu.py, test_dist_index_gpu.py,
 # test_cdense_gpu.py, test_format_helpers_gpu.py, test_array_components_gpu.py, test_gmres_kernels_gpu.py,
-# test_mixed_triples_gpu.py)
+# test_mixed_triples_gpu.py, test_krylov_steps_gpu.py)
 MUST_BE_REACHED = ("idr", "cb_gmres", "dense_simple_apply", "dense_apply", "dense_convert", "compute_norm1",
                    "compute_mean", "reduce_add_array", "prefix_sum", "csr_spgemm_reuse", "csr_spgeam_numeric",
                    "in_index_set", "from_index_set", "csr_build_lookup", "csr_row_wise_absolute_sum",
@@ -28,7 +28,9 @@ MUST_BE_REACHED = ("idr", "cb_gmres", "dense_simple_apply", "dense_apply", "dens
                    "gkoc_dense_absolute", "gkoc_dense_fill_in_matrix_data", "gkoc_dense_add_scaled_identity_real",
                    "gkoc_jacobi_initialize_precisions", "gkoc_fill_array", "gkoc_convert_precision", "gkoc_conj_array",
                    "gkoc_narrow_i64_to_i32", "gkoc_x_residual_norm_then_cg_step_1", "gkoc_gmres_", "gkoc_common_gmres_",
-                   "gkoc_x_gmres_", "gkoc_csr_spmv_mixed", "gkoc_ell_spmv_mixed", "gkoc_dense_row_gather_mixed")
+                   "gkoc_x_gmres_", "gkoc_csr_spmv_mixed", "gkoc_ell_spmv_mixed", "gkoc_dense_row_gather_mixed",
+                   "gkoc_bicgstab_", "gkoc_cgs_", "gkoc_fcg_", "gkoc_pipe_cg_", "gkoc_bicg_", "gkoc_gcr_", "gkoc_minres_",
+                   "gkoc_chebyshev_", "gkoc_x_pipe_cg_step_")
 
 
 def stem(name):

@@ -4,8 +4,10 @@ are the real templates instantiated on gkoc_cplx (csrc/complex_type.hpp).  The r
 numpy's complex arithmetic on the same expressions (reference/solver/{cg,bicgstab,fcg,pipe_cg,
 gmres,common_gmres}_kernels.cpp, reference/matrix/{ell,sellp}_kernels.cpp) - there is no complex
 restatement in oracle/.  Tolerance: r<value_type> of the reference's own tests (1e-14 for
-complex<double>, 1e-6 for complex<float>, relative to the largest entry): complex kernels agree to
-rounding, not bit for bit (textbook product, Smith quotient)."""
+complex<double>, 1e-6 for complex<float>, relative to the largest entry).  That is the coarse check
+of this file only: tests/test_krylov_steps_gpu.py holds every complex step kernel bit for bit to its
+expressions evaluated with the textbook product and Smith's quotient (tests/krylov_step_refs.py), and
+what passes through hypot or the complex square root to rule R against long double."""
 import ctypes as C
 
 import numpy as np
