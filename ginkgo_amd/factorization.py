@@ -46,9 +46,11 @@ by the row of L^T.  A departure from Ginkgo: `with_symbolic_algorithm` accepts "
 true LU fill, whose extra entries come out as exact zeros.  `with_symbolic_factorization(csr)` takes a given
 pattern instead (for Cholesky its lower triangle); it is checked for square shape, sorted rows and stored diagonals
 only, and an entry of A outside it is dropped - with A's own pattern the result is Ilu's / Ic's.  Pivots are not
-checked and nothing is permuted: a zero pivot (negative for Cholesky) gives inf / NaN entries as in Ilu / Ic.  There
-is no fill-reducing ordering yet: in natural order the 27-point stencil's forest is a chain, so the fill is large
-and the numeric phase has n levels.
+checked and nothing is permuted: a zero pivot (negative for Cholesky) gives inf / NaN entries as in Ilu / Ic.  The
+factorizations keep the order they are given: in natural order the 27-point stencil's forest is a chain, so the
+fill is large and the numeric phase has n levels.  A fill-reducing ordering comes from outside:
+reorder.NestedDissection computes one, Csr.permute applies it, and reorder.ScaledReordered wraps Direct (or any
+solver) in it (docs/KERNELS.md 45 says what it buys).
 """
 import ctypes as C
 import math

@@ -192,6 +192,60 @@ def scalar(exec_, value, dtype=torch.float64):
     return Dense.from_numpy(exec_, np.array([[value]], dtype=_np_dtype(dtype)))
 
 
+PERMUTE_MODES = ("symmetric", "rows", "columns", "inverse_symmetric", "inverse_rows", "inverse_columns")
+_VALUE_NAMES = {**VT, torch.complex128: "c128", torch.complex64: "c64"}
+
+
+class Permutation(LinOp):
+    """matrix::Permutation (core/matrix/permutation.cpp): a LinOp over an index array p.  apply:
+    x[i, :] = b[p[i], :] - p[k] is the ORIGINAL index of what stands at the new position k, Ginkgo's convention."""
+
+    def __init__(self, exec_, perm):
+        super().__init__(exec_, (perm.numel(), perm.numel()))
+        if perm.dtype not in IT:
+            raise _lib.NotSupported("Permutation: int32 or int64 indices")
+        self.perm = perm
+
+    @staticmethod
+    def create(exec_, array, index_dtype=None):
+        """from a host array, which is checked to be a permutation of 0 .. n-1"""
+        a = np.asarray(array)
+        if a.ndim != 1 or a.dtype.kind not in "iu":
+            raise GkoError("Permutation.create takes a one-dimensional integer array")
+        if not np.array_equal(np.sort(a), np.arange(len(a))):
+            raise GkoError("Permutation.create: the array is no permutation of 0 .. n-1")
+        return Permutation(exec_, exec_.to_device(a.astype(index_dtype or np.int32), MEM_INDICES))
+
+    def get_permutation(self):
+        return self.perm
+
+    def get_permutation_size(self):
+        return self.perm.numel()
+
+    def compute_inverse(self):
+        out = self.exec.alloc((self.perm.numel(),), self.perm.dtype, MEM_INDICES)
+        call("gkoc_permutation_invert_" + IT[self.perm.dtype], self.exec.stream, self.perm.numel(), self.perm, out)
+        return Permutation(self.exec, out)
+
+    def compose(self, other):
+        """first this permutation, then `other`: result[i] = self[other[i]]"""
+        if other.perm.numel() != self.perm.numel() or other.perm.dtype != self.perm.dtype:
+            raise DimensionMismatch("Permutation.compose: two permutations of one size and index type")
+        out = self.exec.alloc((self.perm.numel(),), self.perm.dtype, MEM_INDICES)
+        call("gkoc_permutation_compose_" + IT[self.perm.dtype], self.exec.stream, self.perm.numel(), self.perm,
+             other.perm, out)
+        return Permutation(self.exec, out)
+
+    def apply_impl(self, b, x):
+        b.row_gather(self.perm, x)
+
+    def apply_advanced_impl(self, alpha, b, beta, x):
+        if b.dtype != x.dtype or b.dtype not in VT:
+            raise _lib.NotSupported("Permutation: the advanced apply takes two vectors of one real value type")
+        call(f"gkoc_dense_advanced_row_gather_{VT[b.dtype]}_{IT[self.perm.dtype]}", self.exec.stream,
+             self.perm.numel(), b.size[1], alpha.values, self.perm, b.values, b.ld, beta.values, x.values, x.ld)
+
+
 class _SparseBase(LinOp):
     def _operands(self, b, x):
         if b.dtype != self.dtype or x.dtype != self.dtype:
@@ -337,6 +391,33 @@ class Csr(_SparseBase):
         call("gkoc_csr_sort_by_column_index_" + self._suf(), self.exec.stream,
              self.size[0], self.row_ptrs, self.col_idxs, self.values)
         return self
+
+    def permute(self, permutation, mode="symmetric"):
+        """Csr::permute(permutation, mode) (core/matrix/csr.cpp): a new, sorted Csr.  With p = the index array,
+        "rows": out[i, :] = self[p[i], :], "columns": out[:, j] = self[:, p[j]], "symmetric": both,
+        out[i, j] = self[p[i], p[j]]; the "inverse_" modes undo them (out[p[i], p[j]] = self[i, j]).
+        gkoc_csr_permute_* moves the rows and renames the columns, gkoc_csr_sort_by_column_index_* sorts."""
+        if mode not in PERMUTE_MODES:
+            raise GkoError(f"Csr.permute: mode {mode!r} is none of {PERMUTE_MODES}")
+        inverse, what = mode.startswith("inverse_"), mode.replace("inverse_", "")
+        p = permutation.get_permutation()
+        if p.dtype != self.col_idxs.dtype:
+            raise _lib.NotSupported("Csr.permute: the permutation has another index type than the matrix")
+        for side, wanted in ((0, what != "columns"), (1, what != "rows")):
+            if wanted and p.numel() != self.size[side]:
+                raise DimensionMismatch(f"Csr.permute: a permutation of {p.numel()} for a {self.size} matrix")
+        ex, nnz, idx = self.exec, self.col_idxs.numel(), self.col_idxs.dtype
+        rows = p if what != "columns" else None
+        # the entry renames a column c to col_perm[c]: the inverse of p for the forward modes
+        cols = None if what == "rows" else p if inverse else permutation.compute_inverse().get_permutation()
+        rp, ci = ex.alloc((self.size[0] + 1,), idx, MEM_INDICES), ex.alloc((nnz,), idx, MEM_INDICES)
+        v = ex.alloc((nnz,), self.dtype, MEM_VALUES)
+        suf = f"{_VALUE_NAMES[self.dtype]}_{IT[idx]}"
+        call("gkoc_csr_permute_" + suf, ex.stream, self.size[0], self.row_ptrs, self.col_idxs, self.values, rows,
+             C.c_int(int(inverse)), cols, None, None, C.c_int(0), rp, ci, v)
+        call("gkoc_csr_sort_by_column_index_" + suf, ex.stream, self.size[0], rp, ci, v)
+        ex.synchronize()                # an inverse made for the columns is released on return
+        return Csr(ex, self.size, v, ci, rp, self.strategy)
 
     def structure_changed(self):
         """row_ptrs / col_idxs were written by the caller (a torch operation, another library) after the

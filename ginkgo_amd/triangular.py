@@ -12,8 +12,8 @@ side of the diagonal are ignored.
 exactly, up to rounding: `Direct.build().with_factorization(f).with_num_rhs(k).on(exec).generate(a)` factorizes
 with factorization.Lu (the default) or factorization.Cholesky and applies the two level-scheduled solves, L (unit
 diagonal for Lu) then U or L^T.  The vectors it needs are allocated at generate time for `num_rhs` columns, so an
-application enqueues kernels only and can be captured.  No pivoting and no fill-reducing ordering
-(factorization.py).
+application enqueues kernels only and can be captured.  No pivoting; the matrix is factorized in the order it has -
+reorder.ScaledReordered with reorder.NestedDissection puts a fill-reducing ordering around it.
 """
 import ctypes as C
 

@@ -3233,6 +3233,97 @@ GKOC_DECL_BATCH_SOLVER(bicgstab, float, f32)
 GKOC_DECL_BATCH(double, f64)
 GKOC_DECL_BATCH(float, f32)
 
+/* ------------------------------------- Nested dissection (reorder::NestedDissection; Ginkgo's
+ * experimental::reorder::NestedDissection, which calls METIS on the host - this one is specified here instead)
+ * A fill-reducing ordering for factorization::Cholesky / Lu.  Integers only, independent of thread order, stated
+ * here exactly (tests/reorder_refs.py restates it in numpy, as a recursion and as the stages below).
+ * G is the graph on the vertices 0 .. n-1 with an edge {i, j}, i != j, wherever the pattern stores (i, j) or
+ * (j, i); diagonal entries and values play no part.  G[R] is G restricted to the vertex set R, ascending(R) is R
+ * by vertex index.  The result is perm = order({0 .. n-1}), perm[k] = the original index of the vertex at the new
+ * position k (Ginkgo's convention; the row_perm of gkoc_csr_permute_* with row_inverse = 0).
+ * order(R), with the one parameter leaf_size >= 1:
+ *   1. |R| <= leaf_size: ascending(R).
+ *   2. C_1 .. C_k the connected components of G[R], ordered by their smallest vertex.  k > 1:
+ *      order(C_1) ++ ... ++ order(C_k).
+ *   3. Otherwise R is connected.  r0 = min R, l0 = the breadth-first levels of G[R] from r0, r1 = the smallest
+ *      vertex of the last level of l0, l = the breadth-first levels from r1, h = its last level.  Two sweeps,
+ *      always.  h < 2: ascending(R).
+ *   4. Sort R by (l(v), v); m* = the level of the vertex at position ceil(|R| / 2) - 1 (from 0),
+ *      m = min(max(m*, 1), h - 1).
+ *   5. S = the vertices of level m with a neighbour in R at level m + 1; A = the vertices of a level below m and
+ *      those of level m outside S; B = the vertices of a level above m.
+ *   6. order(A) ++ order(B) ++ ascending(S).
+ * What follows: A, B and S are non-empty (level 0 .. m-1 is in A as m >= 1; level m + 1 <= h exists, so B and,
+ * through a parent of one of its vertices, S are non-empty).  No edge joins A and B: an edge joins levels that
+ * differ by at most 1, and a vertex of level m with a neighbour at level m + 1 is in S.  Sizes, when m == m* (m
+ * was not clamped): the levels below m hold fewer than ceil(|R| / 2) vertices (the vertex at position
+ * ceil(|R| / 2) - 1 is of level m), and |B| <= floor(|R| / 2) (the levels up to m hold at least ceil(|R| / 2)).
+ * A itself has no such bound: it also takes the vertices of level m outside S, and a level can be wide (a path
+ * a - b - c - d with ten more leaves at b: m = 2, S = {c}, |A| = 12 of 14).  A clamped m gives no bound at all.
+ * Every step makes strictly smaller sets, so the recursion ends.  In the permuted matrix a vertex of S comes
+ * after everything it separates: A and B become subtrees of the elimination forest.
+ * No separator refinement, no multilevel coarsening, no minimum-degree ordering in the leaves, no weights.
+ *
+ * The device works on ALL regions of one recursion depth at once.  State (n words each, index type I):
+ *   order[]   a permutation of the vertices in which every region is one contiguous, ASCENDING segment; a vertex
+ *             whose place is final stays where it is.  At the end order == perm.
+ *   region[v] the position in order[] at which v's segment starts, or -1: v's place is final.
+ * Initially order = 0 .. n-1 and region = 0 everywhere (-1 everywhere if n <= leaf_size).  One round is
+ * components, regroup(key = label, final_from = n), levels(root = order), far_roots, levels(root = far), split,
+ * regroup(key = class, final_from = 2); it ends when regroup reports no live vertex.
+ * "neighbour of v" below: a stored column u != v of row v with region[u] == region[v] (the entries read the
+ * pattern as given; the class passes a symmetric one).
+ * components: label[v] = the smallest vertex of v's connected component inside its region, -1 for a final v.
+ *   Min-label propagation, pull style: one launch per sweep, a sweep reads the labels as they were when it began
+ *   (two buffers) and ends when a sweep changes nothing.  *sweeps_host = the sweeps run.
+ * levels: root[region[v]] is the root vertex of v's region (order[] itself for r0, far[] for r1).  level[v] = the
+ *   breadth-first level of v from its region's root, -1 for a final v and for a v the root does not reach.
+ *   Level-synchronous, pull style: in step t an unlevelled v with a neighbour of level t takes t + 1; one launch
+ *   per step, ends when a step changes nothing.  *steps_host = the steps run.  O(n + entries of the unlevelled
+ *   rows) per step: not work-efficient, chosen because every word has one writer and nothing is compacted.
+ * far_roots: far[s] = the smallest vertex of the largest level among the vertices of the region that starts at
+ *   s, -1 in every word that starts no region.  Integer atomics (max, then min), order-independent.
+ * split: per region |R|, h and m* (a histogram of the levels in the region's own slots s + level, integer
+ *   atomics, and the library's scan), then class[v]: 0 = A, 1 = B, 2 = S, 3 = the region stays undivided
+ *   (h < 2), -1 for a final v.  Every live vertex must have a level.
+ * regroup: order[] is stably sorted by (segment, key[v], v) (two passes of rocprim::radix_sort_pairs); the runs
+ *   of equal (segment, key) are the new segments.  A vertex is final afterwards if it was final, if
+ *   key[v] >= final_from, or if its run has at most leaf_size vertices; the others get their run's start as
+ *   region.  order and region are updated in place.  *live_host = the vertices that are not final.
+ * Every loop the host drives is bounded by n iterations: GKOC_E_INVALID if a sweep (a step) still changes
+ * something after n of them, which no valid input does.  No kernel waits for another workgroup.
+ * GKOC_E_INVALID before any kernel indexes with the inputs, the outputs untouched: negative sizes, null
+ * pointers, leaf_size < 1, row pointers that do not ascend from 0 to nnz, a column outside [0, n), region outside
+ * [-1, n), a root outside [0, n), a level outside [-1, n) or a live vertex without one or a level that leaves
+ * the array from its segment's start (far_roots, split), an order that is no permutation of [0, n) (split,
+ * regroup), a key of a live vertex outside [0, max(n, 4)) (regroup).  n == 0 is GKOC_OK.
+ * Set-up entries: they take scratch from the arena and synchronise the stream; not meant to be captured.
+ * Kernels that read rows (components, levels, split): one group of 16 / 32 / 64 lanes per row, lane = stored
+ * entry, chosen per call from the longest row at the limits gkoc_reorder_row_limits reports (ascending, at most
+ * 4); a longer row is streamed in rounds of 64 entries.  No length cap, no serial path.  A group stops at its
+ * first hit (levels, split).  Every output word has one writer; "something changed" is a plain store of 1.
+ * The column-offset plan (above) and these entries: all arrays they write are STATE of the reordering or the
+ * permutation, typed by the index width of the entry (gkoc_reorder_i32 / gkoc_reorder_i64) - never row_ptrs or
+ * col_idxs of a matrix, so the entries do not belong to the plan's contract and notify nothing; a matrix is
+ * permuted by gkoc_csr_permute_*, which the contract lists.  Host results are long long. */
+typedef int32_t gkoc_reorder_i32;
+typedef int64_t gkoc_reorder_i64;
+int gkoc_reorder_row_limits(int* limits_host, int* count_host);
+#define GKOC_DECL_REORDER(I, A, IN)                                                                          \
+    int gkoc_reorder_components_##IN(gkoc_stream_t s, int64_t n, int64_t nnz, const I* row_ptrs,             \
+                                     const I* col_idxs, const I* region, A* label, long long* sweeps_host);  \
+    int gkoc_reorder_levels_##IN(gkoc_stream_t s, int64_t n, int64_t nnz, const I* row_ptrs,                 \
+                                 const I* col_idxs, const I* region, const I* root, A* level,                \
+                                 long long* steps_host);                                                     \
+    int gkoc_reorder_far_roots_##IN(gkoc_stream_t s, int64_t n, const I* region, const I* level, A* far);    \
+    int gkoc_reorder_split_##IN(gkoc_stream_t s, int64_t n, int64_t nnz, const I* row_ptrs,                  \
+                                const I* col_idxs, const I* order, const I* region, const I* level,          \
+                                A* cls);                                                                     \
+    int gkoc_reorder_regroup_##IN(gkoc_stream_t s, int64_t n, int64_t leaf_size, int64_t final_from,         \
+                                  const I* key, A* order, A* region, long long* live_host);
+GKOC_DECL_REORDER(int32_t, gkoc_reorder_i32, i32)
+GKOC_DECL_REORDER(int64_t, gkoc_reorder_i64, i64)
+
 #ifdef __cplusplus
 }
 #endif
