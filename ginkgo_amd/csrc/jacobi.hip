@@ -1220,8 +1220,7 @@ __global__ __launch_bounds__(256) void jacobi_apply_fixed_multi_kernel(
     load(0, bv, sum);
     for (int j0 = 0; j0 < nrhs; j0 += PC) {
         const int nc = nrhs - j0 < PC ? nrhs - j0 : PC;
-        // the next pass's loads travel while this pass's products are formed.  (When b and x are
-        // the same array the next pass reads columns this pass does not write.)
+        // the next pass's loads travel while this pass's products are formed (b and x do not overlap)
         load(j0 + PC, bvn, sumn);
 #pragma unroll
         for (int c = 0; c < BO; ++c) {
@@ -1608,6 +1607,7 @@ int launch_apply_dot(gkoc_stream_t s, int64_t num_blocks, int64_t n_rows,
         return GKOC_OK;
     }
     GKOC_REQUIRE(block_ptrs && blocks && b && x && work, GKOC_E_INVALID, "null pointer");
+    GKOC_REQUIRE(b != x, GKOC_E_INVALID, "b and x must not overlap");
     const int64_t bo = scheme.block_offset;
     GKOC_REQUIRE(wide_group_layout(scheme), GKOC_E_NOT_SUPPORTED,
                  "fused apply+dot needs block_offset in {1,2,4,8,16} and a 64-wide group");
@@ -1639,6 +1639,7 @@ int launch_apply(gkoc_stream_t s, int64_t num_blocks, uint32_t max_bs,
 {
     if (num_blocks <= 0 || nrhs <= 0) return GKOC_OK;
     GKOC_REQUIRE(block_ptrs && blocks && b && x, GKOC_E_INVALID, "null pointer");
+    GKOC_REQUIRE(b != x, GKOC_E_INVALID, "b and x must not overlap");
     GKOC_REQUIRE(scheme.block_offset >= 1 &&
                      (scheme.block_offset << scheme.group_power) <= 64,
                  GKOC_E_NOT_SUPPORTED, "storage stride must be <= 64 (wave size)");
@@ -1661,7 +1662,7 @@ int launch_apply(gkoc_stream_t s, int64_t num_blocks, uint32_t max_bs,
     const int64_t mfma_mode = tune_value(GKOC_TUNE_JACOBI_MFMA);
     const int64_t mfma_from = mfma_mode == 1 ? 2 : mfma_mode == 3 ? 4 : 9;
     const bool mfma = sizeof(T) == 8 && mfma_mode != 0 && nrhs >= mfma_from && bo == 8 &&
-                      scheme.group_power == 3 && b != x;
+                      scheme.group_power == 3;
     if (nrhs >= 2 && wide && !mfma) {
         // several right-hand sides, fast-path layout: the blocks stay in registers for all columns
         // (L256, block size 8, profiles/r03_jacobi_multi_256.txt: 2 / 4 / 8 columns 279 / 375 / 630 us =
@@ -1733,24 +1734,23 @@ int launch_apply_stored(gkoc_stream_t s, int64_t num_blocks, uint32_t max_bs,
     if (num_blocks <= 0 || nrhs <= 0) return GKOC_OK;
     GKOC_REQUIRE(known_precision(prec), GKOC_E_NOT_SUPPORTED, "unknown storage precision");
     GKOC_REQUIRE(block_ptrs && blocks && b && x, GKOC_E_INVALID, "null pointer");
+    GKOC_REQUIRE(b != x, GKOC_E_INVALID, "b and x must not overlap");
     const int64_t bo = scheme.block_offset;
     GKOC_REQUIRE(wide_group_layout(scheme), GKOC_E_NOT_SUPPORTED,
                  "reduced-precision storage needs block_offset in {1,2,4,8,16}, 64-wide groups");
     GKOC_REQUIRE(max_bs <= uint64_t(bo), GKOC_E_INVALID, "max_block_size exceeds block_offset");
+    // refused before any launch: the kernel takes one column of consecutive values
+    GKOC_REQUIRE(nrhs == 1 && ldb == 1 && ldx == 1, GKOC_E_NOT_SUPPORTED,
+                 "reduced-precision storage: one right-hand side with unit strides");
     const int64_t groups = ceildiv(num_blocks, int64_t(1) << scheme.group_power);
     const int64_t go = scheme.group_offset;
-    // one right-hand side per launch (reference: one apply_block per column as well)
-    for (int64_t j = 0; j < nrhs; ++j) {
-        GKOC_REQUIRE(ldb == 1 && ldx == 1, GKOC_E_NOT_SUPPORTED,
-                     "reduced-precision storage: one right-hand side with unit strides");
-        with_precision(prec, [&](auto pc) {
-            with_block_offset(bo, [&](auto bc) {
-                launch_apply_stored_fixed<I, ADV, decltype(bc)::value, decltype(pc)::value>(
-                    s, num_blocks, groups, go, block_ptrs, blocks, alpha, b + j, beta, x + j);
-            });
+    with_precision(prec, [&](auto pc) {
+        with_block_offset(bo, [&](auto bc) {
+            launch_apply_stored_fixed<I, ADV, decltype(bc)::value, decltype(pc)::value>(
+                s, num_blocks, groups, go, block_ptrs, blocks, alpha, b, beta, x);
         });
-        GKOC_LAUNCH_OK();
-    }
+    });
+    GKOC_LAUNCH_OK();
     return GKOC_OK;
 }
 
@@ -1775,6 +1775,7 @@ int launch_apply_adaptive(gkoc_stream_t s, int64_t num_blocks, uint32_t max_bs,
 {
     if (num_blocks <= 0 || nrhs <= 0) return GKOC_OK;
     GKOC_REQUIRE(block_ptrs && blocks && precisions && b && x, GKOC_E_INVALID, "null pointer");
+    GKOC_REQUIRE(b != x, GKOC_E_INVALID, "b and x must not overlap");
     GKOC_REQUIRE(scheme.block_offset >= 1 && (scheme.block_offset << scheme.group_power) <= 64 &&
                      max_bs <= uint64_t(scheme.block_offset),
                  GKOC_E_NOT_SUPPORTED, "storage stride must be <= 64 (wave size)");
@@ -1953,7 +1954,7 @@ bool launch_apply_lanes_any(hipStream_t st, int64_t num_blocks, gkoc_jacobi_sche
                             const T* blocks, const uint8_t* precisions, const T* alpha, const T* b, int64_t ldb,
                             const T* beta, T* x, int64_t ldx, int64_t nrhs)
 {
-    if (!wave_group_layout(scheme) || nrhs > 0x7fffffff || b == x) return false;
+    if (!wave_group_layout(scheme) || nrhs > 0x7fffffff) return false;
     const int64_t groups = ceildiv(num_blocks, int64_t(1) << scheme.group_power);
 #define GKOC_JAC_LANES(SUB_, GPW_)                                                                       \
     {                                                                                                    \
@@ -1978,13 +1979,15 @@ bool launch_apply_lanes_any(hipStream_t st, int64_t num_blocks, gkoc_jacobi_sche
 }
 
 // ------------------------------------------------------------ 4c. thread per row, any value type
-// What the lane kernel does not take (a scheme whose groups do not fill a wavefront, b == x) and
+// What the lane kernel does not take (a scheme whose groups do not fill a wavefront) and
 // GKOC_TUNE_JACOBI_LANES = 1: one thread per (row, right-hand side) walks its row of the inverse block in
 // the interleaved scheme - element (r, c) of block b at group_offset * (b >> gp) + block_offset * (b & mask)
 // + r + c * stride (include/ginkgo/core/preconditioner/jacobi.hpp:37-140) - widens the entries on load
 // (precisions == nullptr: full storage) and adds the products in column order (reference apply_block with
 // the resolved precision, reference/preconditioner/jacobi_kernels.cpp:419-531).  row_block[row] = the block
 // of a row (filled by jacobi_row_block_kernel).
+// b and x must not overlap: a thread reads the b rows of its whole block while threads of other wavefronts
+// write x.  launch_apply_any refuses b == x.
 template <typename I>
 __global__ __launch_bounds__(256) void jacobi_row_block_kernel(int64_t num_blocks,
                                                               const I* __restrict__ block_ptrs,
@@ -2034,6 +2037,7 @@ int launch_apply_any(gkoc_stream_t s, int64_t num_blocks, gkoc_jacobi_scheme sch
 {
     if (num_blocks <= 0 || nrhs <= 0) return GKOC_OK;
     GKOC_REQUIRE(block_ptrs && blocks && b && x, GKOC_E_INVALID, "null pointer");
+    GKOC_REQUIRE(b != x, GKOC_E_INVALID, "b and x must not overlap");
     hipStream_t st = as_stream(s);
     if (tune_value(GKOC_TUNE_JACOBI_LANES) != 1 &&
         launch_apply_lanes_any<T, I, ADV>(st, num_blocks, scheme, block_ptrs, blocks, precisions, alpha, b, ldb,
@@ -2253,7 +2257,9 @@ extern "C" int gkoc_x_cg_step_2_jacobi_apply_fits(int64_t num_blocks, int64_t n_
 }
 
 // complex block-Jacobi, full storage: generate (the Gauss-Jordan kernel on gkoc_cplx: pivot by magnitude),
-// simple_apply / apply (the lane kernel, else thread per row).  Agrees with the reference to rounding.
+// simple_apply / apply (the lane kernel, else thread per row).  Agrees with the reference to rounding; the products
+// and the complex<double> inverse blocks have the bits of the textbook product / Smith's quotient restatement
+// (tests/jacobi_refs.py), the complex<float> inverse blocks agree with it to rounding.
 #define GKOC_DEF_CJACOBI(T, TN, I, IN)                                                                  \
     extern "C" int gkoc_jacobi_generate_##TN##_##IN(                                                    \
         gkoc_stream_t s, int64_t n_rows, const I* row_ptrs, const I* col_idxs, const T* vals,           \

@@ -947,7 +947,17 @@ int gkoc_set_all_statuses(gkoc_stream_t s, int64_t cols, uint8_t stopping_id,
  * (block_precisions == NULL); adaptive precision returns GKOC_E_NOT_SUPPORTED.
  * block_pointers / num_blocks are integer-exact vs the reference; the inverse
  * blocks and apply results are bit-identical (same pivoting, same operation
- * order, no FMA contraction). */
+ * order, no FMA contraction; the matrix-core kernel that serves nine and more
+ * columns at block_offset 8 in double fuses its multiply-adds and agrees to
+ * (bs + 2) eps sum_c |alpha m_c b_c| per entry).
+ * generate stops transforming a block at a pivot that is exactly zero and stores it
+ * as it stands; of several rows of the largest magnitude the first one is the pivot.
+ * Storage outside the blocks' bs x bs entries is not written.
+ * simple_apply / apply, apply_stored, apply_adaptive (every value type) and the fused
+ * gkoc_x_jacobi_simple_apply_dot: b and x must not overlap - a row of x is written
+ * while other rows of its block are still read from b; a call with b == x is refused
+ * with GKOC_E_INVALID, any other overlap is undefined.
+ * beta == 0 does not read x.  num_blocks == 0 or nrhs == 0 writes nothing. */
 typedef struct gkoc_jacobi_scheme {
     int64_t block_offset;
     int64_t group_offset;
@@ -979,7 +989,11 @@ GKOC_DECL_JACOBI(double, f64, int64_t, i64)
 GKOC_DECL_JACOBI(float, f32, int32_t, i32)
 GKOC_DECL_JACOBI(float, f32, int64_t, i64)
 /* complex blocks, uniform storage precision (block-wise / adaptive: GKOC_DECL_JACOBI_ADAPTIVE_ANY
- * below): max_block_size <= 32, untuned apply (one lane per row) */
+ * below): max_block_size <= 32 (33 and more: GKOC_E_NOT_SUPPORTED).  Operation for operation the real
+ * kernels with the textbook product, Smith's quotient (csrc/complex_type.hpp) and the modulus as the
+ * pivot's measure: the products (sum = 0, sum += m_c b_c in column order, then alpha sum + beta x) and
+ * the complex<double> inverse blocks have the bits of that restatement (tests/jacobi_refs.py); the
+ * complex<float> inverse blocks agree with it to rounding. */
 GKOC_DECL_JACOBI(gkoc_c128, c128, int32_t, i32)
 GKOC_DECL_JACOBI(gkoc_c128, c128, int64_t, i64)
 GKOC_DECL_JACOBI(gkoc_c64, c64, int32_t, i32)
@@ -1019,7 +1033,10 @@ GKOC_DECL_CJACOBI_TRANSPOSE(gkoc_c64, c64, int64_t, i64)
  * widens each entry on load and multiplies in double (apply_block with its
  * default_converter, :413-470).  alpha = beta = NULL: x = M b, else
  * x = alpha M b + beta x.  Bit-identical to the reference.  Layouts with 64-wide
- * groups (max_block_size <= 16), one right-hand side, unit strides. */
+ * groups (max_block_size <= 16), one right-hand side, unit strides: with a reduced
+ * precision nrhs != 1, ldb != 1 or ldx != 1 is refused with GKOC_E_NOT_SUPPORTED
+ * before anything is launched (precision 0 is gkoc_jacobi_apply / simple_apply).
+ * convert_storage narrows every entry of a storage group, its padding included. */
 /* jacobi::initialize_precisions (core/preconditioner/jacobi_kernels.hpp:120-123):
  * precisions[i] = source[i % source_size], one precision_reduction byte per block */
 int gkoc_jacobi_initialize_precisions(gkoc_stream_t s, const uint8_t* source,
