@@ -184,6 +184,11 @@ __global__ __launch_bounds__(256) void fmt_spmv_frag_kernel(
         step = slice_size;
     }
     if (nrow >= n_rows) nlen = 0;
+    // A lane without entries still loads (below) whenever another lane of its wave has some, and
+    // the first slot of an EMPTY SELL-P slice need not exist: with no stored slice behind it,
+    // slice_sets[slice] * slice_size + local lies up to slice_size - 1 elements past the end of
+    // cols / vals.  Such a lane loads element 0, which exists because the wave's maxlen > 0.
+    if (nlen == 0) nfirst = 0;
     int maxlen = nlen;   // wave-wide maximum
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -191,7 +196,8 @@ __global__ __launch_bounds__(256) void fmt_spmv_frag_kernel(
         maxlen = o > maxlen ? o : maxlen;
     }
     // The entry loop has NO branches: every lane always loads (an entry past the end of its row
-    // re-reads the row's first entry and counts as padding, a padding entry gathers row 0 of b, a
+    // re-reads the row's first entry - element 0 of the arrays for a row without entries - and
+    // counts as padding, a padding entry gathers row 0 of b, a
     // lane whose columns lie past nrhs gathers columns 0 and 1) and the sums are selected -
     // conditional loads made the compiler wait for each of them in turn.
     for (int j0 = 0; j0 < nrhs; j0 += NR) {
@@ -269,11 +275,13 @@ __global__ __launch_bounds__(256) void fmt_spmv_frag_kernel(
 }
 
 // the fragment layout serves three and more columns (two: the lane = row kernel is as fast, L256
-// 1.30 ms both) and needs pairs of columns as aligned 2-element vectors of b and c
+// 1.30 ms both) and needs pairs of columns as aligned 2-element vectors of b and c.  Its padding
+// slots gather row 0 of b, so a matrix without columns (every slot is padding, b has no rows) stays
+// with the lane = row kernel, which loads nothing for a padding slot.
 template <typename T>
-inline bool frag_layout(int64_t nrhs, const T* b, int64_t ldb, const T* c, int64_t ldc)
+inline bool frag_layout(int64_t n_cols, int64_t nrhs, const T* b, int64_t ldb, const T* c, int64_t ldc)
 {
-    return nrhs >= 3 && reinterpret_cast<uintptr_t>(b) % (2 * sizeof(T)) == 0 && ldb % 2 == 0 &&
+    return n_cols > 0 && nrhs >= 3 && reinterpret_cast<uintptr_t>(b) % (2 * sizeof(T)) == 0 && ldb % 2 == 0 &&
            reinterpret_cast<uintptr_t>(c) % (2 * sizeof(T)) == 0 && ldc % 2 == 0;
 }
 
@@ -565,12 +573,11 @@ int launch_ell(gkoc_stream_t s, int64_t n_rows, int64_t n_cols, int64_t k,
                const T* b, int64_t ldb, const T* beta, T* c, int64_t ldc,
                int64_t nrhs)
 {
-    (void)n_cols;
     GKOC_REQUIRE(n_rows >= 0 && k >= 0 && nrhs >= 0 && stride >= n_rows,
                  GKOC_E_INVALID, "bad ELL dimensions");
     if (n_rows == 0 || nrhs == 0) return GKOC_OK;
     if (ADV) GKOC_REQUIRE(alpha && beta, GKOC_E_INVALID, "null alpha/beta");
-    if (nrhs >= 2 && frag_layout(nrhs, b, ldb, c, ldc)) {
+    if (nrhs >= 2 && frag_layout(n_cols, nrhs, b, ldb, c, ldc)) {
         const dim3 grid(unsigned(ceildiv(n_rows, 256)));
         const int64_t chunk = tune_value(GKOC_TUNE_MULTI_XCD_CHUNK_ROWS) / 256;
         const bool idx32 = n_cols * ldb < (int64_t(1) << 32);
@@ -643,12 +650,11 @@ int launch_sellp(gkoc_stream_t s, int64_t n_rows, int64_t n_cols,
                  const T* b, int64_t ldb, const T* beta, T* c, int64_t ldc,
                  int64_t nrhs)
 {
-    (void)n_cols;
     GKOC_REQUIRE(n_rows >= 0 && slice_size >= 1 && nrhs >= 0, GKOC_E_INVALID,
                  "bad SELL-P dimensions");
     if (n_rows == 0 || nrhs == 0) return GKOC_OK;
     if (ADV) GKOC_REQUIRE(alpha && beta, GKOC_E_INVALID, "null alpha/beta");
-    if (nrhs >= 2 && frag_layout(nrhs, b, ldb, c, ldc)) {
+    if (nrhs >= 2 && frag_layout(n_cols, nrhs, b, ldb, c, ldc)) {
         const dim3 grid(unsigned(ceildiv(n_rows, 256)));
         const int64_t chunk = tune_value(GKOC_TUNE_MULTI_XCD_CHUNK_ROWS) / 256;
         const bool idx32 = n_cols * ldb < (int64_t(1) << 32);

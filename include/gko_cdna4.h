@@ -367,7 +367,9 @@ int gkoc_csr_plan_classes(const void* row_ptrs, const void* col_idxs, uint64_t* 
  * ell::spmv / advanced_spmv  core/matrix/ell_kernels.hpp:20-34
  * column-major storage: entry (row, j) at row + j*stride; padding col = -1
  * (include/ginkgo/core/matrix/ell.hpp:385-388).  reference semantics:
- * reference/matrix/ell_kernels.cpp:29-69. Bit-identical (row-sequential). */
+ * reference/matrix/ell_kernels.cpp:29-69. Bit-identical (row-sequential).
+ * A slot counts by its column alone: column -1 contributes nothing, whatever value is stored with it
+ * and wherever in the row it sits.  n_cols == 0 is allowed (every slot is padding; b is not read). */
 #define GKOC_DECL_ELL(T, TN, I, IN)                                            \
     int gkoc_ell_spmv_##TN##_##IN(                                             \
         gkoc_stream_t s, int64_t n_rows, int64_t n_cols,                       \
@@ -394,7 +396,8 @@ GKOC_DECL_ELL(gkoc_c64, c64, int64_t, i64)
  * n_slices+1 / n_slices; entry (row, j) of slice s at
  * (slice_sets[s] + j) * slice_size + row_in_slice
  * (include/ginkgo/core/matrix/sellp.hpp:379-383).  reference semantics:
- * reference/matrix/sellp_kernels.cpp:27-100. Bit-identical. */
+ * reference/matrix/sellp_kernels.cpp:27-100. Bit-identical.
+ * A slot counts by its column alone, as for ELL; n_cols == 0 is allowed (b is not read). */
 #define GKOC_DECL_SELLP(T, TN, I, IN)                                          \
     int gkoc_sellp_spmv_##TN##_##IN(                                           \
         gkoc_stream_t s, int64_t n_rows, int64_t n_cols, int64_t slice_size,   \

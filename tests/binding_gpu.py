@@ -1,6 +1,7 @@
 """Device buffers for the tests that call gkoc_* entry points directly (tests/test_idr_gpu.py,
 test_cb_gmres_gpu.py, test_dense_gpu.py, test_csr_struct_gpu.py, test_csr_diag_gpu.py, test_dist_partition_gpu.py, test_dist_index_gpu.py,
-test_cdense_gpu.py, test_format_helpers_gpu.py, test_array_components_gpu.py): any numpy dtype
+test_cdense_gpu.py, test_format_helpers_gpu.py, test_array_components_gpu.py, test_format_spmv_gpu.py,
+test_format_setup_gpu.py): any numpy dtype
 travels as bytes, strided operands are cut out of a padded array whose padding keeps a canary, flat outputs
 are followed by one."""
 import ctypes as C

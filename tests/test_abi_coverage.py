@@ -17,7 +17,8 @@ _SUFFIX = re.compile(r"(_(f64|f32|c128|c64|i32|i64|u64))+$")
 # families this repository tests directly (tests/test_idr_gpu.py, test_cb_gmres_gpu.py, test_dense_gpu.py,
 # test_csr_struct_gpu.py, test_csr_diag_gpu.py, test_dist_partition_gpu.py, test_dist_index_gpu.py,
 # test_cdense_gpu.py, test_format_helpers_gpu.py, test_array_components_gpu.py, test_gmres_kernels_gpu.py,
-# test_mixed_triples_gpu.py, test_krylov_steps_gpu.py, test_jacobi_kernels_gpu.py)
+# test_mixed_triples_gpu.py, test_krylov_steps_gpu.py, test_jacobi_kernels_gpu.py, test_format_spmv_gpu.py,
+# test_format_setup_gpu.py)
 MUST_BE_REACHED = ("idr", "cb_gmres", "dense_simple_apply", "dense_apply", "dense_convert", "compute_norm1",
                    "compute_mean", "reduce_add_array", "prefix_sum", "csr_spgemm_reuse", "csr_spgeam_numeric",
                    "in_index_set", "from_index_set", "csr_build_lookup", "csr_row_wise_absolute_sum",
@@ -32,7 +33,11 @@ MUST_BE_REACHED = ("idr", "cb_gmres", "dense_simple_apply", "dense_apply", "dens
                    "gkoc_bicgstab_", "gkoc_cgs_", "gkoc_fcg_", "gkoc_pipe_cg_", "gkoc_bicg_", "gkoc_gcr_", "gkoc_minres_",
                    "gkoc_chebyshev_", "gkoc_x_pipe_cg_step_", "gkoc_jacobi_find_blocks", "gkoc_jacobi_generate",
                    "gkoc_jacobi_simple_apply", "gkoc_jacobi_apply", "gkoc_jacobi_transpose", "gkoc_jacobi_convert_storage",
-                   "gkoc_x_jacobi_", "gkoc_x_cg_step_2_jacobi_apply", "gkoc_x_pipe_cg_steps_jacobi")
+                   "gkoc_x_jacobi_", "gkoc_x_cg_step_2_jacobi_apply", "gkoc_x_pipe_cg_steps_jacobi",
+                   "gkoc_ell_spmv", "gkoc_ell_advanced_spmv", "gkoc_sellp_spmv", "gkoc_sellp_advanced_spmv",
+                   "gkoc_compute_max_row_nnz", "gkoc_sellp_compute_slice_sets", "gkoc_convert_ptrs_to_sizes",
+                   "gkoc_convert_idxs_to_ptrs", "gkoc_fill_seq_array", "gkoc_aos_to_soa", "gkoc_csr_convert_to_ell",
+                   "gkoc_csr_convert_to_sellp")
 
 
 def stem(name):

@@ -163,10 +163,14 @@ def test_gmres_kernels_complex(gexec, tn):
 @pytest.mark.parametrize("tn", ["c128", "c64"])
 @pytest.mark.parametrize("nrhs", [1, 3])
 def test_ell_and_sellp_products_complex(gexec, tn, nrhs):
-    """ell::{spmv, advanced_spmv}, sellp::{...} on complex values against scipy's product of the same
-    matrix (padding entries skipped, beta = 0 does not read c: c starts as NaN)"""
+    """ell::{spmv, advanced_spmv}, sellp::{...} on complex values of a scipy matrix (padding entries skipped,
+    beta = 0 does not read c: c starts as NaN), under rule R against the long-double product of
+    tests/format_spmv_refs.py - whose CPU test compares it with scipy's product; every launcher branch and
+    edge shape of these entries is in tests/test_format_spmv_gpu.py"""
     import scipy.sparse as sp
     import torch
+    import binding_refs as br
+    import format_spmv_refs as fr
     from ginkgo_amd._lib import call
     ct, rt, tol = CT[tn]
     rng = np.random.default_rng(21)
@@ -177,7 +181,10 @@ def test_ell_and_sellp_products_complex(gexec, tn, nrhs):
     lens = np.diff(a.indptr)
     per_row = int(lens.max())
     b = _rand(rng, (m, nrhs), ct)
-    want = (a.astype(np.complex128) @ b.astype(np.complex128))
+
+    def rule_r(got, pair):
+        ok, ratio = br.rule_r(got, pair[0], pair[1], ct)
+        assert ok and not np.any(np.isnan(got)), ratio
     # ELL (column major, stride n + 5)
     stride = n + 5
     cols = -np.ones((per_row, stride), np.int32)
@@ -190,20 +197,21 @@ def test_ell_and_sellp_products_complex(gexec, tn, nrhs):
     c = _dev(gexec, np.full((n, nrhs), np.nan + 0j, ct))
     call("gkoc_ell_spmv_" + tn + "_i32", gexec.stream, n, m, per_row, stride, dcols, dvals, db, nrhs, c, nrhs, nrhs)
     torch.cuda.synchronize()
-    _close(_host(c), want.astype(ct), 30 * tol)
+    ell = (ct, n, per_row, stride, cols.reshape(-1), vals.reshape(-1), b)
+    rule_r(_host(c), fr.ell_product(*ell))
     alpha, beta = np.array([0.5 - 2j], ct), np.array([0], ct)
     c.copy_(torch.from_numpy(np.full((n, nrhs), np.nan + 0j, ct)))
     call("gkoc_ell_advanced_spmv_" + tn + "_i32", gexec.stream, n, m, per_row, stride, _dev(gexec, alpha), dcols,
          dvals, db, nrhs, _dev(gexec, beta), c, nrhs, nrhs)
     torch.cuda.synchronize()
-    _close(_host(c), (alpha[0] * want).astype(ct), 60 * tol)
+    rule_r(_host(c), fr.ell_product(*ell, alpha=alpha[0], beta=0))
     c0 = _rand(rng, (n, nrhs), ct)
     beta = np.array([-1 + 0.5j], ct)
     c.copy_(torch.from_numpy(c0))
     call("gkoc_ell_advanced_spmv_" + tn + "_i32", gexec.stream, n, m, per_row, stride, _dev(gexec, alpha), dcols,
          dvals, db, nrhs, _dev(gexec, beta), c, nrhs, nrhs)
     torch.cuda.synchronize()
-    _close(_host(c), (alpha[0] * want + beta[0] * c0).astype(ct), 60 * tol)
+    rule_r(_host(c), fr.ell_product(*ell, alpha=alpha[0], beta=beta[0], c=c0))
     # SELL-P, slice size 64
     ss = 64
     n_slices = -(-n // ss)
@@ -222,13 +230,14 @@ def test_ell_and_sellp_products_complex(gexec, tn, nrhs):
     call("gkoc_sellp_spmv_" + tn + "_i32", gexec.stream, n, m, ss, _dev(gexec, sets.view(np.int64)),
          _dev(gexec, slens.view(np.int64)), _dev(gexec, scols), _dev(gexec, svals), db, nrhs, c, nrhs, nrhs)
     torch.cuda.synchronize()
-    _close(_host(c), want.astype(ct), 30 * tol)
+    sellp = (ct, n, ss, sets, slens, scols, svals, b)
+    rule_r(_host(c), fr.sellp_product(*sellp))
     c.copy_(torch.from_numpy(c0))
     call("gkoc_sellp_advanced_spmv_" + tn + "_i32", gexec.stream, n, m, ss, _dev(gexec, alpha),
          _dev(gexec, sets.view(np.int64)), _dev(gexec, slens.view(np.int64)), _dev(gexec, scols),
          _dev(gexec, svals), db, nrhs, _dev(gexec, beta), c, nrhs, nrhs)
     torch.cuda.synchronize()
-    _close(_host(c), (alpha[0] * want + beta[0] * c0).astype(ct), 60 * tol)
+    rule_r(_host(c), fr.sellp_product(*sellp, alpha=alpha[0], beta=beta[0], c=c0))
 
 
 @pytest.mark.parametrize("tn", ["c128", "c64"])
