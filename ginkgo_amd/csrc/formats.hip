@@ -18,10 +18,14 @@
 // issued UNROLL columns ahead of the in-order accumulation, which keeps the
 // reference's sequential summation order => bit-identical results.
 // Algorithmic HBM bytes: stored_elements*(sizeof(T)+sizeof(I)) + 2 n sizeof(T).
+// The product kernels are written once for both formats: they are templated on the struct that says
+// where a row's slots live (fmt_rows.hpp), and launch_fmt picks the kernel for both.
 #include <limits>
+#include <type_traits>
 
 #include "common.hpp"
-#include "csr_spmv_multi.hpp"
+#include "csr_spmv_pipe.hpp"
+#include "fmt_rows.hpp"
 #include "scan.hpp"
 
 namespace gkoc {
@@ -91,15 +95,80 @@ __device__ __forceinline__ T fmt_row_sum(T sum, int64_t len, int64_t first,
     return sum;
 }
 
+// The same for a chunk of NR right-hand sides: the row's entries are read ONCE, the NR
+// values b[col, jcol[0..NR)) of an entry are neighbours in the row-major b (one cache
+// line), and NR sums are carried; per column the products are added in column order,
+// so every column is bit-identical to the single-column kernels.  jcol = column behind slot jj
+// (slots past nrhs repeat the last column and are not stored).
+template <typename T, typename I, bool ADV, int NR>
+__device__ __forceinline__ void fmt_row_sum_multi(T (&sum)[NR], int64_t len, int64_t first,
+                                                  int64_t step, const I* __restrict__ cols,
+                                                  const T* __restrict__ vals,
+                                                  const T* __restrict__ b, int64_t ldb,
+                                                  const int (&jcol)[NR], T alpha)
+{
+    constexpr int U = 4;
+    const int64_t full = len / U * U;
+    T v0[U], v1[U];
+    I c0[U], c1[U];
+    if (full > 0) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            v0[u] = vals[first + u * step];
+            c0[u] = cols[first + u * step];
+        }
+    }
+    int64_t i = 0;
+    while (i < full) {
+        T xv[U][NR];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const T* __restrict__ brow = b + int64_t(c0[u] >= 0 ? c0[u] : I(0)) * ldb;
+#pragma unroll
+            for (int jj = 0; jj < NR; ++jj) xv[u][jj] = c0[u] >= 0 ? brow[jcol[jj]] : T(0);
+        }
+        const int64_t nx = i + U < full ? i + U : i;  // last chunk: harmless reload
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            v1[u] = vals[first + (nx + u) * step];
+            c1[u] = cols[first + (nx + u) * step];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+#pragma unroll
+            for (int jj = 0; jj < NR; ++jj) {
+                const T t = ADV ? (alpha * v0[u]) * xv[u][jj] : v0[u] * xv[u][jj];
+                sum[jj] = c0[u] >= 0 ? sum[jj] + t : sum[jj];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            v0[u] = v1[u];
+            c0[u] = c1[u];
+        }
+        i += U;
+    }
+    for (; i < len; ++i) {
+        const I cc = cols[first + i * step];
+        if (cc >= 0) {
+            const T v = vals[first + i * step];
+            const T* __restrict__ brow = b + int64_t(cc) * ldb;
+#pragma unroll
+            for (int jj = 0; jj < NR; ++jj) {
+                const T xv = brow[jcol[jj]];
+                sum[jj] += ADV ? (alpha * v) * xv : v * xv;
+            }
+        }
+    }
+}
+
 // ELL / SELL-P SpMV with several right-hand sides: lane = row, one pass over the
-// row's entries per chunk of NR columns (SELL: slice_sets != nullptr)
-template <typename T, typename I, bool ADV, int NR, bool SELL>
+// row's entries per chunk of NR columns (L: ell_rows or sellp_rows)
+template <typename T, typename I, bool ADV, int NR, typename L>
 __global__ __launch_bounds__(256) void fmt_spmv_multi_kernel(
-    int64_t n_rows, int64_t k_per_row, int64_t stride, int64_t slice_size,
-    const uint64_t* __restrict__ slice_sets, const uint64_t* __restrict__ slice_lengths,
-    const I* __restrict__ cols, const T* __restrict__ vals, const T* __restrict__ b,
-    int64_t ldb, T* __restrict__ c, int64_t ldc, int nrhs, const T* __restrict__ alpha_p,
-    const T* __restrict__ beta_p, int64_t xcd_chunk = 0)
+    int64_t n_rows, L lay, const I* __restrict__ cols, const T* __restrict__ vals,
+    const T* __restrict__ b, int64_t ldb, T* __restrict__ c, int64_t ldc, int nrhs,
+    const T* __restrict__ alpha_p, const T* __restrict__ beta_p, int64_t xcd_chunk)
 {
     const int64_t row = xcd_chunked_block(blockIdx.x, gridDim.x, xcd_chunk) * 256 + threadIdx.x;
     if (row >= n_rows) return;
@@ -108,13 +177,8 @@ __global__ __launch_bounds__(256) void fmt_spmv_multi_kernel(
         alpha = alpha_p[0];
         beta = beta_p[0];
     }
-    int64_t len = k_per_row, first = row, step = stride;
-    if (SELL) {
-        const int64_t slice = row / slice_size;
-        len = int64_t(slice_lengths[slice]);
-        first = int64_t(slice_sets[slice]) * slice_size + (row - slice * slice_size);
-        step = slice_size;
-    }
+    int64_t len, first, step;
+    lay.locate(row, len, first, step);
     for (int j0 = 0; j0 < nrhs; j0 += NR) {
         int jcol[NR];
         T sum[NR];
@@ -122,9 +186,7 @@ __global__ __launch_bounds__(256) void fmt_spmv_multi_kernel(
         for (int jj = 0; jj < NR; ++jj) {
             jcol[jj] = j0 + jj < nrhs ? j0 + jj : nrhs - 1;
             sum[jj] = T(0);
-            if (ADV && beta != T(0)) {
-                sum[jj] = SELL ? c[row * ldc + jcol[jj]] * beta : beta * c[row * ldc + jcol[jj]];
-            }
+            if (ADV && beta != T(0)) sum[jj] = beta * c[row * ldc + jcol[jj]];
         }
         fmt_row_sum_multi<T, I, ADV, NR>(sum, len, first, step, cols, vals, b, ldb, jcol, alpha);
 #pragma unroll
@@ -145,13 +207,11 @@ __global__ __launch_bounds__(256) void fmt_spmv_multi_kernel(
 // columns) or 32 (four) contiguous 64 / 32 B runs.  The column index and value of an entry are
 // loaded by all lanes of its row (same address: one access).  Every (row, column) sum is still
 // formed by ONE lane in entry order, separate multiply and add: bit-identical to the reference.
-template <typename T, typename I, bool ADV, int NR, bool SELL, bool IDX32>
+template <typename T, typename I, bool ADV, int NR, typename L, bool IDX32>
 __global__ __launch_bounds__(256) void fmt_spmv_frag_kernel(
-    int64_t n_rows, int64_t k_per_row, int64_t stride, int64_t slice_size,
-    const uint64_t* __restrict__ slice_sets, const uint64_t* __restrict__ slice_lengths,
-    const I* __restrict__ cols, const T* __restrict__ vals, const T* __restrict__ b,
-    int64_t ldb, T* __restrict__ c, int64_t ldc, int nrhs, const T* __restrict__ alpha_p,
-    const T* __restrict__ beta_p, int64_t xcd_chunk)
+    int64_t n_rows, L lay, const I* __restrict__ cols, const T* __restrict__ vals,
+    const T* __restrict__ b, int64_t ldb, T* __restrict__ c, int64_t ldc, int nrhs,
+    const T* __restrict__ alpha_p, const T* __restrict__ beta_p, int64_t xcd_chunk)
 {
     static_assert(NR == 4 || NR == 8, "chunks of 4 or 8 columns");
     constexpr int LPR = NR / 2;      // lanes per row
@@ -175,15 +235,9 @@ __global__ __launch_bounds__(256) void fmt_spmv_frag_kernel(
     // (rocprofv3: TA busy 90 % of the kernel's cycles; profiles/r03_multi_rhs_pmc.txt).
     const int64_t nrow = row_base + lane;
     const int64_t nr = nrow < n_rows ? nrow : n_rows - 1;
-    int nlen = int(k_per_row);
-    int64_t nfirst = nr, step = stride;
-    if (SELL) {
-        const int64_t slice = nr / slice_size;
-        nlen = int(slice_lengths[slice]);
-        nfirst = int64_t(slice_sets[slice]) * slice_size + (nr - slice * slice_size);
-        step = slice_size;
-    }
-    if (nrow >= n_rows) nlen = 0;
+    int64_t len, nfirst, step;
+    lay.locate(nr, len, nfirst, step);
+    int nlen = nrow < n_rows ? int(len) : 0;
     // A lane without entries still loads (below) whenever another lane of its wave has some, and
     // the first slot of an EMPTY SELL-P slice need not exist: with no stored slice behind it,
     // slice_sets[slice] * slice_size + local lies up to slice_size - 1 elements past the end of
@@ -291,10 +345,9 @@ inline bool frag_layout(int64_t n_cols, int64_t nrhs, const T* b, int64_t ldb, c
 // read streams cost several times their byte share at the memory side, and
 // only a burst of >= 1 KB issued by ONE wave avoids it - a barrier that lines
 // up the 512 B stores of four waves does not)
-template <typename T, typename I, bool ADV, typename V = T>
-__global__ __launch_bounds__(256) void ell_spmv_kernel(
-    int64_t n_rows, int64_t k_per_row, int64_t stride,
-    const I* __restrict__ cols, const V* __restrict__ vals,
+template <typename T, typename I, bool ADV, typename L, typename V = T>
+__global__ __launch_bounds__(256) void fmt_spmv_kernel(
+    int64_t n_rows, L lay, const I* __restrict__ cols, const V* __restrict__ vals,
     const T* __restrict__ b, int64_t ldb, T* __restrict__ c, int64_t ldc,
     int nrhs, const T* __restrict__ alpha_p, const T* __restrict__ beta_p)
 {
@@ -308,64 +361,39 @@ __global__ __launch_bounds__(256) void ell_spmv_kernel(
     }
     for (int j = 0; j < nrhs; ++j) {
         const bool unit_b = ldb == 1 && j == 0;   // uniform: one of the two instances runs
+        int64_t len, first, step;
         T s0 = T(0), s1 = T(0);
         if (row0 < n_rows) {
+            lay.locate(row0, len, first, step);
             if (ADV && beta != T(0)) s0 = beta * c[row0 * ldc + j];
-            s0 = unit_b ? fmt_row_sum<T, I, ADV, true, V>(s0, k_per_row, row0, stride, cols, vals, b, ldb, j, alpha)
-                        : fmt_row_sum<T, I, ADV, false, V>(s0, k_per_row, row0, stride, cols, vals, b, ldb, j, alpha);
+            s0 = unit_b ? fmt_row_sum<T, I, ADV, true, V>(s0, len, first, step, cols, vals, b, ldb, j, alpha)
+                        : fmt_row_sum<T, I, ADV, false, V>(s0, len, first, step, cols, vals, b, ldb, j, alpha);
         }
         if (row1 < n_rows) {
+            lay.locate(row1, len, first, step);
             if (ADV && beta != T(0)) s1 = beta * c[row1 * ldc + j];
-            s1 = unit_b ? fmt_row_sum<T, I, ADV, true, V>(s1, k_per_row, row1, stride, cols, vals, b, ldb, j, alpha)
-                        : fmt_row_sum<T, I, ADV, false, V>(s1, k_per_row, row1, stride, cols, vals, b, ldb, j, alpha);
+            s1 = unit_b ? fmt_row_sum<T, I, ADV, true, V>(s1, len, first, step, cols, vals, b, ldb, j, alpha)
+                        : fmt_row_sum<T, I, ADV, false, V>(s1, len, first, step, cols, vals, b, ldb, j, alpha);
         }
         if (row0 < n_rows) c[row0 * ldc + j] = s0;
         if (row1 < n_rows) c[row1 * ldc + j] = s1;
     }
 }
 
-template <typename T, typename I, bool ADV>
-__global__ __launch_bounds__(256) void sellp_spmv_kernel(
-    int64_t n_rows, int64_t slice_size,
-    const uint64_t* __restrict__ slice_sets,
-    const uint64_t* __restrict__ slice_lengths, const I* __restrict__ cols,
-    const T* __restrict__ vals, const T* __restrict__ b, int64_t ldb,
-    T* __restrict__ c, int64_t ldc, int nrhs, const T* __restrict__ alpha_p,
-    const T* __restrict__ beta_p)
+// ------------------------------------------------------------- conversions
+// One row written into a column-major layout: slot j < ncols goes to base + j * step of the output,
+// the row's `len` entries from src_vals / src_cols (global memory or LDS), then padding (-1, 0).
+template <typename T, typename I>
+__device__ __forceinline__ void emit_row(int64_t ncols, int64_t len, const T* src_vals, const I* src_cols,
+                                         int64_t base, int64_t step, I* out_cols, T* out_vals)
 {
-    const int64_t wave = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
-    const int64_t rows[2] = {wave * 128 + (threadIdx.x & 63), wave * 128 + 64 + (threadIdx.x & 63)};
-    T alpha = T(1), beta = T(0);
-    if (ADV) {
-        alpha = alpha_p[0];
-        beta = beta_p[0];
-    }
-    for (int j = 0; j < nrhs; ++j) {
-        const bool unit_b = ldb == 1 && j == 0;   // uniform: one of the two instances runs
-        T sum[2] = {T(0), T(0)};
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int64_t row = rows[t];
-            if (row < n_rows) {
-                const int64_t slice = row / slice_size;
-                const int64_t local = row - slice * slice_size;
-                const int64_t len = int64_t(slice_lengths[slice]);
-                const int64_t base = int64_t(slice_sets[slice]) * slice_size + local;
-                if (ADV && beta != T(0)) sum[t] = c[row * ldc + j] * beta;
-                sum[t] = unit_b ? fmt_row_sum<T, I, ADV, true>(sum[t], len, base, slice_size, cols, vals,
-                                                               b, ldb, j, alpha)
-                                : fmt_row_sum<T, I, ADV>(sum[t], len, base, slice_size, cols, vals, b,
-                                                         ldb, j, alpha);
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            if (rows[t] < n_rows) c[rows[t] * ldc + j] = sum[t];
-        }
+    for (int64_t j = 0; j < ncols; ++j) {
+        const bool in = j < len;
+        out_vals[base + j * step] = in ? src_vals[j] : T(0);
+        out_cols[base + j * step] = in ? src_cols[j] : I(-1);
     }
 }
 
-// ------------------------------------------------------------- conversions
 template <typename T, typename I>
 __global__ __launch_bounds__(256) void csr_to_sellp_kernel(
     int64_t n_rows, int64_t slice_size, const I* __restrict__ row_ptrs,
@@ -382,11 +410,7 @@ __global__ __launch_bounds__(256) void csr_to_sellp_kernel(
     const int64_t base = int64_t(slice_sets[slice]) * slice_size + local;
     const int64_t a = row_ptrs[row];
     const int64_t len = row_ptrs[row + 1] - a;
-    for (int64_t i = 0; i < len_slice; ++i) {
-        const bool in = i < len;
-        s_vals[base + i * slice_size] = in ? vals[a + i] : T(0);
-        s_cols[base + i * slice_size] = in ? cols[a + i] : I(-1);
-    }
+    emit_row(len_slice, len, vals + a, cols + a, base, slice_size, s_cols, s_vals);
 }
 
 // Staged conversion of 64 consecutive rows per wave: the rows' contiguous CSR
@@ -436,19 +460,9 @@ __global__ __launch_bounds__(64) void csr_to_colmajor_staged_kernel(
         }
         wave_lds_sync();
         const int off = int(rs - K0);
-        if (valid) {
-            for (int64_t j = 0; j < ncols; ++j) {
-                const bool in = j < len;
-                out_vals[base + j * cstride] = in ? lv[off + int(j)] : T(0);
-                out_cols[base + j * cstride] = in ? lc[off + int(j)] : I(-1);
-            }
-        }
+        if (valid) emit_row(ncols, len, lv + off, lc + off, base, cstride, out_cols, out_vals);
     } else if (valid) {
-        for (int64_t j = 0; j < ncols; ++j) {
-            const bool in = j < len;
-            out_vals[base + j * cstride] = in ? vals[rs + j] : T(0);
-            out_cols[base + j * cstride] = in ? cols[rs + j] : I(-1);
-        }
+        emit_row(ncols, len, vals + rs, cols + rs, base, cstride, out_cols, out_vals);
     }
 }
 
@@ -567,145 +581,93 @@ __global__ __launch_bounds__(256) void fill_in_md_kernel(
 // these grids have no cap
 inline unsigned blocks_for(int64_t n) { return capped_grid(n, 256, no_grid_cap); }
 
-template <typename T, typename I, bool ADV>
-int launch_ell(gkoc_stream_t s, int64_t n_rows, int64_t n_cols, int64_t k,
-               int64_t stride, const T* alpha, const I* cols, const T* vals,
-               const T* b, int64_t ldb, const T* beta, T* c, int64_t ldc,
+// (the entries tell the structure cache about ptrs themselves: gkoc::csr_structure_written)
+template <typename I, typename P>
+int launch_idxs_to_ptrs(gkoc_stream_t s, int64_t num_idxs, const I* idxs, int64_t n, P* ptrs)
+{
+    GKOC_REQUIRE(num_idxs >= 0 && n >= 0, GKOC_E_INVALID, "negative size");
+    idxs_to_ptrs_kernel<I, P><<<dim3(blocks_for(num_idxs + 1)), dim3(256), 0, as_stream(s)>>>(num_idxs, idxs, n, ptrs);
+    GKOC_LAUNCH_OK();
+    return GKOC_OK;
+}
+
+// the scan of uint64_t counts (the scan kernels are instantiated for unsigned long long)
+inline int scan_u64(gkoc_stream_t s, uint64_t* counts, int64_t n)
+{
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "same width");
+    return device_exclusive_scan<unsigned long long>(as_stream(s), reinterpret_cast<unsigned long long*>(counts), n);
+}
+
+// The one launcher of the real products.  V != T (mixed precision: values float, vectors and
+// arithmetic double) and one column take the one-column kernel, column by column; two and more
+// columns take chunks of NR = 2, 4 or 8, in the fragment layout where frag_layout allows it.
+template <typename T, typename I, bool ADV, typename L, typename V>
+int launch_fmt(gkoc_stream_t s, int64_t n_rows, int64_t n_cols, L lay, const T* alpha, const I* cols,
+               const V* vals, const T* b, int64_t ldb, const T* beta, T* c, int64_t ldc, int64_t nrhs)
+{
+    if (n_rows == 0 || nrhs == 0) return GKOC_OK;
+    if (ADV) GKOC_REQUIRE(alpha && beta, GKOC_E_INVALID, "null alpha/beta");
+    if constexpr (std::is_same_v<V, T>) {
+        if (nrhs >= 2) {
+            const dim3 grid(unsigned(ceildiv(n_rows, 256)));
+            const int64_t chunk = tune_value(GKOC_TUNE_MULTI_XCD_CHUNK_ROWS) / 256;
+            const bool frag = frag_layout(n_cols, nrhs, b, ldb, c, ldc);
+            auto launch = [&](auto nr) {
+                constexpr int NR = decltype(nr)::value;
+                if constexpr (NR >= 4) {
+                    if (frag) {
+                        auto launch_frag = [&](auto idx32) {
+                            fmt_spmv_frag_kernel<T, I, ADV, NR, L, decltype(idx32)::value>
+                                <<<grid, dim3(256), 0, as_stream(s)>>>(n_rows, lay, cols, vals, b, ldb, c, ldc,
+                                                                       int(nrhs), alpha, beta, chunk);
+                        };
+                        if (n_cols * ldb < (int64_t(1) << 32)) {
+                            launch_frag(std::true_type{});
+                        } else {
+                            launch_frag(std::false_type{});
+                        }
+                        return;
+                    }
+                }
+                fmt_spmv_multi_kernel<T, I, ADV, NR, L><<<grid, dim3(256), 0, as_stream(s)>>>(
+                    n_rows, lay, cols, vals, b, ldb, c, ldc, int(nrhs), alpha, beta, chunk);
+            };
+            if (nrhs == 2) {
+                launch(std::integral_constant<int, 2>{});
+            } else if (nrhs <= 4) {
+                launch(std::integral_constant<int, 4>{});
+            } else {
+                // wider blocks: 8 columns per pass use every gathered b line in full
+                launch(std::integral_constant<int, 8>{});
+            }
+            GKOC_LAUNCH_OK();
+            return GKOC_OK;
+        }
+    }
+    fmt_spmv_kernel<T, I, ADV, L, V><<<dim3(unsigned(ceildiv(n_rows, 512))), dim3(256), 0, as_stream(s)>>>(
+        n_rows, lay, cols, vals, b, ldb, c, ldc, int(nrhs), alpha, beta);
+    GKOC_LAUNCH_OK();
+    return GKOC_OK;
+}
+
+template <typename T, typename I, bool ADV, typename V = T>
+int launch_ell(gkoc_stream_t s, int64_t n_rows, int64_t n_cols, int64_t k, int64_t stride, const T* alpha,
+               const I* cols, const V* vals, const T* b, int64_t ldb, const T* beta, T* c, int64_t ldc,
                int64_t nrhs)
 {
-    GKOC_REQUIRE(n_rows >= 0 && k >= 0 && nrhs >= 0 && stride >= n_rows,
-                 GKOC_E_INVALID, "bad ELL dimensions");
-    if (n_rows == 0 || nrhs == 0) return GKOC_OK;
-    if (ADV) GKOC_REQUIRE(alpha && beta, GKOC_E_INVALID, "null alpha/beta");
-    if (nrhs >= 2 && frag_layout(n_cols, nrhs, b, ldb, c, ldc)) {
-        const dim3 grid(unsigned(ceildiv(n_rows, 256)));
-        const int64_t chunk = tune_value(GKOC_TUNE_MULTI_XCD_CHUNK_ROWS) / 256;
-        const bool idx32 = n_cols * ldb < (int64_t(1) << 32);
-#define GKOC_LAUNCH_FRAG(NR_)                                                                    \
-    do {                                                                                         \
-        if (idx32) {                                                                             \
-            fmt_spmv_frag_kernel<T, I, ADV, NR_, false, true><<<grid, dim3(256), 0, as_stream(s)>>>( \
-                n_rows, k, stride, 0, nullptr, nullptr, cols, vals, b, ldb, c, ldc, int(nrhs),   \
-                alpha, beta, chunk);                                                             \
-        } else {                                                                                 \
-            fmt_spmv_frag_kernel<T, I, ADV, NR_, false, false><<<grid, dim3(256), 0, as_stream(s)>>>( \
-                n_rows, k, stride, 0, nullptr, nullptr, cols, vals, b, ldb, c, ldc, int(nrhs),   \
-                alpha, beta, chunk);                                                             \
-        }                                                                                        \
-    } while (0)
-        if (nrhs <= 4) {
-            GKOC_LAUNCH_FRAG(4);
-        } else {
-            GKOC_LAUNCH_FRAG(8);
-        }
-#undef GKOC_LAUNCH_FRAG
-        GKOC_LAUNCH_OK();
-        return GKOC_OK;
-    }
-    if (nrhs >= 2) {
-        const dim3 grid(unsigned(ceildiv(n_rows, 256)));
-        if (nrhs == 2) {
-            fmt_spmv_multi_kernel<T, I, ADV, 2, false><<<grid, dim3(256), 0, as_stream(s)>>>(
-                n_rows, k, stride, 0, nullptr, nullptr, cols, vals, b, ldb, c, ldc, int(nrhs),
-                alpha, beta, tune_value(GKOC_TUNE_MULTI_XCD_CHUNK_ROWS) / 256);
-        } else if (nrhs <= 4) {
-            fmt_spmv_multi_kernel<T, I, ADV, 4, false><<<grid, dim3(256), 0, as_stream(s)>>>(
-                n_rows, k, stride, 0, nullptr, nullptr, cols, vals, b, ldb, c, ldc, int(nrhs),
-                alpha, beta, tune_value(GKOC_TUNE_MULTI_XCD_CHUNK_ROWS) / 256);
-        } else {
-            // wider blocks: 8 columns per pass use every gathered b line in full
-            fmt_spmv_multi_kernel<T, I, ADV, 8, false><<<grid, dim3(256), 0, as_stream(s)>>>(
-                n_rows, k, stride, 0, nullptr, nullptr, cols, vals, b, ldb, c, ldc, int(nrhs),
-                alpha, beta, tune_value(GKOC_TUNE_MULTI_XCD_CHUNK_ROWS) / 256);
-        }
-        GKOC_LAUNCH_OK();
-        return GKOC_OK;
-    }
-    ell_spmv_kernel<T, I, ADV><<<dim3(unsigned(ceildiv(n_rows, 512))), dim3(256), 0, as_stream(s)>>>(
-        n_rows, k, stride, cols, vals, b, ldb, c, ldc, int(nrhs), alpha, beta);
-    GKOC_LAUNCH_OK();
-    return GKOC_OK;
-}
-
-// mixed precision (values float, vectors and arithmetic double): the one-column kernel, column by column
-template <typename T, typename V, typename I, bool ADV>
-int launch_ell_mixed(gkoc_stream_t s, int64_t n_rows, int64_t k, int64_t stride, const T* alpha,
-                     const I* cols, const V* vals, const T* b, int64_t ldb, const T* beta, T* c,
-                     int64_t ldc, int64_t nrhs)
-{
-    GKOC_REQUIRE(n_rows >= 0 && k >= 0 && nrhs >= 0 && stride >= n_rows, GKOC_E_INVALID,
-                 "bad ELL dimensions");
-    if (n_rows == 0 || nrhs == 0) return GKOC_OK;
-    if (ADV) GKOC_REQUIRE(alpha && beta, GKOC_E_INVALID, "null alpha/beta");
-    ell_spmv_kernel<T, I, ADV, V><<<dim3(unsigned(ceildiv(n_rows, 512))), dim3(256), 0, as_stream(s)>>>(
-        n_rows, k, stride, cols, vals, b, ldb, c, ldc, int(nrhs), alpha, beta);
-    GKOC_LAUNCH_OK();
-    return GKOC_OK;
+    GKOC_REQUIRE(n_rows >= 0 && k >= 0 && nrhs >= 0 && stride >= n_rows, GKOC_E_INVALID, "bad ELL dimensions");
+    return launch_fmt<T, I, ADV>(s, n_rows, n_cols, ell_rows{k, stride}, alpha, cols, vals, b, ldb, beta, c,
+                                 ldc, nrhs);
 }
 
 template <typename T, typename I, bool ADV>
-int launch_sellp(gkoc_stream_t s, int64_t n_rows, int64_t n_cols,
-                 int64_t slice_size, const T* alpha, const uint64_t* slice_sets,
-                 const uint64_t* slice_lengths, const I* cols, const T* vals,
-                 const T* b, int64_t ldb, const T* beta, T* c, int64_t ldc,
-                 int64_t nrhs)
+int launch_sellp(gkoc_stream_t s, int64_t n_rows, int64_t n_cols, int64_t slice_size, const T* alpha,
+                 const uint64_t* slice_sets, const uint64_t* slice_lengths, const I* cols, const T* vals,
+                 const T* b, int64_t ldb, const T* beta, T* c, int64_t ldc, int64_t nrhs)
 {
-    GKOC_REQUIRE(n_rows >= 0 && slice_size >= 1 && nrhs >= 0, GKOC_E_INVALID,
-                 "bad SELL-P dimensions");
-    if (n_rows == 0 || nrhs == 0) return GKOC_OK;
-    if (ADV) GKOC_REQUIRE(alpha && beta, GKOC_E_INVALID, "null alpha/beta");
-    if (nrhs >= 2 && frag_layout(n_cols, nrhs, b, ldb, c, ldc)) {
-        const dim3 grid(unsigned(ceildiv(n_rows, 256)));
-        const int64_t chunk = tune_value(GKOC_TUNE_MULTI_XCD_CHUNK_ROWS) / 256;
-        const bool idx32 = n_cols * ldb < (int64_t(1) << 32);
-#define GKOC_LAUNCH_FRAG(NR_)                                                                    \
-    do {                                                                                         \
-        if (idx32) {                                                                             \
-            fmt_spmv_frag_kernel<T, I, ADV, NR_, true, true><<<grid, dim3(256), 0, as_stream(s)>>>( \
-                n_rows, 0, 0, slice_size, slice_sets, slice_lengths, cols, vals, b, ldb, c, ldc,     \
-                int(nrhs), alpha, beta, chunk);                                                  \
-        } else {                                                                                 \
-            fmt_spmv_frag_kernel<T, I, ADV, NR_, true, false><<<grid, dim3(256), 0, as_stream(s)>>>( \
-                n_rows, 0, 0, slice_size, slice_sets, slice_lengths, cols, vals, b, ldb, c, ldc,     \
-                int(nrhs), alpha, beta, chunk);                                                  \
-        }                                                                                        \
-    } while (0)
-        if (nrhs <= 4) {
-            GKOC_LAUNCH_FRAG(4);
-        } else {
-            GKOC_LAUNCH_FRAG(8);
-        }
-#undef GKOC_LAUNCH_FRAG
-        GKOC_LAUNCH_OK();
-        return GKOC_OK;
-    }
-    if (nrhs >= 2) {
-        const dim3 grid(unsigned(ceildiv(n_rows, 256)));
-        if (nrhs == 2) {
-            fmt_spmv_multi_kernel<T, I, ADV, 2, true><<<grid, dim3(256), 0, as_stream(s)>>>(
-                n_rows, 0, 0, slice_size, slice_sets, slice_lengths, cols, vals, b, ldb, c, ldc,
-                int(nrhs), alpha, beta,
-                tune_value(GKOC_TUNE_MULTI_XCD_CHUNK_ROWS) / 256);
-        } else if (nrhs <= 4) {
-            fmt_spmv_multi_kernel<T, I, ADV, 4, true><<<grid, dim3(256), 0, as_stream(s)>>>(
-                n_rows, 0, 0, slice_size, slice_sets, slice_lengths, cols, vals, b, ldb, c, ldc,
-                int(nrhs), alpha, beta,
-                tune_value(GKOC_TUNE_MULTI_XCD_CHUNK_ROWS) / 256);
-        } else {
-            fmt_spmv_multi_kernel<T, I, ADV, 8, true><<<grid, dim3(256), 0, as_stream(s)>>>(
-                n_rows, 0, 0, slice_size, slice_sets, slice_lengths, cols, vals, b, ldb, c, ldc,
-                int(nrhs), alpha, beta,
-                tune_value(GKOC_TUNE_MULTI_XCD_CHUNK_ROWS) / 256);
-        }
-        GKOC_LAUNCH_OK();
-        return GKOC_OK;
-    }
-    sellp_spmv_kernel<T, I, ADV>
-        <<<dim3(unsigned(ceildiv(n_rows, 512))), dim3(256), 0, as_stream(s)>>>(
-            n_rows, slice_size, slice_sets, slice_lengths, cols, vals, b, ldb, c,
-            ldc, int(nrhs), alpha, beta);
-    GKOC_LAUNCH_OK();
-    return GKOC_OK;
+    GKOC_REQUIRE(n_rows >= 0 && slice_size >= 1 && nrhs >= 0, GKOC_E_INVALID, "bad SELL-P dimensions");
+    return launch_fmt<T, I, ADV>(s, n_rows, n_cols, sellp_rows{slice_size, slice_sets, slice_lengths}, alpha,
+                                 cols, vals, b, ldb, beta, c, ldc, nrhs);
 }
 
 }  // namespace
@@ -719,18 +681,16 @@ using namespace gkoc;
                                               const float* vals, const double* b, int64_t ldb,     \
                                               double* c, int64_t ldc, int64_t nrhs)                \
     {                                                                                              \
-        (void)n_cols;                                                                              \
-        return launch_ell_mixed<double, float, I, false>(s, n_rows, k, stride, nullptr, cols,      \
-                                                         vals, b, ldb, nullptr, c, ldc, nrhs);     \
+        return launch_ell<double, I, false, float>(s, n_rows, n_cols, k, stride, nullptr, cols,    \
+                                                   vals, b, ldb, nullptr, c, ldc, nrhs);           \
     }                                                                                              \
     extern "C" int gkoc_ell_advanced_spmv_f32_f64_##IN(                                            \
         gkoc_stream_t s, int64_t n_rows, int64_t n_cols, int64_t k, int64_t stride,                \
         const double* alpha, const I* cols, const float* vals, const double* b, int64_t ldb,       \
         const double* beta, double* c, int64_t ldc, int64_t nrhs)                                  \
     {                                                                                              \
-        (void)n_cols;                                                                              \
-        return launch_ell_mixed<double, float, I, true>(s, n_rows, k, stride, alpha, cols, vals,   \
-                                                        b, ldb, beta, c, ldc, nrhs);               \
+        return launch_ell<double, I, true, float>(s, n_rows, n_cols, k, stride, alpha, cols, vals, \
+                                                  b, ldb, beta, c, ldc, nrhs);                     \
     }
 GKOC_DEF_ELL_MIXED(int32_t, i32)
 GKOC_DEF_ELL_MIXED(int64_t, i64)
@@ -812,7 +772,8 @@ GKOC_DEF_ELL_MIXED(int64_t, i64)
         return GKOC_OK;                                                        \
     }
 
-#define GKOC_DEF_MD(T, TN, I, IN)                                              \
+// (all eight type pairs)
+#define GKOC_DEF_AOS_TO_SOA(T, TN, I, IN)                                      \
     extern "C" int gkoc_aos_to_soa_##TN##_##IN(gkoc_stream_t s, int64_t nnz,   \
                                                const void* entries,            \
                                                I* row_idxs, I* col_idxs,       \
@@ -820,53 +781,39 @@ GKOC_DEF_ELL_MIXED(int64_t, i64)
     {                                                                          \
         gkoc::csr_structure_written(row_idxs); gkoc::csr_structure_written(col_idxs); \
         if (nnz <= 0) return GKOC_OK;                                          \
-        int64_t nb = ceildiv(nnz, 256);                                        \
-        if (nb > max_stream_blocks) nb = max_stream_blocks;                    \
         aos_to_soa_kernel<T, I>                                                \
-            <<<dim3(unsigned(nb)), dim3(256), 0, as_stream(s)>>>(              \
+            <<<dim3(capped_grid(nnz, 256, max_stream_blocks)), dim3(256), 0,   \
+               as_stream(s)>>>(                                                \
                 nnz, static_cast<const md_entry<T, I>*>(entries), row_idxs,    \
                 col_idxs, vals);                                               \
         GKOC_LAUNCH_OK();                                                      \
         return GKOC_OK;                                                        \
-    }                                                                          \
+    }
+// (the four real ones)
+#define GKOC_DEF_FILL_IN_MD(T, TN, I, IN)                                      \
     extern "C" int gkoc_dense_fill_in_matrix_data_##TN##_##IN(                 \
         gkoc_stream_t s, int64_t nnz, const I* row_idxs, const I* col_idxs,    \
         const T* vals, T* out, int64_t ld_out)                                 \
     {                                                                          \
         if (nnz <= 0) return GKOC_OK;                                          \
-        int64_t nb = ceildiv(nnz, 256);                                        \
-        if (nb > max_stream_blocks) nb = max_stream_blocks;                    \
         fill_in_md_kernel<T, I>                                                \
-            <<<dim3(unsigned(nb)), dim3(256), 0, as_stream(s)>>>(              \
-                nnz, row_idxs, col_idxs, vals, out, ld_out);                   \
+            <<<dim3(capped_grid(nnz, 256, max_stream_blocks)), dim3(256), 0,   \
+               as_stream(s)>>>(nnz, row_idxs, col_idxs, vals, out, ld_out);    \
         GKOC_LAUNCH_OK();                                                      \
         return GKOC_OK;                                                        \
     }
-#define GKOC_DEF_COMPLEX_MD(T, TN, I, IN)                                       \
-    extern "C" int gkoc_aos_to_soa_##TN##_##IN(gkoc_stream_t s, int64_t nnz,   \
-                                               const void* entries,            \
-                                               I* row_idxs, I* col_idxs,       \
-                                               T* vals)                        \
-    {                                                                          \
-        gkoc::csr_structure_written(row_idxs); gkoc::csr_structure_written(col_idxs); \
-        if (nnz <= 0) return GKOC_OK;                                          \
-        int64_t nb = ceildiv(nnz, 256);                                        \
-        if (nb > max_stream_blocks) nb = max_stream_blocks;                    \
-        aos_to_soa_kernel<T, I>                                                \
-            <<<dim3(unsigned(nb)), dim3(256), 0, as_stream(s)>>>(              \
-                nnz, static_cast<const md_entry<T, I>*>(entries), row_idxs,    \
-                col_idxs, vals);                                               \
-        GKOC_LAUNCH_OK();                                                      \
-        return GKOC_OK;                                                        \
-    }
-GKOC_DEF_COMPLEX_MD(gkoc_c128, c128, int32_t, i32)
-GKOC_DEF_COMPLEX_MD(gkoc_c128, c128, int64_t, i64)
-GKOC_DEF_COMPLEX_MD(gkoc_c64, c64, int32_t, i32)
-GKOC_DEF_COMPLEX_MD(gkoc_c64, c64, int64_t, i64)
-GKOC_DEF_MD(double, f64, int32_t, i32)
-GKOC_DEF_MD(double, f64, int64_t, i64)
-GKOC_DEF_MD(float, f32, int32_t, i32)
-GKOC_DEF_MD(float, f32, int64_t, i64)
+GKOC_DEF_AOS_TO_SOA(gkoc_c128, c128, int32_t, i32)
+GKOC_DEF_AOS_TO_SOA(gkoc_c128, c128, int64_t, i64)
+GKOC_DEF_AOS_TO_SOA(gkoc_c64, c64, int32_t, i32)
+GKOC_DEF_AOS_TO_SOA(gkoc_c64, c64, int64_t, i64)
+GKOC_DEF_AOS_TO_SOA(double, f64, int32_t, i32)
+GKOC_DEF_AOS_TO_SOA(double, f64, int64_t, i64)
+GKOC_DEF_AOS_TO_SOA(float, f32, int32_t, i32)
+GKOC_DEF_AOS_TO_SOA(float, f32, int64_t, i64)
+GKOC_DEF_FILL_IN_MD(double, f64, int32_t, i32)
+GKOC_DEF_FILL_IN_MD(double, f64, int64_t, i64)
+GKOC_DEF_FILL_IN_MD(float, f32, int32_t, i32)
+GKOC_DEF_FILL_IN_MD(float, f32, int64_t, i64)
 
 GKOC_DEF_FMT(double, f64, int32_t, i32)
 GKOC_DEF_FMT(double, f64, int64_t, i64)
@@ -891,10 +838,9 @@ GKOC_DEF_FMT_CONVERT(gkoc_c64, c64, int64_t, i64)
         unsigned long long* d = nullptr;                                       \
         GKOC_TRY(scratch_malloc(as_stream(s), reinterpret_cast<void**>(&d), 8)); \
         GKOC_HIP(hipMemsetAsync(d, 0, 8, as_stream(s)));                       \
-        int64_t nb = ceildiv(n_rows, 256);                                     \
-        if (nb > max_stream_blocks) nb = max_stream_blocks;                    \
-        max_row_nnz_kernel<I><<<dim3(unsigned(nb)), dim3(256), 0, as_stream(s)>>>( \
-            n_rows, row_ptrs, d);                                              \
+        max_row_nnz_kernel<I>                                                  \
+            <<<dim3(capped_grid(n_rows, 256, max_stream_blocks)), dim3(256), 0, \
+               as_stream(s)>>>(n_rows, row_ptrs, d);                           \
         GKOC_LAUNCH_OK();                                                      \
         unsigned long long h = 0;                                              \
         GKOC_HIP(hipMemcpyAsync(&h, d, 8, hipMemcpyDeviceToHost, as_stream(s))); \
@@ -923,9 +869,7 @@ GKOC_DEF_FMT_CONVERT(gkoc_c64, c64, int64_t, i64)
         }                                                                      \
         GKOC_HIP(hipMemsetAsync(slice_sets + n_slices, 0, sizeof(uint64_t),    \
                                 as_stream(s)));                                \
-        return device_exclusive_scan<unsigned long long>(                      \
-            as_stream(s), reinterpret_cast<unsigned long long*>(slice_sets),   \
-            n_slices + 1);                                                     \
+        return scan_u64(s, slice_sets, n_slices + 1);                          \
     }                                                                          \
     extern "C" int gkoc_convert_ptrs_to_sizes_##IN(                            \
         gkoc_stream_t s, int64_t n, const I* ptrs, uint64_t* sizes)            \
@@ -941,12 +885,7 @@ GKOC_DEF_FMT_CONVERT(gkoc_c64, c64, int64_t, i64)
         gkoc_stream_t s, int64_t num_idxs, const I* idxs, int64_t n, I* ptrs)  \
     {                                                                          \
         gkoc::csr_structure_written(ptrs);                                     \
-        GKOC_REQUIRE(num_idxs >= 0 && n >= 0, GKOC_E_INVALID, "negative size"); \
-        idxs_to_ptrs_kernel<I>                                                 \
-            <<<dim3(blocks_for(num_idxs + 1)), dim3(256), 0, as_stream(s)>>>(  \
-                num_idxs, idxs, n, ptrs);                                      \
-        GKOC_LAUNCH_OK();                                                      \
-        return GKOC_OK;                                                        \
+        return launch_idxs_to_ptrs(s, num_idxs, idxs, n, ptrs);                \
     }                                                                          \
     extern "C" int gkoc_prefix_sum_nonnegative_##IN(gkoc_stream_t s,           \
                                                     I* counts, int64_t n)      \
@@ -971,9 +910,7 @@ GKOC_DEF_FMT_CONVERT(gkoc_c64, c64, int64_t, i64)
     {                                                                          \
         if (n <= 0) return GKOC_OK;                                            \
         gkoc::csr_structure_written(data, size_t(n) * sizeof(I));              \
-        int64_t nb = ceildiv(n, 256);                                          \
-        if (nb > max_stream_blocks) nb = max_stream_blocks;                    \
-        fill_idx_kernel<I><<<dim3(unsigned(nb)), dim3(256), 0, as_stream(s)>>>( \
+        fill_idx_kernel<I><<<dim3(capped_grid(n, 256, max_stream_blocks)), dim3(256), 0, as_stream(s)>>>( \
             n, data, value, false);                                            \
         GKOC_LAUNCH_OK();                                                      \
         return GKOC_OK;                                                        \
@@ -983,9 +920,7 @@ GKOC_DEF_FMT_CONVERT(gkoc_c64, c64, int64_t, i64)
     {                                                                          \
         if (n <= 0) return GKOC_OK;                                            \
         gkoc::csr_structure_written(data, size_t(n) * sizeof(I));              \
-        int64_t nb = ceildiv(n, 256);                                          \
-        if (nb > max_stream_blocks) nb = max_stream_blocks;                    \
-        fill_idx_kernel<I><<<dim3(unsigned(nb)), dim3(256), 0, as_stream(s)>>>( \
+        fill_idx_kernel<I><<<dim3(capped_grid(n, 256, max_stream_blocks)), dim3(256), 0, as_stream(s)>>>( \
             n, data, I(0), true);                                              \
         GKOC_LAUNCH_OK();                                                      \
         return GKOC_OK;                                                        \
@@ -1008,9 +943,7 @@ extern "C" int gkoc_narrow_i64_to_i32(gkoc_stream_t s, int64_t n, const int64_t*
 {
     if (n <= 0) return GKOC_OK;
     GKOC_REQUIRE(in && out, GKOC_E_INVALID, "null pointer");
-    int64_t nb = ceildiv(n, 256);
-    if (nb > max_stream_blocks) nb = max_stream_blocks;
-    narrow_i64_kernel<<<dim3(unsigned(nb)), dim3(256), 0, as_stream(s)>>>(n, in, out);
+    narrow_i64_kernel<<<dim3(capped_grid(n, 256, max_stream_blocks)), dim3(256), 0, as_stream(s)>>>(n, in, out);
     GKOC_LAUNCH_OK();
     return GKOC_OK;
 }
@@ -1021,22 +954,14 @@ extern "C" int gkoc_convert_idxs_to_ptrs_i32_i64(gkoc_stream_t s, int64_t num_id
                                                  const int32_t* idxs, int64_t n, int64_t* ptrs)
 {
     gkoc::csr_structure_written(ptrs);
-    GKOC_REQUIRE(num_idxs >= 0 && n >= 0, GKOC_E_INVALID, "negative size");
-    idxs_to_ptrs_kernel<int32_t, int64_t>
-        <<<dim3(blocks_for(num_idxs + 1)), dim3(256), 0, as_stream(s)>>>(num_idxs, idxs, n, ptrs);
-    GKOC_LAUNCH_OK();
-    return GKOC_OK;
+    return launch_idxs_to_ptrs(s, num_idxs, idxs, n, ptrs);
 }
 
 extern "C" int gkoc_convert_idxs_to_ptrs_i64_i32(gkoc_stream_t s, int64_t num_idxs,
                                                  const int64_t* idxs, int64_t n, int32_t* ptrs)
 {
     gkoc::csr_structure_written(ptrs);
-    GKOC_REQUIRE(num_idxs >= 0 && n >= 0, GKOC_E_INVALID, "negative size");
-    idxs_to_ptrs_kernel<int64_t, int32_t>
-        <<<dim3(blocks_for(num_idxs + 1)), dim3(256), 0, as_stream(s)>>>(num_idxs, idxs, n, ptrs);
-    GKOC_LAUNCH_OK();
-    return GKOC_OK;
+    return launch_idxs_to_ptrs(s, num_idxs, idxs, n, ptrs);
 }
 
 extern "C" int gkoc_prefix_sum_nonnegative_checked_u64(gkoc_stream_t s, uint64_t* counts,
@@ -1046,13 +971,11 @@ extern "C" int gkoc_prefix_sum_nonnegative_checked_u64(gkoc_stream_t s, uint64_t
     const int rc = scan_overflows(as_stream(s), counts, n - 1, 8, ~0ull, &over);
     if (rc != GKOC_OK) return rc;
     GKOC_REQUIRE(!over, GKOC_E_OVERFLOW, "prefix sum overflows uint64_t");
-    return device_exclusive_scan<unsigned long long>(
-        as_stream(s), reinterpret_cast<unsigned long long*>(counts), n);
+    return scan_u64(s, counts, n);
 }
 
 extern "C" int gkoc_prefix_sum_nonnegative_u64(gkoc_stream_t s, uint64_t* counts,
                                                int64_t n)
 {
-    return device_exclusive_scan<unsigned long long>(
-        as_stream(s), reinterpret_cast<unsigned long long*>(counts), n);
+    return scan_u64(s, counts, n);
 }

@@ -212,7 +212,8 @@ COMPLEX_SCALARS = (None, (0.5 - 2j, -1 + 0.5j), (0.5 - 2j, 0.0))
 
 
 def branch_of(n_cols, nrhs, ldb, ldc, b_ptr, c_ptr, itemsize):
-    """the launcher's own conditions (formats.hip, launch_ell / launch_sellp and frag_layout)"""
+    """the launcher's own conditions (formats.hip: launch_fmt, which launch_ell and launch_sellp both end in, and
+    frag_layout)"""
     frag = n_cols > 0 and nrhs >= 3 and ldb % 2 == 0 and ldc % 2 == 0 and \
         b_ptr % (2 * itemsize) == 0 and c_ptr % (2 * itemsize) == 0
     if nrhs == 1:

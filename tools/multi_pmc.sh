@@ -25,7 +25,7 @@ import csv, glob, os, re, sys
 from collections import defaultdict
 root = sys.argv[1]
 def short(k):
-    m = re.search(r"(fmt_spmv_multi_kernel|fmt_spmv_frag_kernel|csr_spmv_frag_kernel|csr_spmv_multi_kernel|csr_spmv_rowmulti_kernel|ell_spmv\w*|csr_spmv_pipe3_kernel)<([^>]*)>", k)
+    m = re.search(r"(fmt_spmv_multi_kernel|fmt_spmv_frag_kernel|csr_spmv_frag_kernel|csr_spmv_multi_kernel|csr_spmv_rowmulti_kernel|fmt_spmv_kernel|ell_spmv\w*|csr_spmv_pipe3_kernel)<([^>]*)>", k)
     if not m: return None
     return m.group(1) + "<" + m.group(2).replace("double, int, ", "") + ">"
 for d in sorted(glob.glob(os.path.join(root, "pmc_*"))):
